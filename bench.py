@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric (G1 scalar-muls/sec + pairings/sec) on BASELINE.json's configs.
 
-    python bench.py [--config 2|3|4|5] --gpus N --steps K --warmup W
+    python bench.py [--config 2|3|4|5] --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 --config (SURVEY.md 8d numbering; default 2, the configuration BASELINE.json's metric is quoted on):
@@ -17,12 +17,19 @@ host Horner tail and, for N > 1, ONE all-gather of the per-rank partial sums ove
 (config 4: the G1 and the G2 MSM of the step are both in flight, their partials share the all-gather).  Timed
 protocol: W warm-up steps, then exactly K steps, ONE step in flight at a time, bracketed by barrier +
 synchronize; `value` = units of all ranks / max over ranks of the K-step time -- protocol (a), inputs resident in HBM
-when the timed region starts.  `extra` carries median / min of the K per-step times and, measured after the timed
-region without any flag: protocol (b) (resident bases, scalars from host memory per call: mlhip_bases_msm), protocol
-(c) (points and scalars from host memory: mlhip_msm_g1, what the reference's MultiScalarMul maps to), the
-skewed-scalar MSM (all scalars < 2^32, 1 % duplicated pairs), the same steps issued two-deep on two plans and streams,
-and (config 2) the 65 536-pairing batch.  The PCIe-inclusive rates are never `value`.  --kernels-only skips every
-extra and the CPU baseline, so that a rocprofv3 run of it averages exactly the timed steps' kernels.
+when the timed region starts; `ms_per_step` = that time / K.  `extra` carries median / min of the K per-step times.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  --full adds, measured after the timed
+region: protocol (b) (resident bases, scalars from host memory per call: mlhip_bases_msm), protocol (c) (points and
+scalars from host memory: mlhip_msm_g1, what the reference's MultiScalarMul maps to), the skewed-scalar MSM (all
+scalars < 2^32, 1 % duplicated pairs), the same steps issued two-deep on two plans and streams, (config 2) the
+65 536-pairing batch, the CPU baseline, and (config 4 / --pipelined) the per-kernel times from a separate one-MSM-at-a-time
+pass.  The PCIe-inclusive rates are never `value`.  --kernels-only (with or without --full) skips every extra and the CPU
+baseline, so that a rocprofv3 run of it averages exactly the timed steps' kernels.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed (the MSM totals, the GT values of the
+pairing batch; a fixed sample of them when the batch is larger than 4 096) as DIR/<name>.npy in float64, one byte of
+the library's output encoding per element, so that two builds can be compared output for output on the same inputs.
 
 `roofline` is for the dominant kernel (the bucket accumulation; the fused pairing kernel for config 3): algorithmic
 bytes of one launch / its average duration, from HIP events recorded on the stream the kernel is launched on, in the
@@ -96,6 +103,21 @@ def seeded_scalars(n_total: int, lo: int, hi: int, seed: int, dev) -> torch.Tens
     return torch.cat(out).contiguous() if out else torch.empty((0, 32), dtype=torch.uint8, device=dev)
 
 
+DUMP_SAMPLE = 4096  # --dump-outputs: at most this many GT values of a pairing batch (a fixed, seeded sample beyond it)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 (one byte of the output encoding per element: exact)"""
+    import numpy as np
+
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:  # a dump inside a checkout leaves `git status` clean
+            f.write("*\n")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def self_launch(n_ranks: int) -> int:
     """python -m torch.distributed.run --standalone --nproc-per-node N bench.py <the same arguments>, as a child"""
     import socket
@@ -119,6 +141,8 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--log-n", type=int, default=0, help="override the config's size (rehearsals only: the line is marked reduced and is not a measurement of the config)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the extras, the pairing batch, the CPU baseline and the separate per-kernel pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy (float64)")
     ap.add_argument("--kernels-only", action="store_true", help="timed steps only: no extras, no pairing batch, no CPU baseline (rocprofv3 passes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pairing", action="store_true")
@@ -131,7 +155,7 @@ def main() -> None:
     ap.add_argument("--skewed", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pipelined-extra", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.kernels_only:
+    if args.kernels_only or not args.full:
         args.no_cpu_baseline = args.no_pairing = args.no_extras = True
 
     cfg = CONFIGS[args.config]
@@ -252,6 +276,15 @@ def main() -> None:
         torch.cuda.synchronize()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            import numpy as np
+
+            if npair > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0x6D6C).choice(npair, DUMP_SAMPLE, replace=False))
+            else:
+                idx = np.arange(npair)
+            rows = gt.view(npair, gtb)[torch.from_numpy(idx).to(dev)].cpu().numpy()
+            dump_outputs(args.dump_outputs, {"pairing_gt": rows.reshape(len(idx), 12, fpb), "pairing_gt_index": idx})
         kernel_ms = statistics.mean(a.elapsed_time(b) for a, b in ev) if ev else 0.0
         units_per_step = npair * world
         achieved = PAIRING_BYTES_PER_UNIT * npair / (kernel_ms * 1e-3) / 1e9 if kernel_ms else 0.0
@@ -279,7 +312,7 @@ def main() -> None:
     else:
         # =========================================================== MSM configs
         # one plan + stream per (slot, group); slot 1 only for the two-deep runs
-        nslots = 2
+        nslots = 2 if (args.pipelined or not args.no_extras) else 1
         window_c = cfg.get("window_c", WINDOW_C)  # 0: the library's pick for this shard's size
         plans = {(s, g): _lib.MsmPlan(CURVE, g, n, window_c) for s in range(nslots) for g in groups}
         window_c, n_windows = plans[(0, groups[0])].window()
@@ -350,10 +383,17 @@ def main() -> None:
         torch.cuda.synchronize()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0 and res:
+            import numpy as np
+
+            dump_outputs(args.dump_outputs, {"msm_g%d" % g: np.frombuffer(res[g], dtype=np.uint8).reshape(2 * g, fpb) for g in groups})
         steps_n = max(args.steps, 1)
         # per-kernel times: unshared only when one MSM is in flight -- config 4 (G1 and G2 of a step overlap) and
-        # --pipelined take them from a separate pass, one MSM at a time
-        if (len(groups) > 1 and not shared) or args.pipelined:
+        # --pipelined take them from a separate pass, one MSM at a time (--full only: a plain run leaves them out)
+        separate_pass = (len(groups) > 1 and not shared) or args.pipelined
+        if separate_pass and not args.full:
+            phase_avg = {}
+        elif separate_pass:
             phase.clear()
             reps = 3
             for _ in range(reps):
@@ -395,6 +435,8 @@ def main() -> None:
             "phase_ms": {("g1_" if g == G1 else "g2_") + k_: v for (g, k_), v in sorted(phase_avg.items()) if k_ not in ("tiles", "edwards")},
         }
         roofline["traffic"], roofline["traffic_note"] = _pmc(args.config, acc_kernel.split("<")[0] + "<" + cname)
+        if separate_pass and not args.full:
+            roofline["phase_note"] = "per-kernel times of overlapping MSMs need a separate one-at-a-time pass: --full"
         if reduced:
             roofline["traffic"], roofline["traffic_note"] = None, "reduced size: the PMC passes are of the full config"
         if dom == G1 and not acc32 and fpb == 48:

@@ -51,22 +51,35 @@ ALT_SWITCHES = ("MLHIP_ACC32", "MLHIP_REDUCE32", "MLHIP_REDUCE_ONE_LANE", "MLHIP
                 "MLHIP_SCALAR_MUL_ONE_LANE")
 
 
-def alt_build() -> bool:
-    """Can this test run a second implementation?  Either the loaded library is the test build (mlhip_version() bit 16), or
-    an up-to-date libmlhip_alt.so lies next to the product library and the `monkeypatch` fixture below will route the test
-    through it when it turns such a switch on."""
+def ensure_alt() -> bool:
+    """Is an up-to-date test build next to the product library?  A clean checkout has only the product library (build()
+    makes that one), so the first test that needs the test build compiles it (python -m mathlib_amd.build --alt); a failed
+    compile fails that test rather than skipping it."""
     from mathlib_amd import _lib
 
-    return bool(_lib.load().mlhip_version() & 0x10000) or _lib.alt_available()
+    if not _lib.alt_available():
+        from mathlib_amd import build
+
+        build.build(verbose=False, alt=True)
+    return _lib.alt_available()
+
+
+def alt_build() -> bool:
+    """Can this test run a second implementation?  Either the loaded library is the test build (mlhip_version() bit 16), or
+    an up-to-date libmlhip_alt.so lies next to the product library (ensure_alt builds it when it is missing) and the
+    `monkeypatch` fixture below will route the test through it when it turns such a switch on."""
+    from mathlib_amd import _lib
+
+    return bool(_lib.load().mlhip_version() & 0x10000) or ensure_alt()
 
 
 @pytest.fixture
 def monkeypatch(monkeypatch):
     """pytest's monkeypatch, except that switching on a second implementation the product library does not contain routes
-    the REST OF THE TEST through the test build (mathlib_amd/_lib.py: use_alt; back to the product at teardown) -- or skips
-    the test when there is no up-to-date test build (the product ignores those switches: the test would silently re-run the
-    default path).  Tests that reach such a switch only after creating library objects guard it with alt_build() and create
-    the objects afterwards: a handle never crosses from one library to the other."""
+    the REST OF THE TEST through the test build (mathlib_amd/_lib.py: use_alt; back to the product at teardown), building
+    it first when there is no up-to-date one (ensure_alt; the product ignores those switches: the test would silently re-run
+    the default path).  Tests that reach such a switch only after creating library objects guard it with alt_build() and
+    create the objects afterwards: a handle never crosses from one library to the other."""
     from mathlib_amd import _lib
 
     plain = monkeypatch.setenv
@@ -74,8 +87,8 @@ def monkeypatch(monkeypatch):
 
     def setenv(name, value, *a, **k):
         if name in ALT_SWITCHES and str(value) == "1" and not (_lib.load().mlhip_version() & 0x10000):
-            if not _lib.alt_available():
-                pytest.skip("%s=1 needs the test build (python -m mathlib_amd.build --alt)" % name)
+            if not ensure_alt():
+                pytest.fail("%s=1 needs the test build, and python -m mathlib_amd.build --alt did not make an up-to-date one" % name)
             _lib.use_alt(True)
             switched.append(name)
         return plain(name, value, *a, **k)

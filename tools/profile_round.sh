@@ -1,10 +1,10 @@
 #!/bin/bash
 # The round's judged profile artifacts, produced on the GPU box from the repo root:
-#   1. python bench.py (default flags the driver uses)                        -> $out/bench_default.json
+#   1. python bench.py --full (the default config with every extra)             -> $out/bench_default.json
 #   2. per BASELINE config N in 2 3 4 5 (`bench.py --config N --kernels-only`, rocprofv3 directly in front of python3):
 #      rocprofv3 --kernel-trace --stats                                       -> $out/stats_cN/  (+ the bench line under rocprof)
 #      rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes)        -> $out/pmc_fetch_cN, $out/pmc_write_cN
-#   3. the full bench lines of configs 3, 4, 5                                -> $out/bench_cN.json
+#   3. the full bench lines (--full) of configs 3, 4, 5                        -> $out/bench_cN.json
 # Usage: bash tools/profile_round.sh gpurun_out/r03_profile ["2 3 4 5"]
 # Afterwards, here: python tools/pmc_traffic.py profiles/rNN_pmc_traffic.json $(cat $out/source_hash.txt) $(git rev-parse --short HEAD) \
 #                     2:$out/pmc_fetch_c2/..counter_collection.csv 2:$out/pmc_write_c2/.. 3:.. (tools/collect_profiles.py does it)
@@ -14,7 +14,7 @@ configs=${2:-2 3 4 5}
 mkdir -p "$out"
 export TMPDIR=/tmp
 python3 -m mathlib_amd.build --source-hash > "$out/source_hash.txt"
-python3 bench.py --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err"
 echo "bench default done"
 for c in $configs; do
   steps=10; warm=3
@@ -24,7 +24,7 @@ for c in $configs; do
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$out/pmc_write_c$c" -o w --output-format csv -- python3 bench.py --config $c --kernels-only --steps 3 --warmup 1 > "$out/pmc_write_c$c.json" 2> "$out/pmc_write_c$c.err"
   echo "config $c profiled"
   if [ "$c" != 2 ]; then
-    python3 bench.py --config $c --steps 5 --warmup 2 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err"
+    python3 bench.py --full --config $c --steps 5 --warmup 2 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err"
     echo "config $c bench line done"
   fi
 done

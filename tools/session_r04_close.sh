@@ -45,13 +45,13 @@ A)
 B)
   profile_configs "2 3 5"
   make_traffic B
-  python3 bench.py --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "default bench line done"
-  for c in 3 5; do python3 bench.py --config $c --steps 5 --warmup 2 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err"; echo "config $c bench line done"; done
+  python3 bench.py --full --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "default bench line done"
+  for c in 3 5; do python3 bench.py --full --config $c --steps 5 --warmup 2 > "$out/bench_c$c.json" 2> "$out/bench_c$c.err"; echo "config $c bench line done"; done
   ;;
 C)
   profile_configs "4"
   make_traffic C
-  python3 bench.py --config 4 --steps 5 --warmup 2 > "$out/bench_c4.json" 2> "$out/bench_c4.err"; echo "config 4 bench line done"
+  python3 bench.py --full --config 4 --steps 5 --warmup 2 > "$out/bench_c4.json" 2> "$out/bench_c4.err"; echo "config 4 bench line done"
   ;;
 D)
   # the shifted-base-table path (msm_fold.h): kernel stats of tools/perf_fold.py (plain table and tables, alternating), 2^20 BLS12-381 G1

@@ -10,7 +10,7 @@ for a in "BLS12-381 20 20" "BLS12-377 20 20" "BN254 20 20" "BLS12-381 17 20" "BL
 done
 MLHIP_PERF_GROUP=2 timeout -k 10 300 python3 tools/perf_fold.py BLS12-381 20 20 2>&1 | grep -v amdgpu.ids | tee -a $out/perf_fold.txt || exit 1
 unset MLHIP_PERF_PLAIN_C
-timeout -k 10 400 python3 bench.py 2>&1 | grep -v amdgpu.ids | tail -1 > $out/bench_config2.json || exit 1
+timeout -k 10 400 python3 bench.py --full 2>&1 | grep -v amdgpu.ids | tail -1 > $out/bench_config2.json || exit 1
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04g/bench_config2.json").read())

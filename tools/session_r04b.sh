@@ -25,7 +25,7 @@ done | tee $out/chunks_two_ab.txt
 python3 tools/perf_hostapi_schedule.py 20 > $out/hostapi_schedule_20.txt 2>&1; cat $out/hostapi_schedule_20.txt
 python3 tools/perf_hostapi_schedule.py 22 BLS12-381 quick > $out/hostapi_schedule_22.txt 2>&1; cat $out/hostapi_schedule_22.txt
 python3 tools/perf_fixed_base_ed.py 20 2>&1 | tee $out/fixed_base_edwards_ab.txt
-python3 bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
 python3 - <<PY
 import json
 d=json.loads(open("$out/bench_default.json").read().strip().splitlines()[-1])

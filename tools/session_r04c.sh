@@ -6,7 +6,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 timeout -k 10 600 python3 -m pytest tests -x -q -m gpu > $out/gpu_tests_product.txt 2>&1; echo "rc $?" >> $out/gpu_tests_product.txt; tail -3 $out/gpu_tests_product.txt
 MLHIP_LIB=$PWD/mathlib_amd/libmlhip_alt.so timeout -k 10 600 python3 -m pytest tests -x -q -m gpu > $out/gpu_tests_alt.txt 2>&1; echo "rc $?" >> $out/gpu_tests_alt.txt; tail -3 $out/gpu_tests_alt.txt
-python3 bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
 python3 - <<PY
 import json
 d=json.loads(open("$out/bench_default.json").read().strip().splitlines()[-1])
