@@ -60,6 +60,16 @@ var WindowC = 0
 // pairs; 32 keeps the tiny proofs-of-knowledge MSMs (perf_test.go:198-224, 3-7 pairs) on the CPU.
 var MinDeviceMSM = 32
 
+// MinDeviceMSMBatch: MultiScalarMulBatch / Mul2Batch with fewer pairs in all stay on the embedded gurvy driver;
+// MaxBatchSegment: a segment of this many pairs or more is sent to MultiScalarMul on its own.  Measured with
+// tools/perf_msm_batch.py (profiles/msm_batch_grid.jsonl, DESIGN.md section 8): a batch call costs the device 3-7 ms
+// while it is not filled, and the C restatement on the GPU box's 16 cores needs 12-47 ms for 2 048 pairs; as for
+// MinDeviceMSM, gnark itself cannot be timed here, and its ADX code being several times faster than that port puts the
+// break-even near 2^11 pairs.  A single mlhip_msm_g1 call of 2^14 pairs (0.72 ms) costs about what those pairs cost
+// inside a full batch (1.8-2.5e7 pairs/s).
+var MinDeviceMSMBatch = 2048
+var MaxBatchSegment = 16384
+
 // MinDevicePairingBatch: PairingBatch with fewer pairs stays on the embedded gurvy driver.  Any batch up to 16 384
 // pairs costs one wave time on the device (5.2 ms on an MI355X, one pairing per quad of lanes:
 // profiles/r02_perf_pairing_quads.txt); a CPU
@@ -140,6 +150,76 @@ func (c *Curve) MultiScalarMul(a []driver.G1, b []driver.Zr) driver.G1 {
 		unsafe.Pointer(&out.G1Affine))
 	})
 	return out
+}
+
+// MultiScalarMulBatch returns MultiScalarMul(a[i], b[i]) for every i -- an idemix / BBS verifier's many small MSMs --
+// with one device call (mlhip_msm_batch: chunks of a few pairs per lane, DESIGN.md section 8).  Every segment keeps
+// MultiScalarMul's rules: fewer scalars than points panics (index out of range, math.go:960-969), more gives the
+// identity.  A batch of fewer than MinDeviceMSMBatch pairs in all stays on the embedded gurvy driver, and a segment of
+// MaxBatchSegment pairs or more goes to MultiScalarMul on its own (mlhip_msm_g1 is faster there).
+func (c *Curve) MultiScalarMulBatch(a [][]driver.G1, b [][]driver.Zr) []driver.G1 {
+	if len(a) != len(b) {
+		panic("hip: MultiScalarMulBatch length mismatch")
+	}
+	k := len(a)
+	out := make([]driver.G1, k)
+	total := 0
+	for i := range a {
+		if len(b[i]) < len(a[i]) {
+			_ = b[i][len(a[i])-1] // the reference's index out of range
+		}
+		if len(b[i]) == len(a[i]) && len(a[i]) < MaxBatchSegment {
+			total += len(a[i])
+		}
+	}
+	if total < MinDeviceMSMBatch {
+		for i := range a {
+			out[i] = c.MultiScalarMul(a[i], b[i])
+		}
+		return out
+	}
+	offsets := make([]uint64, k+1)
+	points := make([]bls12381.G1Affine, 0, total)
+	scalars := make([]fr.Element, 0, total)
+	for i := range a {
+		offsets[i+1] = offsets[i]
+		if len(b[i]) != len(a[i]) || len(a[i]) >= MaxBatchSegment {
+			continue // the identity, or (below) a segment of its own
+		}
+		for j := range a[i] {
+			points = append(points, a[i][j].(*gurvy381.G1).G1Affine)
+			scalars = append(scalars, gurvy381.ZrValue(b[i][j]))
+		}
+		offsets[i+1] += uint64(len(a[i]))
+	}
+	res := make([]bls12381.G1Affine, k)
+	check(func() C.int {
+		return C.mlhip_msm_batch(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1, unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1,
+			(*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k), unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		if len(b[i]) == len(a[i]) && len(a[i]) >= MaxBatchSegment {
+			out[i] = c.MultiScalarMul(a[i], b[i])
+		} else {
+			out[i] = &gurvy381.G1{G1Affine: res[i]}
+		}
+	}
+	return out
+}
+
+// Mul2Batch returns g[i].Mul2(e[i], q[i], f[i]) for every i: MultiScalarMulBatch over segments of two pairs.
+func (c *Curve) Mul2Batch(g []driver.G1, e []driver.Zr, q []driver.G1, f []driver.Zr) []driver.G1 {
+	n := len(g)
+	if len(e) != n || len(q) != n || len(f) != n {
+		panic("hip: Mul2Batch length mismatch")
+	}
+	a := make([][]driver.G1, n)
+	b := make([][]driver.Zr, n)
+	for i := range g {
+		a[i] = []driver.G1{g[i], q[i]}
+		b[i] = []driver.Zr{e[i], f[i]}
+	}
+	return c.MultiScalarMulBatch(a, b)
 }
 
 // Pairing replaces bls12-381.go:448-455: Miller loop only, compare after FExp.

@@ -202,6 +202,24 @@ MLHIP_API int mlhip_scalar_mul_device(int curve, int group, const void* d_points
 MLHIP_API int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stride, const void* scalars,
                      int scalars_mont, size_t n, void* out_affine);
 
+/* K independent MSMs in one call: out[k] = sum_{offsets[k] <= i < offsets[k+1]} [scalars[i]] points[i] (the batched form of
+ * MultiScalarMul / Mul2: an idemix or BBS verifier's many proofs of a few pairs each).
+ * offsets: K+1 nondecreasing entries in HOST memory, offsets[0] = 0, offsets[K] = total pairs; anything else, or a null
+ * pointer in a non-empty batch, is MLHIP_EINVAL before anything is launched.  K = 0 returns 0 and does nothing.
+ * An empty segment gives the point at infinity.  group = MLHIP_GROUP_G1 or _G2.  Scalars as in mlhip_msm_g1
+ * (scalars_mont, not necessarily reduced).  Affine output in this header's layout (infinity = all zero).
+ * Every segment is cut into chunks of at most P pairs, one lane (G1) or lane pair (G2) per chunk runs an interleaved
+ * signed 4-bit-window double-and-add (256 / P + 71 group operations per pair), and the chunk sums of each segment are
+ * added in passes of at most 32 per lane.  P = 4 (MLHIP_MSM_BATCH_CHUNK = 1, 2, 4 or 8 overrides; below ~2^17 pairs in all
+ * the device is not filled and P = 1 is faster).  Meant for segments of
+ * 2 to a few hundred pairs: a long segment is exact but slower than mlhip_msm_g1 on it.
+ * Runs on the first listed device.  Device pointers; the offsets are read on the host. */
+MLHIP_API int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
+                                     const uint64_t* offsets, size_t k, void* d_out_affine, void* stream);
+/* host-buffer form */
+MLHIP_API int mlhip_msm_batch(int curve, int group, const void* points, const void* scalars, int scalars_mont,
+                              const uint64_t* offsets, size_t k, void* out_affine);
+
 /* ---- resident bases (upload-once point table, only the scalars travel per call) ----------
  * For callers that cannot hold device pointers themselves (the Go shim): the points are uploaded once, every
  * mlhip_bases_msm() uploads n x 32 bytes of scalars and returns sum_i [s_i] P_i over the first n bases (n <= the
@@ -295,6 +313,7 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_EDWARDS=0                  BLS12-377 G1 over a checked SRS: keep the Weierstrass bucket sums
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
+ *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
  *     MLHIP_PAIRING_QUAD=0|1           BLS12-381: never / always one pairing per quad of lanes (default: up to 2^14 elements)
  *   2nd impl (parity tests; DESIGN.md section 2 lists which test runs which)
  *     MLHIP_ACC32=1                    boundary-form (32-bit limb) bucket accumulation, G1 and G2

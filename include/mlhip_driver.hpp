@@ -16,7 +16,8 @@
 //   Curve::FExp(gt)                      driver/math.go:56-57                         -> mlhip_final_exp
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
-//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch
+//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch,
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch
 #pragma once
 #include <array>
 #include <cstdint>
@@ -437,6 +438,26 @@ class Curve {
     check(mlhip_msm_g2(id, pts.data(), sc.data(), scalars_mont ? 1 : 0, a.size(), window_c, out.raw.data()));
     return out;
   }
+  // out[i] = MultiScalarMul(a[i], b[i]) for many small MSMs in one device call (mlhip_msm_batch); every segment keeps
+  // MultiScalarMul's length rules: fewer scalars than points throws, more gives the identity
+  std::vector<G1> MultiScalarMulBatch(const std::vector<std::vector<G1>>& a, const std::vector<std::vector<Zr>>& b) const {
+    return msm_batch(MLHIP_GROUP_G1, g1_bytes, a, b, "MultiScalarMulBatch");
+  }
+  std::vector<G2> MultiScalarMulG2Batch(const std::vector<std::vector<G2>>& a, const std::vector<std::vector<Zr>>& b) const {
+    return msm_batch(MLHIP_GROUP_G2, g2_bytes, a, b, "MultiScalarMulG2Batch");
+  }
+  // out[i] = g[i].Mul2(e[i], q[i], f[i]): segments of two pairs
+  std::vector<G1> Mul2Batch(const std::vector<G1>& g, const std::vector<Zr>& e, const std::vector<G1>& q,
+                            const std::vector<Zr>& f) const {
+    if (e.size() != g.size() || q.size() != g.size() || f.size() != g.size()) throw std::invalid_argument("Mul2Batch: length mismatch");
+    std::vector<std::vector<G1>> a(g.size());
+    std::vector<std::vector<Zr>> b(g.size());
+    for (size_t i = 0; i < g.size(); i++) {
+      a[i] = {g[i], q[i]};
+      b[i] = {e[i], f[i]};
+    }
+    return MultiScalarMulBatch(a, b);
+  }
   // (MultiScalarMul(a1, b), MultiScalarMulG2(a2, b)) over ONE scalar vector: one sort on the device for both groups
   std::pair<G1, G2> MultiScalarMulG1G2(const std::vector<G1>& a1, const std::vector<G2>& a2, const std::vector<Zr>& b) const {
     if (b.size() < a1.size() || b.size() < a2.size()) throw std::out_of_range("MultiScalarMulG1G2: fewer scalars than points");
@@ -538,6 +559,38 @@ class Curve {
     pack(points, scalars, pts, sc);
     check(mlhip_scalar_mul(id, group, pts.data(), stride, sc.data(), scalars_mont ? 1 : 0, n, o.data()));
     for (size_t i = 0; i < n; i++) {
+      P g;
+      g.curve = this;
+      g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);
+      out.push_back(g);
+    }
+    return out;
+  }
+  template <class P>
+  std::vector<P> msm_batch(int group, size_t size, const std::vector<std::vector<P>>& a, const std::vector<std::vector<Zr>>& b,
+                           const char* what) const {
+    if (a.size() != b.size()) throw std::invalid_argument(std::string(what) + ": as many point lists as scalar lists");
+    std::vector<P> out;
+    const size_t k = a.size();
+    if (k == 0) return out;
+    std::vector<uint64_t> offsets(k + 1, 0);
+    Bytes pts, sc;
+    for (size_t i = 0; i < k; i++) {
+      if (b[i].size() < a[i].size()) throw std::out_of_range(std::string(what) + ": fewer scalars than points");
+      const bool used = b[i].size() == a[i].size();  // otherwise MultiExp's dropped error: an empty segment, the identity
+      offsets[i + 1] = offsets[i] + (used ? a[i].size() : 0);
+      if (!used) continue;
+      for (auto& x : a[i]) pts.insert(pts.end(), x.raw.begin(), x.raw.end());
+      for (auto& z : b[i]) {
+        auto l = z.abi_limbs();
+        const size_t at = sc.size();
+        sc.resize(at + 32);
+        memcpy(sc.data() + at, l.data(), 32);
+      }
+    }
+    Bytes o(size * k);
+    check(mlhip_msm_batch(id, group, pts.data(), sc.data(), scalars_mont ? 1 : 0, offsets.data(), k, o.data()));
+    for (size_t i = 0; i < k; i++) {
       P g;
       g.curve = this;
       g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);

@@ -55,6 +55,8 @@ SYMBOLS = [
     "mlhip_gt_exp_device",
     "mlhip_scalar_mul_device",
     "mlhip_scalar_mul",
+    "mlhip_msm_batch_device",
+    "mlhip_msm_batch",
     "mlhip_bases_create",
     "mlhip_bases_msm",
     "mlhip_bases_create_device",
@@ -190,6 +192,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.mlhip_gt_mul_device.argtypes = [ci, vp, vp, sz, vp, vp]
     lib.mlhip_scalar_mul_device.argtypes = [ci, ci, vp, sz, vp, ci, sz, vp, vp]
     lib.mlhip_scalar_mul.argtypes = [ci, ci, vp, sz, vp, ci, sz, vp]
+    lib.mlhip_msm_batch_device.argtypes = [ci, ci, vp, vp, ci, vp, sz, vp, vp]
+    lib.mlhip_msm_batch.argtypes = [ci, ci, vp, vp, ci, vp, sz, vp]
     lib.mlhip_bases_create.argtypes = [ci, ci, vp, sz, ci, ctypes.POINTER(c_void_p)]
     lib.mlhip_bases_msm.argtypes = [vp, vp, ci, sz, vp]
     lib.mlhip_bases_create_device.argtypes = [ci, ci, vp, sz, ci, ctypes.POINTER(c_void_p)]
@@ -225,6 +229,29 @@ def sizes(curve: int):
     a, b, c, d = c_size_t(), c_size_t(), c_size_t(), c_size_t()
     check(lib.mlhip_sizes(curve, byref(a), byref(b), byref(c), byref(d)))
     return a.value, b.value, c.value, d.value
+
+
+def batch_offsets(lengths):
+    """the offsets array of mlhip_msm_batch* (K + 1 uint64 entries) for segments of these lengths"""
+    offs = (ctypes.c_uint64 * (len(lengths) + 1))()
+    t = 0
+    for i, m in enumerate(lengths):
+        t += m
+        offs[i + 1] = t
+    return offs
+
+
+def msm_batch(curve: int, group: int, points: bytes, scalars: bytes, scalars_mont: bool, lengths):
+    """mlhip_msm_batch: one affine point (bytes) per segment; segment i has lengths[i] consecutive pairs"""
+    _, g1, g2, _ = sizes(curve)
+    ptsz = g1 if group == GROUP_G1 else g2
+    k = len(lengths)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k * ptsz)
+    check(load().mlhip_msm_batch(curve, group, points, scalars, 1 if scalars_mont else 0, batch_offsets(lengths), k, out))
+    raw = out.raw
+    return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
 
 
 def init_devices(devices=None) -> None:

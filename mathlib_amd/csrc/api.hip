@@ -1504,6 +1504,60 @@ int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stri
   return hc.down(out, dout, n * ptsz);
 }
 
+// offsets of a batch: k + 1 nondecreasing host entries from 0 (k = 0: nothing to check)
+static int check_batch_offsets(const uint64_t* offsets, size_t k) {
+  if (k == 0) return 0;
+  if (!offsets) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets is null");
+  if (offsets[0] != 0) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets[0] must be 0");
+  for (size_t i = 0; i < k; i++)
+    if (offsets[i + 1] < offsets[i]) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets decrease");
+  return 0;
+}
+
+int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
+                           const uint64_t* offsets, size_t k, void* d_out_affine, void* stream) {
+  Sizes sz;
+  if (!curve_sizes(curve, sz)) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (group != MLHIP_GROUP_G1 && group != MLHIP_GROUP_G2) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!d_out_affine || (offsets[k] && (!d_points || !d_scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  rc = ensure_device();
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  switch (curve) {
+    case MLHIP_CURVE_BN254: return mlhip_tu_msm_batch_Bn254(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, st);
+    case MLHIP_CURVE_BLS12_381: return mlhip_tu_msm_batch_Bls381(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, st);
+    case MLHIP_CURVE_BLS12_377: return mlhip_tu_msm_batch_Bls377(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, st);
+    default: return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  }
+}
+
+int mlhip_msm_batch(int curve, int group, const void* points, const void* scalars, int scalars_mont, const uint64_t* offsets,
+                    size_t k, void* out_affine) {
+  Sizes sz;
+  if (!curve_sizes(curve, sz)) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (group != MLHIP_GROUP_G1 && group != MLHIP_GROUP_G2) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  const size_t n = offsets[k];
+  if (!out_affine || (n && (!points || !scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  rc = ensure_device();
+  if (rc) return rc;
+  const size_t ptsz = group == MLHIP_GROUP_G1 ? sz.g1 : sz.g2;
+  HostCall hc;
+  hc.reserve(n * ptsz + n * 32 + k * ptsz);
+  void* dp = hc.up(points, n * ptsz);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(k * ptsz);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_msm_batch_device(curve, group, dp, ds, scalars_mont, offsets, k, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out_affine, dout, k * ptsz);
+}
+
 int mlhip_gt_exp_device(int curve, const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, void* stream) {
   int rc = ensure_device();
   if (rc) return rc;

@@ -142,6 +142,8 @@ struct mlhip_msm_plan {
   int mlhip_tu_scalar_mul_##NAME(int group, const void* d_points, size_t point_stride, const void* d_scalars,     \
                                  int mont, size_t n, void* d_out, hipStream_t st);                                 \
   int mlhip_tu_plan_fold_build_##NAME(mlhip_msm_plan* p, const void* d_points, size_t n, hipStream_t st);          \
+  int mlhip_tu_msm_batch_##NAME(int group, const void* d_points, const void* d_scalars, int mont,                 \
+                                const uint64_t* offsets, size_t k, void* d_out, hipStream_t st);                   \
   void mlhip_tu_release_cache_##NAME(void);
 // G1 points outside the prime-order subgroup (or off the curve) in an array of affine points: mlhip_bases_create's check
 int mlhip_tu_g1_count_outside_subgroup_Bls377(const void* d_pts, size_t n, uint32_t* d_bad, hipStream_t st);

@@ -13,6 +13,25 @@
 
 namespace mlhip {
 
+// Signed 4-bit windows of a 256-bit integer: s + 0x88..8 has the nibbles d_w + 8 with d_w in [-8, 7] and
+// s = sum_w d_w 16^w + t[8] 16^64 (t[8] = the carry out of the addition: 0 for a scalar below 2^255).  The carries of the
+// recoding are the carries of one 256-bit addition -- no per-window branch; the table holds {1..8}P, half of the
+// unsigned form's, and every lane of a wave adds at the same loop positions (a windowed NAF would not: its non-zero
+// digits sit at data-dependent positions, which serialises the lanes).
+MLHIP_HD void signed_windows4(uint32_t t[9], const uint32_t s[8]) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    c += (uint64_t)s[k] + 0x88888888u;
+    t[k] = (uint32_t)c;
+    c >>= 32;
+  }
+  t[8] = (uint32_t)c;
+}
+MLHIP_HD int signed_window4_digit(const uint32_t t[9], int w) {
+  return w == 64 ? (int)t[8] : (int)((t[w >> 3] >> ((w & 7) * 4)) & 15u) - 8;
+}
+
 // ---- scalar handling -------------------------------------------------------------------------
 // Scalars arrive as 8 little-endian 32-bit words: either gnark's fr.Element (Montgomery, R = 2^256;
 // what driver/gurvy/bls12381 passes, bls12-381.go:772) or a plain integer (any 256-bit value; it is

@@ -5,24 +5,7 @@
 
 namespace mlhip {
 
-// Signed 4-bit windows of a 256-bit integer: s + 0x88..8 has the nibbles d_w + 8 with d_w in [-8, 7] and
-// s = sum_w d_w 16^w + t[8] 16^64 (t[8] = the carry out of the addition: 0 for a scalar below 2^255).  The carries of the
-// recoding are the carries of one 256-bit addition -- no per-window branch; the table holds {1..8}P, half of the
-// unsigned form's, and every lane of a wave adds at the same loop positions (a windowed NAF would not: its non-zero
-// digits sit at data-dependent positions, which serialises the lanes).
-__device__ __forceinline__ void signed_windows4(uint32_t t[9], const uint32_t s[8]) {
-  uint64_t c = 0;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    c += (uint64_t)s[k] + 0x88888888u;
-    t[k] = (uint32_t)c;
-    c >>= 32;
-  }
-  t[8] = (uint32_t)c;
-}
-__device__ __forceinline__ int signed_window4_digit(const uint32_t t[9], int w) {
-  return w == 64 ? (int)t[8] : (int)((t[w >> 3] >> ((w & 7) * 4)) & 15u) - 8;
-}
+// (signed_windows4 / signed_window4_digit, the signed 4-bit recoding used below: msm_body.h)
 
 // out[i] = [s_i] P_i: batched single-scalar multiplication (the reference's G1.Mul / G2.Mul,
 // driver/gurvy/bls12381/bls12-381.go:238-247, :342-351; double-and-add shape of :920-932), one lane per

@@ -33,4 +33,12 @@ int mlhip_tu_plan_fold_build_Bn254(mlhip_msm_plan* p, const void* d_points, size
   if (p->group == MLHIP_GROUP_G1) return plan_fold_build<Bn254, FpField<Bn254>>(p, d_points, n, st);
   return plan_fold_build<Bn254, Fp2Field<Bn254>>(p, d_points, n, st);
 }
-void mlhip_tu_release_cache_Bn254(void) { fixed_base_release(); }
+int mlhip_tu_msm_batch_Bn254(int group, const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k,
+                          void* d_out, hipStream_t st) {
+  if (group == MLHIP_GROUP_G1) return msm_batch_device<Bn254, FpField<Bn254>>(d_points, d_scalars, mont, offsets, k, d_out, st);
+  return msm_batch_device<Bn254, Fp2Field<Bn254>>(d_points, d_scalars, mont, offsets, k, d_out, st);
+}
+void mlhip_tu_release_cache_Bn254(void) {
+  fixed_base_release();
+  msm_batch_release();
+}

@@ -11,7 +11,8 @@ names, argument order and error behaviour -- so the parity tests read like math_
     Curve.FExp(Gt) Gt                            driver/math.go:56-57     -> mlhip_final_exp
     G1.Mul / G2.Mul / Gt.Mul / G1.Add ...        driver/math.go:249-360   -> n=1 MSM, group helpers
     Gt.Exp(Zr) Gt                                driver/math.go:358-359   -> mlhip_gt_exp
-  additive: MultiScalarMulG2, PairingBatch, PairingProduct.
+  additive: MultiScalarMulG2, PairingBatch, PairingProduct, MultiScalarMulBatch, MultiScalarMulG2Batch,
+  Mul2Batch.
 
 Only plumbing happens here (byte packing, Montgomery <-> integer conversion for printing and wire
 bytes).  All group / field arithmetic is done by libmlhip.so; nothing under oracle/ is imported.
@@ -25,7 +26,7 @@ import secrets
 from typing import List, Sequence
 
 from . import _lib
-from ._lib import CURVE_BLS12_377, CURVE_BLS12_381, CURVE_BN254, GROUP_G1, GROUP_G2, check, load
+from ._lib import CURVE_BLS12_377, CURVE_BLS12_381, CURVE_BN254, GROUP_G1, GROUP_G2, check, load, msm_batch
 from ._lib import concrete as _concrete
 
 _X381 = -0xD201000000010000
@@ -408,6 +409,40 @@ class Curve:
         check(load().mlhip_msm_g1g2(self.id, b"".join(p.raw for p in a1), b"".join(p.raw for p in a2), self._scalars(b),
                                     1 if self.scalars_mont else 0, len(a1), self.window_c, o1, o2))
         return G1(o1.raw, self), G2(o2.raw, self)
+
+    def _msm_batch(self, group: int, a_lists, b_lists, name: str, identity) -> list:
+        """one mlhip_msm_batch call for every segment; each keeps MultiScalarMul's length rules (fewer scalars than points
+        raises, more gives the identity: an empty segment)"""
+        if len(a_lists) != len(b_lists):
+            raise ValueError("%s: %d point lists, %d scalar lists" % (name, len(a_lists), len(b_lists)))
+        lengths, pts, scs = [], [], []
+        for a, b in zip(a_lists, b_lists):
+            if len(b) < len(a):
+                raise IndexError("%s: fewer scalars than points" % name)
+            if len(b) != len(a):
+                lengths.append(0)
+                continue
+            lengths.append(len(a))
+            pts.extend(p.raw for p in a)
+            scs.append(self._scalars(b))
+        if not lengths:
+            return []
+        raw = msm_batch(self.id, group, b"".join(pts), b"".join(scs), self.scalars_mont, lengths)
+        return [identity(r) for r in raw]
+
+    def MultiScalarMulBatch(self, a_lists: Sequence[Sequence[G1]], b_lists: Sequence[Sequence[Zr]]) -> List[G1]:
+        """out[i] = MultiScalarMul(a_lists[i], b_lists[i]) for many small MSMs in one device call (include/mlhip.h:
+        mlhip_msm_batch)"""
+        return self._msm_batch(GROUP_G1, a_lists, b_lists, "MultiScalarMulBatch", lambda r: G1(r, self))
+
+    def MultiScalarMulG2Batch(self, a_lists: Sequence[Sequence[G2]], b_lists: Sequence[Sequence[Zr]]) -> List[G2]:
+        return self._msm_batch(GROUP_G2, a_lists, b_lists, "MultiScalarMulG2Batch", lambda r: G2(r, self))
+
+    def Mul2Batch(self, g: Sequence[G1], e: Sequence[Zr], q: Sequence[G1], f: Sequence[Zr]) -> List[G1]:
+        """out[i] = g[i].Mul2(e[i], q[i], f[i]): segments of two pairs in one mlhip_msm_batch call"""
+        if not (len(g) == len(e) == len(q) == len(f)):
+            raise ValueError("Mul2Batch: length mismatch")
+        return self.MultiScalarMulBatch([[g[i], q[i]] for i in range(len(g))], [[e[i], f[i]] for i in range(len(g))])
 
     def NewBases(self, points: Sequence[G1]) -> "Bases":
         """Upload a G1 point table once; Bases.MultiScalarMul(scalars) then moves only the scalars."""
