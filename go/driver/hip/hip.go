@@ -555,6 +555,62 @@ func (b *Bases) MultiScalarMul(scalars []driver.Zr) driver.G1 {
 	return out
 }
 
+// MultiScalarMulBatch returns, for every i, sum_j [scalars[i][j]] bases[index[i][j]] -- or bases[j] when index is nil, as
+// MultiScalarMul does -- in one device call (mlhip_bases_msm_batch: per-base fixed-window tables built on the first call
+// that needs them, DESIGN.md section 9).  An idemix / BBS verifier checking many proofs against one issuer key keeps the
+// key's bases in one handle.  Without index lists a segment of more scalars than bases panics, as MultiScalarMul does; with
+// them every list has as many entries as its scalars and every entry is below the number of bases.
+func (b *Bases) MultiScalarMulBatch(scalars [][]driver.Zr, index [][]uint32) []driver.G1 {
+	k := len(scalars)
+	out := make([]driver.G1, k)
+	if k == 0 {
+		return out
+	}
+	if index != nil && len(index) != k {
+		panic("hip: MultiScalarMulBatch: as many index lists as scalar lists")
+	}
+	offsets := make([]uint64, k+1)
+	sc := make([]fr.Element, 0, k)
+	var idx []uint32
+	for i := range scalars {
+		if index == nil && len(scalars[i]) > b.n {
+			panic("hip: more scalars than resident bases")
+		}
+		if index != nil {
+			if len(index[i]) != len(scalars[i]) {
+				panic("hip: MultiScalarMulBatch: as many indices as scalars")
+			}
+			for _, x := range index[i] {
+				if int(x) >= b.n {
+					panic("hip: MultiScalarMulBatch: base index out of range")
+				}
+			}
+			idx = append(idx, index[i]...)
+		}
+		for j := range scalars[i] {
+			sc = append(sc, gurvy381.ZrValue(scalars[i][j]))
+		}
+		offsets[i+1] = offsets[i] + uint64(len(scalars[i]))
+	}
+	res := make([]bls12381.G1Affine, k)
+	var scp unsafe.Pointer
+	if len(sc) > 0 {
+		scp = unsafe.Pointer(&sc[0])
+	}
+	var idxp *C.uint32_t
+	if len(idx) > 0 {
+		idxp = (*C.uint32_t)(unsafe.Pointer(&idx[0]))
+	}
+	check(func() C.int {
+		return C.mlhip_bases_msm_batch(b.h, scp, 1, idxp, (*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k),
+			unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		out[i] = &gurvy381.G1{G1Affine: res[i]}
+	}
+	return out
+}
+
 // CheckedSubgroup reports whether the library verified, on the device, that every point of the table lies in G1.  A
 // BLS12-377 table that passes has its bucket sums done in twisted Edwards coordinates (7 field products per addition
 // instead of 10); one that does not keeps the Weierstrass kernels and gnark's result for that input.

@@ -257,6 +257,32 @@ MLHIP_API mlhip_msm_plan* mlhip_bases_plan(mlhip_bases* bases);
  * subgroup, MLHIP_EDWARDS=0): such tables take the Weierstrass kernels and give the reference's result for any input. */
 MLHIP_API int mlhip_bases_checked_subgroup(mlhip_bases* bases);
 MLHIP_API int mlhip_bases_destroy(mlhip_bases* bases);
+/* K independent MSMs over the resident bases of a handle (an idemix or BBS verifier checking many proofs against one issuer
+ * key: most pairs of every proof multiply the same few dozen bases):
+ *   out[k] = sum_{offsets[k] <= i < offsets[k+1]} [scalars[i]] B[idx(i)]
+ * idx(i) = base_index[i] when base_index != NULL; otherwise i - offsets[k] (pair j of a segment takes base j).
+ * Semantics as mlhip_msm_batch (offsets rules, K = 0 does nothing, empty segment = infinity, scalars_mont, scalars not
+ * necessarily reduced, affine output with infinity all zero), in the group the handle was created with.  offsets and
+ * base_index are HOST memory in both forms.  MLHIP_EINVAL before anything is launched for malformed offsets, an index >= the
+ * handle's n, a segment longer than n without base_index, or a handle spread over several devices (not supported).
+ * The first call that reads base m - 1 builds per-base fixed-window tables T_b[j][m'-1] = [m' 2^(wj)] B_b for the bases
+ * [0, m) on the device (a later call that reads further extends them); every pair then costs ceil(256 / w) mixed additions
+ * and no doubling.  Width w = 12 (MLHIP_BASES_BATCH_WINDOW = 4 .. 12), ceil(256 / w) 2^(w-1) rows of
+ * 112 B (BLS12 G1; G2 twice) per base: 5 MB at w = 12, 459 KB at w = 8.  Chunks of P pairs per lane: the largest of
+ * 1, 2, 4, 8, 16 that still fills 2^16 lanes (MLHIP_BASES_BATCH_CHUNK overrides).  The tables are owned by the handle (freed
+ * by mlhip_bases_destroy, untouched by mlhip_release_cache) and capped at MLHIP_BASES_BATCH_MAX_MB (1024) per handle -- 212
+ * BLS12-381 G1 or 106 G2 bases at w = 12: a call whose tables would pass the cap (or MLHIP_BASES_BATCH_MAX_MB=0) runs
+ * mlhip_msm_batch's variable-base kernel on the handle's points instead.
+ * Growing the tables briefly holds the old and the new ones.  A handle that never sees a batch call allocates nothing.
+ * Calls on one handle are serialized, as for mlhip_bases_msm. */
+MLHIP_API int mlhip_bases_msm_batch(mlhip_bases* bases, const void* scalars, int scalars_mont, const uint32_t* base_index,
+                                    const uint64_t* offsets, size_t k, void* out_affine);
+/* the same with the scalars in device memory and the outputs written to device memory, in order on `stream` */
+MLHIP_API int mlhip_bases_msm_batch_device(mlhip_bases* bases, const void* d_scalars, int scalars_mont, const uint32_t* base_index,
+                                           const uint64_t* offsets, size_t k, void* stream, void* d_out_affine);
+/* number of leading bases of the handle that currently have batch tables (0: none; every batch call takes the
+ * table-free path) */
+MLHIP_API int mlhip_bases_batch_tabled(mlhip_bases* bases, size_t* n_tabled);
 
 /* The host-buffer MSM entry points above keep up to 16 plans + input buffers (at most 32 GB) alive between calls (creating and
  * destroying them costs as much as a 2^20-point MSM); this frees the idle ones.  MLHIP_NO_PLAN_CACHE=1 disables the pool. */
@@ -314,6 +340,9 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
  *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
+ *     MLHIP_BASES_BATCH_WINDOW=w, MLHIP_BASES_BATCH_CHUNK=P   mlhip_bases_msm_batch*: table width 4 .. 12 (default 12), pairs
+ *                                      per chunk on the table path, 1, 2, 4, 8 or 16 (default: the largest that fills 2^16 lanes)
+ *     MLHIP_BASES_BATCH_MAX_MB=m       ... tables per handle at most m MB (default 1024; 0 = never: the table-free path)
  *     MLHIP_PAIRING_QUAD=0|1           BLS12-381: never / always one pairing per quad of lanes (default: up to 2^14 elements)
  *   2nd impl (parity tests; DESIGN.md section 2 lists which test runs which)
  *     MLHIP_ACC32=1                    boundary-form (32-bit limb) bucket accumulation, G1 and G2

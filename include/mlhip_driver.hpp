@@ -17,7 +17,7 @@
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
 //   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch,
-//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch
 #pragma once
 #include <array>
 #include <cstdint>
@@ -632,6 +632,52 @@ class Bases {
     }
     check(mlhip_bases_msm(h_, sc.data(), curve_->scalars_mont ? 1 : 0, b.size(), out.raw.data()));
     return out;
+  }
+  // out[i] = sum_j [b[i][j]] B[index[i][j]] (no index lists: B[j], as MultiScalarMul) for many small MSMs over the resident
+  // bases in one device call (mlhip_bases_msm_batch).  Without index lists a segment has at most n scalars (out_of_range);
+  // with them, as many indices as scalars (invalid_argument), each below n (out_of_range).
+  std::vector<G1> MultiScalarMulBatch(const std::vector<std::vector<Zr>>& b,
+                                      const std::vector<std::vector<uint32_t>>* index = nullptr) const {
+    std::vector<G1> out;
+    const size_t k = b.size();
+    if (index && index->size() != k) throw std::invalid_argument("MultiScalarMulBatch: as many index lists as scalar lists");
+    if (k == 0) return out;
+    std::vector<uint64_t> offsets(k + 1, 0);
+    std::vector<uint32_t> idx;
+    Bytes sc;
+    for (size_t i = 0; i < k; i++) {
+      if (!index && b[i].size() > n_) throw std::out_of_range("MultiScalarMulBatch: more scalars than resident bases");
+      if (index) {
+        if ((*index)[i].size() != b[i].size()) throw std::invalid_argument("MultiScalarMulBatch: as many indices as scalars");
+        for (uint32_t x : (*index)[i]) {
+          if (x >= n_) throw std::out_of_range("MultiScalarMulBatch: base index out of range");
+          idx.push_back(x);
+        }
+      }
+      offsets[i + 1] = offsets[i] + b[i].size();
+      for (auto& z : b[i]) {
+        auto l = z.abi_limbs();
+        const size_t at = sc.size();
+        sc.resize(at + 32);
+        memcpy(sc.data() + at, l.data(), 32);
+      }
+    }
+    const size_t size = curve_->g1_bytes;
+    Bytes o(size * k);
+    check(mlhip_bases_msm_batch(h_, sc.data(), curve_->scalars_mont ? 1 : 0, index ? idx.data() : nullptr, offsets.data(), k,
+                                o.data()));
+    for (size_t i = 0; i < k; i++) {
+      G1 g = curve_->NewG1();
+      g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);
+      out.push_back(g);
+    }
+    return out;
+  }
+  // the number of leading bases that have MultiScalarMulBatch tables (mlhip_bases_batch_tabled)
+  size_t BatchTabled() const {
+    size_t n = 0;
+    check(mlhip_bases_batch_tabled(h_, &n));
+    return n;
   }
   // every point of the table was verified on the device to lie in G1 (BLS12-377: its MSMs then sum their buckets in
   // twisted Edwards coordinates; a table with a point outside G1 keeps the Weierstrass kernels and the reference's result)

@@ -64,6 +64,9 @@ SYMBOLS = [
     "mlhip_bases_plan",
     "mlhip_bases_checked_subgroup",
     "mlhip_bases_destroy",
+    "mlhip_bases_msm_batch",
+    "mlhip_bases_msm_batch_device",
+    "mlhip_bases_batch_tabled",
     "mlhip_release_cache",
     "mlhip_g1_from_bytes",
     "mlhip_g1_to_bytes",
@@ -202,6 +205,9 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.mlhip_bases_plan.restype = c_void_p
     lib.mlhip_bases_destroy.argtypes = [vp]
     lib.mlhip_bases_checked_subgroup.argtypes = [vp]
+    lib.mlhip_bases_msm_batch.argtypes = [vp, vp, ci, vp, vp, sz, vp]
+    lib.mlhip_bases_msm_batch_device.argtypes = [vp, vp, ci, vp, vp, sz, vp, vp]
+    lib.mlhip_bases_batch_tabled.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
     lib.mlhip_g1_from_bytes.argtypes = [ci, vp, sz, ci, ci, vp, vp]
     lib.mlhip_g1_to_bytes.argtypes = [ci, vp, sz, ci, vp]
     lib.mlhip_g1_from_bytes_device.argtypes = [ci, vp, sz, ci, ci, vp, vp, vp]
@@ -252,6 +258,34 @@ def msm_batch(curve: int, group: int, points: bytes, scalars: bytes, scalars_mon
     check(load().mlhip_msm_batch(curve, group, points, scalars, 1 if scalars_mont else 0, batch_offsets(lengths), k, out))
     raw = out.raw
     return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
+
+
+def batch_index(index_lists):
+    """the base_index array of mlhip_bases_msm_batch* (one uint32 per pair, segment after segment), or None"""
+    if index_lists is None:
+        return None
+    flat = [i for lst in index_lists for i in lst]
+    return (ctypes.c_uint32 * max(1, len(flat)))(*flat)
+
+
+def bases_msm_batch(lib, handle, ptsz: int, scalars: bytes, scalars_mont: bool, lengths, index_lists=None):
+    """mlhip_bases_msm_batch on the handle `handle` of `lib` (points of ptsz bytes): one affine point (bytes) per segment;
+    segment i has lengths[i] consecutive scalars; index_lists[i] (optional) names the base of each of its pairs"""
+    k = len(lengths)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k * ptsz)
+    check(lib.mlhip_bases_msm_batch(handle, scalars, 1 if scalars_mont else 0, batch_index(index_lists), batch_offsets(lengths), k,
+                                    out))
+    raw = out.raw
+    return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
+
+
+def bases_batch_tabled(lib, handle) -> int:
+    """mlhip_bases_batch_tabled: the number of leading bases of the handle that have batch tables"""
+    n = ctypes.c_size_t()
+    check(lib.mlhip_bases_batch_tabled(handle, ctypes.byref(n)))
+    return n.value
 
 
 def init_devices(devices=None) -> None:

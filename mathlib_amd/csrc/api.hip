@@ -1091,6 +1091,7 @@ struct mlhip_bases {
   int curve = 0, group = 0, device = 0;
   hipStream_t stream = nullptr;  // own non-blocking stream (see PoolEntry)
   std::mutex mu;  // one MSM at a time per handle: the plan and the scalar buffer are shared state
+  mlhip_bases_batch_tables batch;  // mlhip_bases_msm_batch's per-base tables: built by the first batch call that wants them
   // a table spread over several devices: contiguous shards, shard r = bases [lo[r], lo[r + 1]) on devs[r]
   std::vector<mlhip_bases*> shards;
   std::vector<size_t> lo;
@@ -1104,6 +1105,7 @@ int mlhip_bases_destroy(mlhip_bases* b) {
     (void)hipSetDevice(b->device);
     if (b->d_pts) (void)hipFree(b->d_pts);
     if (b->d_sc) (void)hipFree(b->d_sc);
+    if (b->batch.buf) (void)hipFree(b->batch.buf);
     if (b->plan) mlhip_msm_plan_destroy(b->plan);
     if (b->stream) (void)hipStreamDestroy(b->stream);
   }
@@ -1355,6 +1357,93 @@ int mlhip_bases_msm_device(mlhip_bases* b, const void* d_scalars, int scalars_mo
   if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   std::lock_guard<std::mutex> lk(b->mu);
   return mlhip_msm_run(b->plan, b->d_pts, d_scalars, scalars_mont, n, stream, out_affine, nullptr);
+}
+
+static int check_batch_offsets(const uint64_t* offsets, size_t k);
+
+// the checks of a batch over a handle that need its size: every index below n (base_index given), or every segment at most n
+// pairs long (not given); *need = 1 + the largest base any pair reads (0: every segment is empty)
+static int check_bases_batch_index(const mlhip_bases* b, const uint32_t* base_index, const uint64_t* offsets, size_t k,
+                                   size_t* need) {
+  size_t most = 0;
+  if (base_index) {
+    for (uint64_t i = 0; i < offsets[k]; i++) {
+      if (base_index[i] >= b->n) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: base index out of range");
+      most = std::max<size_t>(most, (size_t)base_index[i] + 1);
+    }
+  } else {
+    for (size_t s = 0; s < k; s++) {
+      const uint64_t m = offsets[s + 1] - offsets[s];
+      if (m > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: a segment is longer than the handle's bases");
+      most = std::max<size_t>(most, (size_t)m);
+    }
+  }
+  *need = most;
+  return 0;
+}
+
+int mlhip_bases_msm_batch_device(mlhip_bases* b, const void* d_scalars, int scalars_mont, const uint32_t* base_index,
+                                 const uint64_t* offsets, size_t k, void* stream, void* d_out_affine) {
+  if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
+  size_t need = 0;
+  rc = check_bases_batch_index(b, base_index, offsets, k, &need);
+  if (rc) return rc;
+  if (!d_out_affine || (offsets[k] && !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  std::lock_guard<std::mutex> lk(b->mu);
+  hipStream_t st = (hipStream_t)stream;
+  switch (b->curve) {
+    case MLHIP_CURVE_BN254:
+      return mlhip_tu_bases_batch_Bn254(b->group, &b->batch, b->d_pts, b->n, d_scalars, scalars_mont, base_index, offsets, k, need,
+                                        d_out_affine, st);
+    case MLHIP_CURVE_BLS12_381:
+      return mlhip_tu_bases_batch_Bls381(b->group, &b->batch, b->d_pts, b->n, d_scalars, scalars_mont, base_index, offsets, k, need,
+                                         d_out_affine, st);
+    default:
+      return mlhip_tu_bases_batch_Bls377(b->group, &b->batch, b->d_pts, b->n, d_scalars, scalars_mont, base_index, offsets, k, need,
+                                         d_out_affine, st);
+  }
+}
+
+int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont, const uint32_t* base_index, const uint64_t* offsets,
+                          size_t k, void* out_affine) {
+  if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
+  size_t need = 0;
+  rc = check_bases_batch_index(b, base_index, offsets, k, &need);
+  if (rc) return rc;
+  const size_t n = offsets[k];
+  if (!out_affine || (n && !scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  // the call's scratch comes from the process's device (HostCall); a handle made there before a later mlhip_init moved it
+  // elsewhere has to be driven through the device form
+  if (b->device != g_device) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle lives on another device");
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  HostCall hc;
+  hc.reserve(n * 32 + k * b->ptsz);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(k * b->ptsz);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_bases_msm_batch_device(b, ds, scalars_mont, base_index, offsets, k, hc.l.st, dout);
+  if (rc) return rc;
+  return hc.down(out_affine, dout, k * b->ptsz);
+}
+
+int mlhip_bases_batch_tabled(mlhip_bases* b, size_t* n_tabled) {
+  if (!b || !n_tabled) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!b->shards.empty()) {
+    *n_tabled = 0;
+    return 0;
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  *n_tabled = b->batch.n_tabled;
+  return 0;
 }
 
 mlhip_msm_plan* mlhip_bases_plan(mlhip_bases* b) { return b && b->shards.empty() ? b->plan : nullptr; }

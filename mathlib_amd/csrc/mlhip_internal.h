@@ -120,6 +120,14 @@ struct mlhip_msm_plan {
 };
 
 
+// the per-base fixed-window tables of a mlhip_bases handle for mlhip_bases_msm_batch (msm_bases_batch.h): rows of bases
+// [0, n_tabled) at width w, on the handle's device; freed by mlhip_bases_destroy
+struct mlhip_bases_batch_tables {
+  char* buf = nullptr;
+  size_t n_tabled = 0;
+  int w = 0;
+};
+
 // per-curve entry points, defined in tu_msm_<curve>.hip / tu_pairing_<curve>.hip
 #define MLHIP_DECLARE_CURVE(NAME)                                                                                   \
   int mlhip_tu_plan_alloc_##NAME(mlhip_msm_plan* p);                                                                \
@@ -144,6 +152,9 @@ struct mlhip_msm_plan {
   int mlhip_tu_plan_fold_build_##NAME(mlhip_msm_plan* p, const void* d_points, size_t n, hipStream_t st);          \
   int mlhip_tu_msm_batch_##NAME(int group, const void* d_points, const void* d_scalars, int mont,                 \
                                 const uint64_t* offsets, size_t k, void* d_out, hipStream_t st);                   \
+  int mlhip_tu_bases_batch_##NAME(int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases,       \
+                                  const void* d_scalars, int mont, const uint32_t* base_index, const uint64_t* offsets, \
+                                  size_t k, size_t need, void* d_out, hipStream_t st);                              \
   void mlhip_tu_release_cache_##NAME(void);
 // G1 points outside the prime-order subgroup (or off the curve) in an array of affine points: mlhip_bases_create's check
 int mlhip_tu_g1_count_outside_subgroup_Bls377(const void* d_pts, size_t n, uint32_t* d_bad, hipStream_t st);

@@ -29,7 +29,7 @@ inline bool msm_batch_p_valid(int p) { return p == 1 || p == 2 || p == 4 || p ==
 struct MsmBatchChunk {
   uint64_t first;  // index of the chunk's first pair in points / scalars
   uint32_t count;  // 1 .. P pairs
-  uint32_t pad;
+  uint32_t base0;  // mlhip_bases_msm_batch without an index list: the position of the first pair in its segment (= its base)
 };
 struct MsmBatchGroup {
   uint32_t begin, count;  // partials [begin, begin + count) of the pass's input, all of one segment
@@ -55,7 +55,8 @@ inline bool msm_batch_layout(MsmBatchLayout& L, const uint64_t* offsets, size_t 
   for (size_t s = 0; s < k; s++) {
     const uint64_t a = offsets[s], b = offsets[s + 1];
     n[s] = (b - a + (uint64_t)P - 1) / (uint64_t)P;
-    for (uint64_t f = a; f < b; f += (uint64_t)P) L.chunks.push_back({f, (uint32_t)(b - f < (uint64_t)P ? b - f : (uint64_t)P), 0u});
+    for (uint64_t f = a; f < b; f += (uint64_t)P)
+      L.chunks.push_back({f, (uint32_t)(b - f < (uint64_t)P ? b - f : (uint64_t)P), (uint32_t)(f - a)});
   }
   if (L.chunks.size() >= ((uint64_t)1 << 32)) return false;
   for (;;) {
@@ -299,22 +300,21 @@ void msm_batch_launch_chunks(const void* d_points, const void* d_scalars, int mo
         (const Affine<Fp2Field<C>>*)d_points, (const uint32_t*)d_scalars, mont, d_chunks, n_chunks, (XYZZ<Fp2Field<C>>*)d_partials);
 }
 
-// offsets: k + 1 checked host entries (api.hip: mlhip_msm_batch_device), k >= 1
-template <class C, class F>
-int msm_batch_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
-                     hipStream_t st) {
+// the passes of one batch call over a built layout: one upload of [chunk table | groups | extra] on the call's stream,
+// launch(d_chunks, n_chunks, d_extra, d_partials) queues the chunk kernel (n_chunks >= 1), then the sum passes write the k
+// affine results.  extra: extra_bytes of host data the chunk kernel reads (the base indices of mlhip_bases_msm_batch)
+template <class C, class F, class Launch>
+int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes, void* d_out, hipStream_t st, Launch launch) {
   constexpr bool kG1 = std::is_same<F, FpField<C>>::value;
-  const int P = msm_batch_chunk_len<C, F>();
-  MsmBatchLayout L;
-  if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: more than 2^32 - 1 chunks");
   const size_t n_chunks = L.chunks.size(), n_groups = L.groups.size();
   const size_t chunk_bytes = n_chunks * sizeof(MsmBatchChunk), group_bytes = n_groups * sizeof(MsmBatchGroup);
-  const size_t meta = (chunk_bytes + group_bytes + 255) & ~(size_t)255;
+  const size_t meta = (chunk_bytes + group_bytes + extra_bytes + 255) & ~(size_t)255;
   const size_t a_bytes = ((n_chunks * sizeof(XYZZ<F>)) + 255) & ~(size_t)255;
   const size_t need = meta + a_bytes + L.max_mid * sizeof(XYZZ<F>);
-  std::vector<char> host(chunk_bytes + group_bytes);
+  std::vector<char> host(chunk_bytes + group_bytes + extra_bytes);
   if (chunk_bytes) memcpy(host.data(), L.chunks.data(), chunk_bytes);
   memcpy(host.data() + chunk_bytes, L.groups.data(), group_bytes);
+  if (extra_bytes) memcpy(host.data() + chunk_bytes + group_bytes, extra, extra_bytes);
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mb_mu);
@@ -335,14 +335,7 @@ int msm_batch_device(const void* d_points, const void* d_scalars, int mont, cons
   const MsmBatchChunk* d_chunks = (const MsmBatchChunk*)mb.buf;
   const MsmBatchGroup* d_groups = (const MsmBatchGroup*)(mb.buf + chunk_bytes);
   void* bufs[2] = {mb.buf + meta, mb.buf + meta + a_bytes};
-  if (n_chunks) {
-    switch (P) {
-      case 1: msm_batch_launch_chunks<C, F, 1>(d_points, d_scalars, mont, d_chunks, (uint32_t)n_chunks, bufs[0], st); break;
-      case 2: msm_batch_launch_chunks<C, F, 2>(d_points, d_scalars, mont, d_chunks, (uint32_t)n_chunks, bufs[0], st); break;
-      case 4: msm_batch_launch_chunks<C, F, 4>(d_points, d_scalars, mont, d_chunks, (uint32_t)n_chunks, bufs[0], st); break;
-      default: msm_batch_launch_chunks<C, F, 8>(d_points, d_scalars, mont, d_chunks, (uint32_t)n_chunks, bufs[0], st); break;
-    }
-  }
+  if (n_chunks) launch(d_chunks, (uint32_t)n_chunks, (const void*)(mb.buf + chunk_bytes + group_bytes), bufs[0]);
   const size_t passes = L.pass_begin.size() - 1;
   for (size_t q = 0; q < passes; q++) {
     const bool last = q + 1 == passes;
@@ -360,6 +353,23 @@ int msm_batch_device(const void* d_points, const void* d_scalars, int mont, cons
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(mb.last, st));
   return 0;
+}
+
+// offsets: k + 1 checked host entries (api.hip: mlhip_msm_batch_device), k >= 1
+template <class C, class F>
+int msm_batch_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
+                     hipStream_t st) {
+  const int P = msm_batch_chunk_len<C, F>();
+  MsmBatchLayout L;
+  if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: more than 2^32 - 1 chunks");
+  return msm_batch_run<C, F>(L, nullptr, 0, d_out, st, [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void*, void* part) {
+    switch (P) {
+      case 1: msm_batch_launch_chunks<C, F, 1>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
+      case 2: msm_batch_launch_chunks<C, F, 2>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
+      case 4: msm_batch_launch_chunks<C, F, 4>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
+      default: msm_batch_launch_chunks<C, F, 8>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
+    }
+  });
 }
 #endif  // __HIPCC__
 

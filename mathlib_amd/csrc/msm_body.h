@@ -124,6 +124,9 @@ MLHIP_HD uint32_t msm_window_digit(const uint32_t (&s)[8], int off, int width, u
   return v;
 }
 
+// windows of a signed w-bit fixed-base table (msm_scalar_mul.h, msm_bases_batch.h): ceil(256 / w)
+MLHIP_HD int fb_windows(int w) { return (256 + w - 1) / w; }
+
 // Encoded as 0 (skip) or (magnitude << 1) | sign with magnitude in [1, 2^(width-1)] -> bucket magnitude-1.
 template <class C>
 MLHIP_HD void msm_digits_body(size_t i, size_t n, const uint32_t* scalars, bool mont, int c, int W,

@@ -13,18 +13,21 @@ namespace mlhip {
 template <class C, class F>
 __global__ void __launch_bounds__(64) k_scalar_mul(const Affine<F>* __restrict__ points, size_t point_stride,
                                                    const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                   Affine<F>* __restrict__ out, const uint32_t* __restrict__ skip = nullptr) {
+                                                   Affine<F>* __restrict__ out, const uint32_t* __restrict__ skip = nullptr,
+                                                   uint32_t per_point = 0) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (skip && *skip) return;  // the fixed-base table of this base is still in `out` (k_fb_check)
+  // per_point != 0 (the tables of many bases, msm_bases_batch.h): product i is [scalars[i % per_point]] points[i / per_point]
+  const size_t si = per_point ? i % per_point : i, pi = per_point ? i / per_point : i * point_stride;
   uint32_t s[8];
   if (mont < 0) {  // plain 256-bit integers, not reduced mod r (the fixed-base table: [d 2^(8j)]P for ANY P on the curve)
 #pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = scalars[8 * i + k];
+    for (int k = 0; k < 8; k++) s[k] = scalars[8 * si + k];
   } else {
-    fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+    fr_canonical<C>(s, scalars + 8 * si, mont != 0);
   }
-  const Affine<F> P = points[i * point_stride];
+  const Affine<F> P = points[pi];
   uint32_t sw[9];
   signed_windows4(sw, s);
   XYZZ<F> tab[8];
@@ -86,7 +89,7 @@ constexpr size_t FB_HEADER = 512;  // bytes in front of the table: [flag | tag |
 // header word: 1 iff the base lies in the prime-order subgroup ([r]P = infinity, computed by the table build itself as one
 // extra entry) on a curve with a twisted Edwards model -- the products then run on the 7-product Edwards addition (ed28.h)
 constexpr uint32_t FB_FLAG_ED = 120;
-MLHIP_HD int fb_windows(int w) { return (256 + w - 1) / w; }
+// (fb_windows(w) = ceil(256 / w), the number of windows of such a table: msm_body.h)
 
 struct FixedBaseScratch {
   char* buf = nullptr;
@@ -324,22 +327,23 @@ template <class C>
 __global__ void __launch_bounds__(64) k_scalar_mul_lp(const Affine<Fp2Field<C>>* __restrict__ points, size_t point_stride,
                                                       const uint32_t* __restrict__ scalars, int mont, size_t n,
                                                       Affine<Fp2Field<C>>* __restrict__ out,
-                                                      const uint32_t* __restrict__ skip = nullptr) {
+                                                      const uint32_t* __restrict__ skip = nullptr, uint32_t per_point = 0) {
   typedef Fp2LField<C> FL;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 1;  // both lanes of a pair share i and the scalar: every branch below is pair-uniform
   if (i >= n) return;
   if (skip && *skip) return;
   const int hi = (int)(threadIdx.x & 1u);
+  const size_t si = per_point ? i % per_point : i, pi = per_point ? i / per_point : i * point_stride;  // (k_scalar_mul)
   uint32_t s[8];
   if (mont < 0) {
 #pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = scalars[8 * i + k];
+    for (int k = 0; k < 8; k++) s[k] = scalars[8 * si + k];
   } else {
-    fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+    fr_canonical<C>(s, scalars + 8 * si, mont != 0);
   }
   Affine<FL> P;
-  lp_load_affine<C>(P, points, i * point_stride, hi);
+  lp_load_affine<C>(P, points, pi, hi);
   uint32_t sw[9];
   signed_windows4(sw, s);
   XYZZ<FL> tab[8];

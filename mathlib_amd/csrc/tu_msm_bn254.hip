@@ -38,6 +38,13 @@ int mlhip_tu_msm_batch_Bn254(int group, const void* d_points, const void* d_scal
   if (group == MLHIP_GROUP_G1) return msm_batch_device<Bn254, FpField<Bn254>>(d_points, d_scalars, mont, offsets, k, d_out, st);
   return msm_batch_device<Bn254, Fp2Field<Bn254>>(d_points, d_scalars, mont, offsets, k, d_out, st);
 }
+int mlhip_tu_bases_batch_Bn254(int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars,
+                             int mont, const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out,
+                             hipStream_t st) {
+  if (group == MLHIP_GROUP_G1)
+    return bases_batch_device<Bn254, FpField<Bn254>>(t, d_pts, n_bases, d_scalars, mont, base_index, offsets, k, need, d_out, st);
+  return bases_batch_device<Bn254, Fp2Field<Bn254>>(t, d_pts, n_bases, d_scalars, mont, base_index, offsets, k, need, d_out, st);
+}
 void mlhip_tu_release_cache_Bn254(void) {
   fixed_base_release();
   msm_batch_release();

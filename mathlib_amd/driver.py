@@ -552,6 +552,31 @@ class Bases:
         check(self._lib.mlhip_bases_msm(self._h, c._scalars(scalars), 1 if c.scalars_mont else 0, len(scalars), out))
         return G1(out.raw, c)
 
+    def MultiScalarMulBatch(self, scalar_lists: Sequence[Sequence[Zr]], index_lists=None) -> List[G1]:
+        """out[i] = sum_j [scalar_lists[i][j]] B[index_lists[i][j]] (without index lists: B[j], as MultiScalarMul) for many small
+        MSMs over the resident bases in one device call (include/mlhip.h: mlhip_bases_msm_batch).  Each segment keeps
+        MultiScalarMul's rule: at most n scalars without an index list; with one, as many indices as scalars, each below n."""
+        c = self.curve
+        lengths = [len(b) for b in scalar_lists]
+        if index_lists is None:
+            if any(m > self.n for m in lengths):
+                raise IndexError("MultiScalarMulBatch: more scalars than resident bases")
+        else:
+            if len(index_lists) != len(scalar_lists):
+                raise ValueError("MultiScalarMulBatch: %d scalar lists, %d index lists" % (len(scalar_lists), len(index_lists)))
+            for b, ix in zip(scalar_lists, index_lists):
+                if len(ix) != len(b):
+                    raise ValueError("MultiScalarMulBatch: as many indices as scalars in every segment")
+                if any(i < 0 or i >= self.n for i in ix):
+                    raise IndexError("MultiScalarMulBatch: base index out of range")
+        scs = b"".join(c._scalars(b) for b in scalar_lists)
+        raw = _lib.bases_msm_batch(self._lib, self._h, c.g1_bytes, scs, c.scalars_mont, lengths, index_lists)
+        return [G1(r, c) for r in raw]
+
+    def BatchTabled(self) -> int:
+        """the number of leading bases that have MultiScalarMulBatch tables (include/mlhip.h: mlhip_bases_batch_tabled)"""
+        return _lib.bases_batch_tabled(self._lib, self._h)
+
     def CheckedSubgroup(self) -> bool:
         """every point of the table was verified on the device to lie in G1 (BLS12-377: Edwards bucket sums)"""
         return self._lib.mlhip_bases_checked_subgroup(self._h) == 1
