@@ -139,7 +139,8 @@ MLHIP_API int mlhip_msm_plan_create(int curve, int group, size_t max_n, int wind
 MLHIP_API int mlhip_msm_plan_destroy(mlhip_msm_plan* plan);
 /* d_points / d_scalars are device pointers; stream is a hipStream_t (NULL = default stream).
  * out_affine is HOST memory; the call returns after the result is there.  When out_xyzz is non-NULL
- * the un-normalised partial sum (X,Y,ZZ,ZZZ) is written there too (multi-GPU combine). */
+ * the un-normalised partial sum (X,Y,ZZ,ZZZ) is written there too (multi-GPU combine): x = X/ZZ, y = Y/ZZZ is out_affine,
+ * but the representation is not canonical -- two runs of one MSM can give different bytes for the same point. */
 MLHIP_API int mlhip_msm_run(mlhip_msm_plan* plan, const void* d_points, const void* d_scalars, int scalars_mont, size_t n,
                   void* stream, void* out_affine, void* out_xyzz);
 /* The same in two halves, so consecutive MSMs pipeline: mlhip_msm_launch enqueues the kernels and the

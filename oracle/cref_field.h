@@ -341,11 +341,10 @@ static void FN(add_step)(FN(g2p)* T, const FN(fp2)* qx, const FN(fp2)* qy, FN(fp
   FN(fp2_neg)(r1, &O);
 }
 
-static void FN(miller_loop)(FN(fp12)* f, const FN(g1a)* P, const FN(g2a)* Q, int n_pairs) {
+static void FN(miller_loop8)(FN(fp12)* f, const FN(g1a)* P, const FN(g2a)* Q, int n_pairs) {
   FN(fp12_one)(f);
   FN(g2p) T[8];
   int live[8], any = 0;
-  if (n_pairs > 8) n_pairs = 8;
   for (int k = 0; k < n_pairs; k++) {
     live[k] = !(FN(g1a_is_inf)(&P[k]) || FN(g2a_is_inf)(&Q[k]));
     T[k].x = Q[k].x; T[k].y = Q[k].y; FN(fp2_one)(&T[k].z);
@@ -382,6 +381,17 @@ static void FN(miller_loop)(FN(fp12)* f, const FN(g1a)* P, const FN(g2a)* Q, int
     }
   }
   if (K(_X_NEG)) FN(fp12_conj)(f, f);
+}
+
+/* any number of pairs: the shared loop of up to 8 pairs, times that of the next 8, ...  The loops share nothing but the
+ * squarings of the accumulator, so the product of the partial loops is the same Fp12 value as one loop over all pairs. */
+static void FN(miller_loop)(FN(fp12)* f, const FN(g1a)* P, const FN(g2a)* Q, int n_pairs) {
+  FN(miller_loop8)(f, P, Q, n_pairs < 8 ? n_pairs : 8);
+  for (int k = 8; k < n_pairs; k += 8) {
+    FN(fp12) g;
+    FN(miller_loop8)(&g, P + k, Q + k, n_pairs - k < 8 ? n_pairs - k : 8);
+    FN(fp12_mul)(f, f, &g);
+  }
 }
 
 /* z^|x| (plain squarings: the oracle does not use cyclotomic squaring), conjugated for a negative seed */

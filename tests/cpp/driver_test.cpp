@@ -166,6 +166,21 @@ static void runPairingTest(const Curve& c, const G2& g2, uint64_t& st) {
   prod.Mul(batch[1]);
   prod.Mul(batch[2]);
   EXPECT(c.PairingProduct(qs, ps).Equals(prod));
+  {  // against a known exponent, not only against the batch: e(G1, G2)^(r1 r2 + r2 + r1); with ([-s]G1, G2) appended the
+     // product is what a verifier checks, exactly one
+    Zr s = r1.Mul(r2).Plus(r2).Plus(r1);
+    Gt want = c.FExp(c.Pairing(g2, g1.Mul(s)));
+    EXPECT(!want.IsUnity());
+    EXPECT(c.PairingProduct(qs, ps).Equals(want));
+    EXPECT(gengt.Exp(s).Equals(want));
+    std::vector<G1> vps = ps;
+    std::vector<G2> vqs = qs;
+    vps.push_back(g1.Mul(s.Neg()));
+    vqs.push_back(g2);
+    EXPECT(c.PairingProduct(vqs, vps).IsUnity());
+    vps.back() = g1.Mul(s);  // the sign matters: e(G1, G2)^(2s) is not one
+    EXPECT(!c.PairingProduct(vqs, vps).IsUnity());
+  }
   G2 sum = g2.Mul(r1);
   sum.Add(g2.Mul(r2));
   EXPECT(c.MultiScalarMulG2({g2, g2}, {r1, r2}).Equals(sum));

@@ -64,3 +64,19 @@ def test_cref_input_generator(name):
     gq = cref.gen_points(cid, 2, k0, k1, 5)
     assert R.g2_from_mont_bytes(cp, gq[3 * qs : 4 * qs]) == R.g2_mul(cp, R.g2_generator(cp), k0 + 3 * k1)
     assert cref.point_mul(cid, 1, R.g1_to_mont_bytes(cp, cp.g1), k0) == gp[:ps]
+
+
+@pytest.mark.parametrize("name", CURVES)
+def test_cref_miller_loop_any_pairs_per_product(name):
+    """cref.miller_loop with more than 8 pairs per product (mlhip_pairing_product's oracle): once it kept the first 8 pairs
+    and silently dropped the rest.  FExp of the product of n pairs ([a_i]G1, [b_i]G2) is e(G1, G2)^(sum a_i b_i)."""
+    cp = R.CURVES[name]
+    cid = cp.curve_id
+    n = 17
+    g1 = cref.gen_points(cid, 1, 11, 13, n)
+    g2 = cref.gen_points(cid, 2, 17, 19, n)
+    gen1, gen2 = cref.gen_points(cid, 1, 1, 0, 1), cref.gen_points(cid, 2, 1, 0, 1)
+    for m in (8, 9, 16, 17):
+        s = sum((11 + 13 * i) * (17 + 19 * i) for i in range(m)) % cp.r
+        got = cref.final_exp(cid, cref.miller_loop(cid, g1[: m * len(gen1)], g2[: m * len(gen2)], m, 1, 2), 1)
+        assert got == cref.pairing_batch(cid, cref.point_mul(cid, 1, gen1, s), gen2, 1), (name, m)

@@ -9,6 +9,7 @@ import os
 import pytest
 
 from conftest import load_golden, load_msm1000
+from wire_cases import g1_bad_encodings, g1_off_curve_uncompressed, g2_bad_encodings
 
 pytestmark = pytest.mark.gpu
 
@@ -426,39 +427,16 @@ def test_g1_wire_codec_vs_oracle(lib, mlhip, curve):
         mlhip.check(lib.mlhip_g1_to_bytes(cid, out.raw, len(pts), comp, back))
         assert back.raw == wire  # runToFroBytesTest / runToFroCompressedTest (math_test.go:511-589)
     # invalid encodings: every status must agree with the oracle's SetBytes restatement
-    bad = []
-    x = 1
-    while len(bad) < 4:  # x^3 + b a non-residue
-        x += 1
-        if R.fp_sqrt((x**3 + cp.b) % cp.p, cp.p) is None:
-            w = bytearray(x.to_bytes(n, "big"))
-            w[0] |= 0x80
-            bad.append(bytes(w))
-    w = bytearray(cp.p.to_bytes(n, "big"))  # coordinate >= p
-    w[0] |= 0x80
-    bad.append(bytes(w))
-    w = bytearray(R.g1_wire_compressed(cp, None))  # infinity with stray bits
-    w[7] = 3
-    bad.append(bytes(w))
-    if cp.family == "BLS12":  # on the curve but outside the r-torsion subgroup
-        x = 2
-        while True:
-            y = R.fp_sqrt((x**3 + cp.b) % cp.p, cp.p)
-            if y is not None and R.g1_mul_unreduced(cp, (x, y), cp.r) is not None:
-                break
-            x += 1
-        bad.append(R.g1_wire_compressed(cp, (x, y)))
-    bad.append(R.g1_wire_compressed(cp, pts[0]))  # a good one in between
+    bad = g1_bad_encodings(R, cp, pts[0])  # (the last one is a good one in between)
     st = ctypes.create_string_buffer(len(bad))
     out = ctypes.create_string_buffer(2 * n * len(bad))
     for mode in (1, 2):  # 1: endomorphism test (BLS12), 2: the plain [r]P ladder -- both exact
         mlhip.check(lib.mlhip_g1_from_bytes(cid, b"".join(bad), len(bad), 1, mode, out, st))
         assert list(st.raw) == [R.g1_from_wire(cp, w)[1] for w in bad], mode
         assert out.raw[-2 * n :] == R.g1_to_mont_bytes(cp, pts[0])
-    w = bytearray(R.g1_wire_uncompressed(cp, pts[1]))  # uncompressed, off the curve
-    w[-1] ^= 1
+    w = g1_off_curve_uncompressed(R, cp, pts[1])  # uncompressed, off the curve
     st1 = ctypes.create_string_buffer(1)
-    mlhip.check(lib.mlhip_g1_from_bytes(cid, bytes(w), 1, 0, 1, ctypes.create_string_buffer(2 * n), st1))
+    mlhip.check(lib.mlhip_g1_from_bytes(cid, w, 1, 0, 1, ctypes.create_string_buffer(2 * n), st1))
     assert st1.raw[0] == 2
 
 
@@ -467,7 +445,6 @@ def test_g2_wire_codec_vs_oracle(lib, mlhip, curve):
     from oracle import pyref as R
 
     cp = R.CURVES[curve]
-    T = R.tower(cp)
     cid = cp.curve_id
     n = cp.fp_bytes
     d = R.Drbg("gpu/codec2/" + curve)
@@ -483,24 +460,7 @@ def test_g2_wire_codec_vs_oracle(lib, mlhip, curve):
         back = ctypes.create_string_buffer(len(wire))
         mlhip.check(lib.mlhip_g2_to_bytes(cid, out.raw, len(pts), comp, back))
         assert back.raw == wire
-    bad = []
-    k = 1
-    while len(bad) < 3:
-        k += 1
-        x = (k, 0) if len(bad) == 0 else (k, 1)
-        if T.f2_sqrt(T.f2_add(T.f2_mul(T.f2_sqr(x), x), R.twist_b(cp))) is None:
-            w = bytearray(x[1].to_bytes(n, "big") + x[0].to_bytes(n, "big"))
-            w[0] |= 0x80
-            bad.append(bytes(w))
-    w = bytearray((1).to_bytes(n, "big") + cp.p.to_bytes(n, "big"))
-    w[0] |= 0x80
-    bad.append(bytes(w))
-    w = bytearray(R.g2_wire_compressed(cp, None))
-    w[n + 3] = 1
-    bad.append(bytes(w))
-    Qx = R._g2_some_point(cp, 3)
-    bad.append(R.g2_wire_compressed(cp, Qx))
-    bad.append(R.g2_wire_compressed(cp, pts[0]))
+    bad, Qx = g2_bad_encodings(R, cp, pts[0])
     st = ctypes.create_string_buffer(len(bad))
     out = ctypes.create_string_buffer(4 * n * len(bad))
     want = [R.g2_from_wire(cp, w)[1] for w in bad]
