@@ -638,3 +638,62 @@ func (b *Bases) Close() {
 		b.h = nil
 	}
 }
+
+// G2Prepared holds fixed G2 points with their Miller-loop lines resident on the device (mlhip_g2_prepared_*): the G2
+// arguments of the verifier's Pairing2 + FExp (bls12-381.go:448-468), prepared once.
+type G2Prepared struct {
+	h *C.mlhip_g2_prepared
+	m int
+}
+
+func (c *Curve) NewG2Prepared(points []driver.G2) *G2Prepared {
+	m := len(points)
+	if m == 0 {
+		panic("hip: NewG2Prepared needs at least one point")
+	}
+	aff := make([]bls12381.G2Affine, m)
+	for i := range points {
+		aff[i] = points[i].(*gurvy381.G2).G2Affine
+	}
+	p := &G2Prepared{m: m}
+	check(func() C.int {
+		return C.mlhip_g2_prepared_create(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&aff[0]), C.size_t(m), &p.h)
+	})
+	return p
+}
+
+// Pairing2Batch returns out[k] = FExp(Pairing2(Q[0], Q[1], p1a[k], p1b[k])) for the handle's first two points: the
+// verifier's pairing check over K proofs in one launch (mlhip_pairing_prepared).
+func (p *G2Prepared) Pairing2Batch(p1a, p1b []driver.G1) []driver.Gt {
+	n := len(p1a)
+	if len(p1b) != n {
+		panic("hip: Pairing2Batch length mismatch")
+	}
+	if p.m < 2 {
+		panic("hip: Pairing2Batch needs a handle of two points")
+	}
+	if n == 0 {
+		return nil
+	}
+	g1 := make([]bls12381.G1Affine, 2*n)
+	for i := 0; i < n; i++ {
+		g1[2*i] = p1a[i].(*gurvy381.G1).G1Affine
+		g1[2*i+1] = p1b[i].(*gurvy381.G1).G1Affine
+	}
+	gts := make([]bls12381.GT, n)
+	check(func() C.int {
+		return C.mlhip_pairing_prepared(p.h, unsafe.Pointer(&g1[0]), nil, 2, C.size_t(n), unsafe.Pointer(&gts[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range gts {
+		out[i] = &gurvy381.Gt{GT: gts[i]}
+	}
+	return out
+}
+
+func (p *G2Prepared) Close() {
+	if p.h != nil {
+		C.mlhip_g2_prepared_destroy(p.h)
+		p.h = nil
+	}
+}

@@ -285,6 +285,56 @@ MLHIP_API int mlhip_bases_msm_batch_device(mlhip_bases* bases, const void* d_sca
  * table-free path) */
 MLHIP_API int mlhip_bases_batch_tabled(mlhip_bases* bases, size_t* n_tabled);
 
+/* ---- prepared G2 handles: pairings against FIXED G2 points ("G2Prepared") ------------------------------------------------
+ * The reference's verifier calls Pairing2(g, sig, pk, h) + FExp with the same two G2 arguments in every call
+ * (driver/gurvy/bls12381/bls12-381.go:448-468); so do BBS+ and idemix verification.  The line coefficients of the Miller loop
+ * depend on Q alone: a handle computes them once for each of its m points -- 68 lines of three Fp2 per BLS12-381 point, 23 KB,
+ * stored in loop order in the limb form the kernels multiply in -- and keeps them, with the affine points, on the device that
+ * is current at creation.  A prepared Miller loop then carries no G2 point at all.
+ * m >= 1; the points are affine G2 points in the layout of mlhip_miller_loop, infinity all zero.  A point on the curve but
+ * outside the subgroup gives what mlhip_miller_loop gives for it (the same arithmetic); a point off the curve gives an
+ * undefined result, never a fault.  The tables are read-only after creation: calls on one handle from several threads run
+ * concurrently, there is no per-handle lock.  mlhip_release_cache does not touch a handle.  No CPU fallback: MLHIP_ENODEVICE
+ * without a device. */
+typedef struct mlhip_g2_prepared mlhip_g2_prepared;
+/* bls12-381.go:448-468: the G2 arguments of Pairing / Pairing2, prepared once (host points) */
+MLHIP_API int mlhip_g2_prepared_create(int curve, const void* g2_points, size_t m, mlhip_g2_prepared** h);
+/* bls12-381.go:448-468: the same from device memory; a copy is taken, the caller's buffer is free again on return */
+MLHIP_API int mlhip_g2_prepared_create_device(int curve, const void* d_g2_points, size_t m, mlhip_g2_prepared** h);
+/* bls12-381.go:448-468: the number of points m of the handle */
+MLHIP_API int mlhip_g2_prepared_count(mlhip_g2_prepared* h, size_t* m);
+MLHIP_API int mlhip_g2_prepared_destroy(mlhip_g2_prepared* h);
+/* bls12-381.go:448-464 (Pairing / Pairing2 without FExp):
+ *   out[k] = prod_{j < ppp} MillerLoop(g1[k ppp + j], Q[idx(j)]),   idx(j) = q_index ? q_index[j] : j
+ * not final-exponentiated (raw values are defined up to what FExp kills, as for mlhip_miller_loop; after mlhip_final_exp they
+ * are byte-identical to mlhip_final_exp(mlhip_miller_loop(..)) on the expanded pairs).  q_index is HOST memory in both forms
+ * and has ppp entries that ALL products share: slot j of every product pairs with the same Q, which keeps the line reads
+ * uniform across a wave.  ppp = 1 .. 4.  A G1 argument at infinity, or a Q at infinity, contributes 1.  n_products = 0 does
+ * nothing.  MLHIP_EINVAL before anything is launched for a null handle, ppp outside 1 .. 4, an index >= m, ppp > m without
+ * q_index.
+ * Kernels: one product per quad of lanes up to 2^14 products (BLS12-377: 2^15, its Miller loop at every size), per lane pair
+ * above -- the sizes the general entry points switch at; MLHIP_PAIRING_QUAD=0|1 forbids / forces the quads.  Switch to the
+ * general kernels: at no size, on any curve.  In the A/B against the general entry points on an MI355X
+ * (tools/perf_g2_prepared.py -> profiles/g2_prepared_ab.txt: ppp 1, 2 x 1, 2^10, 2^14, 2^16 products; DESIGN.md section 10 has
+ * the table) the prepared kernels are ahead at every grid point; at 2^16 products of two pairs the Miller loop takes about two
+ * thirds of the general one's time on every curve.  prepared_general_range() (pairing_prepared_kernels.h) is where a losing
+ * size would go: inside it the general kernels run on the Qs expanded from the handle's affine copy, same bytes after FExp.
+ * MLHIP_G2_PREPARED_GENERAL=1 selects that path at every size (0: never); it allocates and frees its scratch per call, so a
+ * _device call through it returns only when its work is done and cannot be captured into a graph.
+ * The _device forms launch on the handle's device and leave the caller's current device as it was; `stream` and the device
+ * pointers must belong to the handle's device. */
+MLHIP_API int mlhip_miller_loop_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp,
+                                         size_t n_products, void* out_gt);
+/* bls12-381.go:448-464: the same on device pointers, in order on `stream` */
+MLHIP_API int mlhip_miller_loop_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                                size_t n_products, void* d_out_gt, void* stream);
+/* bls12-381.go:448-468: out[k] = FExp of the same product -- the verifier's whole Pairing2 + FExp in one launch */
+MLHIP_API int mlhip_pairing_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp,
+                                     size_t n_products, void* out_gt);
+/* bls12-381.go:448-468: the same on device pointers, in order on `stream` */
+MLHIP_API int mlhip_pairing_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                            size_t n_products, void* d_out_gt, void* stream);
+
 /* The host-buffer MSM entry points above keep up to 16 plans + input buffers (at most 32 GB) alive between calls (creating and
  * destroying them costs as much as a 2^20-point MSM); this frees the idle ones.  MLHIP_NO_PLAN_CACHE=1 disables the pool. */
 MLHIP_API int mlhip_release_cache(void);
@@ -345,6 +395,7 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *                                      per chunk on the table path, 1, 2, 4, 8 or 16 (default: the largest that fills 2^16 lanes)
  *     MLHIP_BASES_BATCH_MAX_MB=m       ... tables per handle at most m MB (default 1024; 0 = never: the table-free path)
  *     MLHIP_PAIRING_QUAD=0|1           BLS12-381: never / always one pairing per quad of lanes (default: up to 2^14 elements)
+ *     MLHIP_G2_PREPARED_GENERAL=1      mlhip_*_prepared*: the general kernels on the Qs expanded from the handle (same bytes after FExp)
  *   2nd impl (parity tests; DESIGN.md section 2 lists which test runs which)
  *     MLHIP_ACC32=1                    boundary-form (32-bit limb) bucket accumulation, G1 and G2
  *     MLHIP_REDUCE32=1, MLHIP_REDUCE_ONE_LANE=1   boundary-form / one-point-per-lane bucket reduction

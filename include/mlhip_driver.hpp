@@ -695,6 +695,65 @@ class Bases {
   mlhip_bases* h_ = nullptr;
 };
 
+// Fixed G2 points with their Miller-loop lines resident on the device (mlhip_g2_prepared_*, bls12-381.go:448-468): the
+// G2 arguments of a verifier's Pairing2 + FExp, prepared once; destroyed with the object.
+class G2Prepared {
+ public:
+  G2Prepared(const Curve& c, const std::vector<G2>& points) : curve_(&c), m_(points.size()) {
+    Bytes q;
+    for (auto& x : points) q.insert(q.end(), x.raw.begin(), x.raw.end());
+    check(mlhip_g2_prepared_create(c.id, q.data(), m_, &h_));
+  }
+  G2Prepared(const G2Prepared&) = delete;
+  G2Prepared& operator=(const G2Prepared&) = delete;
+  ~G2Prepared() { mlhip_g2_prepared_destroy(h_); }
+  size_t Count() const {
+    size_t m = 0;
+    check(mlhip_g2_prepared_count(h_, &m));
+    return m;
+  }
+  // out[k] = prod_j MillerLoop(g1[k][j], Q[index[j]]) (no index: Q[j]); compare after FExp, as Curve::Pairing
+  std::vector<Gt> MillerLoopBatch(const std::vector<std::vector<G1>>& g1, const std::vector<uint32_t>* index = nullptr) const {
+    return run(false, g1, index);
+  }
+  // out[k] = FExp of the same product: Pairing2 + FExp over K proofs in one launch
+  std::vector<Gt> PairingBatch(const std::vector<std::vector<G1>>& g1, const std::vector<uint32_t>* index = nullptr) const {
+    return run(true, g1, index);
+  }
+
+ private:
+  std::vector<Gt> run(bool fused, const std::vector<std::vector<G1>>& g1, const std::vector<uint32_t>* index) const {
+    std::vector<Gt> out;
+    const size_t n = g1.size();
+    if (n == 0) return out;
+    const size_t ppp = g1[0].size();
+    Bytes p;
+    for (auto& l : g1) {
+      if (l.size() != ppp) throw std::invalid_argument("G2Prepared: every product takes the same number of G1 points");
+      for (auto& x : l) p.insert(p.end(), x.raw.begin(), x.raw.end());
+    }
+    if (index && index->size() != ppp) throw std::invalid_argument("G2Prepared: one index per pair of a product");
+    if (!index && ppp > m_) throw std::out_of_range("G2Prepared: more pairs per product than prepared points");
+    if (index)
+      for (uint32_t x : *index)
+        if (x >= m_) throw std::out_of_range("G2Prepared: point index out of range");
+    const size_t size = curve_->gt_bytes;
+    Bytes o(size * n);
+    const uint32_t* ix = index ? index->data() : nullptr;
+    check(fused ? mlhip_pairing_prepared(h_, p.data(), ix, ppp, n, o.data())
+                : mlhip_miller_loop_prepared(h_, p.data(), ix, ppp, n, o.data()));
+    for (size_t i = 0; i < n; i++) {
+      Gt g = curve_->new_gt();
+      g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);
+      out.push_back(g);
+    }
+    return out;
+  }
+  const Curve* curve_;
+  size_t m_;
+  mlhip_g2_prepared* h_ = nullptr;
+};
+
 // ---------------------------------------------------------------------------------------------------
 inline Zr Zr::Plus(const Zr& o) const {
   Zr z = *this;

@@ -67,6 +67,14 @@ SYMBOLS = [
     "mlhip_bases_msm_batch",
     "mlhip_bases_msm_batch_device",
     "mlhip_bases_batch_tabled",
+    "mlhip_g2_prepared_create",
+    "mlhip_g2_prepared_create_device",
+    "mlhip_g2_prepared_count",
+    "mlhip_g2_prepared_destroy",
+    "mlhip_miller_loop_prepared",
+    "mlhip_miller_loop_prepared_device",
+    "mlhip_pairing_prepared",
+    "mlhip_pairing_prepared_device",
     "mlhip_release_cache",
     "mlhip_g1_from_bytes",
     "mlhip_g1_to_bytes",
@@ -208,6 +216,14 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.mlhip_bases_msm_batch.argtypes = [vp, vp, ci, vp, vp, sz, vp]
     lib.mlhip_bases_msm_batch_device.argtypes = [vp, vp, ci, vp, vp, sz, vp, vp]
     lib.mlhip_bases_batch_tabled.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    lib.mlhip_g2_prepared_create.argtypes = [ci, vp, sz, ctypes.POINTER(c_void_p)]
+    lib.mlhip_g2_prepared_create_device.argtypes = [ci, vp, sz, ctypes.POINTER(c_void_p)]
+    lib.mlhip_g2_prepared_count.argtypes = [vp, ctypes.POINTER(ctypes.c_size_t)]
+    lib.mlhip_g2_prepared_destroy.argtypes = [vp]
+    for f in (lib.mlhip_miller_loop_prepared, lib.mlhip_pairing_prepared):
+        f.argtypes = [vp, vp, vp, sz, sz, vp]
+    for f in (lib.mlhip_miller_loop_prepared_device, lib.mlhip_pairing_prepared_device):
+        f.argtypes = [vp, vp, vp, sz, sz, vp, vp]
     lib.mlhip_g1_from_bytes.argtypes = [ci, vp, sz, ci, ci, vp, vp]
     lib.mlhip_g1_to_bytes.argtypes = [ci, vp, sz, ci, vp]
     lib.mlhip_g1_from_bytes_device.argtypes = [ci, vp, sz, ci, ci, vp, vp, vp]
@@ -286,6 +302,25 @@ def bases_batch_tabled(lib, handle) -> int:
     n = ctypes.c_size_t()
     check(lib.mlhip_bases_batch_tabled(handle, ctypes.byref(n)))
     return n.value
+
+
+def q_index_array(index, ppp: int):
+    """the q_index array of mlhip_*_prepared* (ppp uint32 entries shared by every product), or None"""
+    if index is None:
+        return None
+    index = list(index)
+    if len(index) != ppp:
+        raise ValueError("index must name one G2 point per pair of a product (%d entries, got %d)" % (ppp, len(index)))
+    return (ctypes.c_uint32 * max(1, ppp))(*index)
+
+
+def g2_prepared_run(lib, handle, gtsz: int, fused: bool, g1: bytes, index, ppp: int, n: int) -> bytes:
+    """mlhip_miller_loop_prepared (fused = False) / mlhip_pairing_prepared (True) on the handle `handle` of `lib`: n Gt
+    values (bytes) for n products of ppp pairs; g1 holds the n * ppp affine G1 points"""
+    out = ctypes.create_string_buffer(max(1, n * gtsz))
+    fn = lib.mlhip_pairing_prepared if fused else lib.mlhip_miller_loop_prepared
+    check(fn(handle, g1, q_index_array(index, ppp), ppp, n, out))
+    return out.raw[: n * gtsz]
 
 
 def init_devices(devices=None) -> None:

@@ -1524,6 +1524,149 @@ int mlhip_pairing_batch_device(int curve, const void* d_g1, const void* d_g2, si
   return tu_pairing(curve, 2, d_g1, d_g2, 1, n, nullptr, d_out_gt, (hipStream_t)stream);
 }
 
+// ---- prepared G2 handles (include/mlhip.h; kernels: pairing_prepared_kernels.h) ---------------------------------------------
+struct mlhip_g2_prepared {
+  mlhip_g2_prepared_tables t;
+  int curve = 0, device = 0;
+  size_t g1sz = 0, g2sz = 0, gtsz = 0;
+};
+
+static int tu_g2_prepared(int curve, mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                          size_t n, void* d_out, hipStream_t st) {
+  switch (curve) {
+    case MLHIP_CURVE_BN254: return mlhip_tu_g2_prepared_Bn254(t, what, d_g1, q_index, ppp, n, d_out, st);
+    case MLHIP_CURVE_BLS12_381: return mlhip_tu_g2_prepared_Bls381(t, what, d_g1, q_index, ppp, n, d_out, st);
+    case MLHIP_CURVE_BLS12_377: return mlhip_tu_g2_prepared_Bls377(t, what, d_g1, q_index, ppp, n, d_out, st);
+    default: return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  }
+}
+
+int mlhip_g2_prepared_destroy(mlhip_g2_prepared* h) {
+  if (!h) return 0;
+  (void)hipSetDevice(h->device);
+  if (h->t.d_q) (void)hipFree(h->t.d_q);
+  if (h->t.d_t28) (void)hipFree(h->t.d_t28);
+  if (h->t.d_t32) (void)hipFree(h->t.d_t32);
+  if (h->t.d_inf) (void)hipFree(h->t.d_inf);
+  delete h;
+  return 0;
+}
+
+static int g2_prepared_create(int curve, const void* points, bool on_device, size_t m, mlhip_g2_prepared** out) {
+  Sizes sz;
+  if (!curve_sizes(curve, sz)) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  *out = nullptr;
+  if (m == 0) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_g2_prepared_create: m must be at least 1");
+  if (!points) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  mlhip_g2_prepared* h = new mlhip_g2_prepared;
+  h->curve = curve;
+  h->device = g_device;
+  h->g1sz = sz.g1;
+  h->g2sz = sz.g2;
+  h->gtsz = sz.gt;
+  h->t.m = m;
+  auto body = [&]() -> int {
+    HIPCHK(hipMalloc(&h->t.d_q, m * sz.g2));
+    HostCall hc;  // a leased stream: the build does not meet other callers on the null stream
+    if (hc.rc) return hc.rc;
+    HIPCHK(hipMemcpyAsync(h->t.d_q, points, m * sz.g2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, hc.l.st));
+    int r = tu_g2_prepared(curve, &h->t, -1, nullptr, nullptr, 0, 0, nullptr, hc.l.st);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(hc.l.st));
+    return 0;
+  };
+  rc = body();
+  if (rc) {
+    mlhip_g2_prepared_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return 0;
+}
+
+int mlhip_g2_prepared_create(int curve, const void* g2_points, size_t m, mlhip_g2_prepared** h) {
+  return g2_prepared_create(curve, g2_points, false, m, h);
+}
+
+int mlhip_g2_prepared_create_device(int curve, const void* d_g2_points, size_t m, mlhip_g2_prepared** h) {
+  return g2_prepared_create(curve, d_g2_points, true, m, h);
+}
+
+int mlhip_g2_prepared_count(mlhip_g2_prepared* h, size_t* m) {
+  if (!h || !m) return mlhip_rt::fail(MLHIP_EINVAL, h ? "null pointer" : "null handle");
+  *m = h->t.m;
+  return 0;
+}
+
+// every argument error of the four entry points, before anything is launched; 1 = nothing to do
+static int g2_prepared_check(const mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
+                             const void* out) {
+  if (!h) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
+  if (q_index) {
+    for (size_t j = 0; j < ppp; j++)
+      if (q_index[j] >= h->t.m) return mlhip_rt::fail(MLHIP_EINVAL, "q_index entry beyond the handle's points");
+  } else if (ppp > h->t.m) {
+    return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product exceeds the handle's points (no q_index)");
+  }
+  if (n == 0) return 1;
+  if (!g1 || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  return 0;
+}
+
+static int g2_prepared_device(mlhip_g2_prepared* h, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,
+                              void* d_out, void* stream) {
+  int rc = g2_prepared_check(h, d_g1, q_index, ppp, n, d_out);
+  if (rc) return rc < 0 ? rc : 0;
+  // the launch needs the handle's device current; the caller gets its own current device back (`stream` and the pointers
+  // must belong to the handle's device: multi-device handles are out of scope)
+  int prev = h->device;
+  (void)hipGetDevice(&prev);
+  if (prev != h->device && hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  rc = tu_g2_prepared(h->curve, &h->t, what, d_g1, q_index, ppp, n, d_out, (hipStream_t)stream);
+  if (prev != h->device) (void)hipSetDevice(prev);
+  return rc;
+}
+
+static int g2_prepared_host(mlhip_g2_prepared* h, int what, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
+                            void* out) {
+  int rc = g2_prepared_check(h, g1, q_index, ppp, n, out);
+  if (rc) return rc < 0 ? rc : 0;
+  if (hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  g_device = h->device;  // thread_local (the device of this thread's call in progress): the call's scratch is leased on the handle's device
+  HostCall hc;
+  hc.reserve(n * ppp * h->g1sz + n * h->gtsz);
+  void* d1 = hc.up(g1, n * ppp * h->g1sz);
+  void* dout = hc.dev(n * h->gtsz);
+  if (hc.rc) return hc.rc;
+  rc = tu_g2_prepared(h->curve, &h->t, what, d1, q_index, ppp, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * h->gtsz);
+}
+
+int mlhip_miller_loop_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n_products,
+                               void* out_gt) {
+  return g2_prepared_host(h, 0, g1, q_index, ppp, n_products, out_gt);
+}
+
+int mlhip_miller_loop_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                      size_t n_products, void* d_out_gt, void* stream) {
+  return g2_prepared_device(h, 0, d_g1, q_index, ppp, n_products, d_out_gt, stream);
+}
+
+int mlhip_pairing_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n_products,
+                           void* out_gt) {
+  return g2_prepared_host(h, 2, g1, q_index, ppp, n_products, out_gt);
+}
+
+int mlhip_pairing_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                  size_t n_products, void* d_out_gt, void* stream) {
+  return g2_prepared_device(h, 2, d_g1, q_index, ppp, n_products, d_out_gt, stream);
+}
+
 int mlhip_gt_mul_device(int curve, const void* d_a, const void* d_b, size_t n, void* d_out, void* stream) {
   int rc = ensure_device();
   if (rc) return rc;

@@ -128,6 +128,16 @@ struct mlhip_bases_batch_tables {
   int w = 0;
 };
 
+// the device state of a mlhip_g2_prepared handle (pairing_prepared_kernels.h), on the handle's device; read-only once built,
+// freed by mlhip_g2_prepared_destroy
+struct mlhip_g2_prepared_tables {
+  void* d_q = nullptr;       // the m affine points
+  int32_t* d_t28 = nullptr;  // every line of every point in the carry-free form
+  void* d_t32 = nullptr;     // ... and in the boundary form (test build only)
+  uint32_t* d_inf = nullptr;  // [m]: the point is the point at infinity
+  size_t m = 0;
+};
+
 // per-curve entry points, defined in tu_msm_<curve>.hip / tu_pairing_<curve>.hip
 #define MLHIP_DECLARE_CURVE(NAME)                                                                                   \
   int mlhip_tu_plan_alloc_##NAME(mlhip_msm_plan* p);                                                                \
@@ -155,6 +165,9 @@ struct mlhip_bases_batch_tables {
   int mlhip_tu_bases_batch_##NAME(int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases,       \
                                   const void* d_scalars, int mont, const uint32_t* base_index, const uint64_t* offsets, \
                                   size_t k, size_t need, void* d_out, hipStream_t st);                              \
+  /* what = -1: build t's tables from t->d_q ; 0 / 2: Miller loops / fused pairings of n products against them */    \
+  int mlhip_tu_g2_prepared_##NAME(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, \
+                                  size_t ppp, size_t n, void* d_out, hipStream_t st);                               \
   void mlhip_tu_release_cache_##NAME(void);
 // G1 points outside the prime-order subgroup (or off the curve) in an array of affine points: mlhip_bases_create's check
 int mlhip_tu_g1_count_outside_subgroup_Bls377(const void* d_pts, size_t n, uint32_t* d_bad, hipStream_t st);

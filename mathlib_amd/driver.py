@@ -448,6 +448,11 @@ class Curve:
         """Upload a G1 point table once; Bases.MultiScalarMul(scalars) then moves only the scalars."""
         return Bases(self, points)
 
+    def NewG2Prepared(self, points: Sequence[G2]) -> "G2Prepared":
+        """Prepare fixed G2 points once (the generator and an issuer key, say); G2Prepared.PairingBatch(g1_lists) then runs
+        the verifier's Pairing2 + FExp over many proofs without any G2 arithmetic (include/mlhip.h: mlhip_g2_prepared_*)."""
+        return G2Prepared(self, points)
+
     def Pairing(self, p2: G2, p1: G1) -> Gt:
         """Miller loop only, like the gurvy drivers (bls12-381.go:448-455); compare after FExp."""
         out = ctypes.create_string_buffer(self.gt_bytes)
@@ -591,6 +596,56 @@ class Bases:
     def Close(self) -> None:
         if self._h:
             self._lib.mlhip_bases_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+class G2Prepared:
+    """Fixed G2 points with their Miller-loop lines resident on the device (mlhip_g2_prepared_*, bls12-381.go:448-468)."""
+
+    def __init__(self, curve: "Curve", points: Sequence[G2]):
+        self.curve = curve
+        self.m = len(points)
+        self._h = ctypes.c_void_p()
+        self._lib = _concrete()  # the handle stays with the library that made it
+        check(self._lib.mlhip_g2_prepared_create(curve.id, b"".join(q.raw for q in points), self.m, ctypes.byref(self._h)))
+
+    def _run(self, fused: bool, g1_lists: Sequence[Sequence[G1]], index) -> List[Gt]:
+        c = self.curve
+        n = len(g1_lists)
+        if n == 0:
+            return []
+        ppp = len(g1_lists[0])
+        if any(len(l) != ppp for l in g1_lists):
+            raise ValueError("G2Prepared: every product takes the same number of G1 points")
+        if index is None and ppp > self.m:
+            raise IndexError("G2Prepared: more pairs per product than prepared points")
+        if index is not None and any(i < 0 or i >= self.m for i in index):
+            raise IndexError("G2Prepared: point index out of range")
+        raw = _lib.g2_prepared_run(self._lib, self._h, c.gt_bytes, fused, b"".join(p.raw for l in g1_lists for p in l), index, ppp, n)
+        return [Gt(raw[i * c.gt_bytes : (i + 1) * c.gt_bytes], c) for i in range(n)]
+
+    def MillerLoopBatch(self, g1_lists: Sequence[Sequence[G1]], index=None) -> List[Gt]:
+        """out[k] = prod_j MillerLoop(g1_lists[k][j], Q[index[j]]) (without index: Q[j]); compare after FExp, as Curve.Pairing"""
+        return self._run(False, g1_lists, index)
+
+    def PairingBatch(self, g1_lists: Sequence[Sequence[G1]], index=None) -> List[Gt]:
+        """out[k] = FExp(prod_j MillerLoop(g1_lists[k][j], Q[index[j]])): Pairing2 + FExp over K proofs in one launch"""
+        return self._run(True, g1_lists, index)
+
+    def Count(self) -> int:
+        m = ctypes.c_size_t()
+        check(self._lib.mlhip_g2_prepared_count(self._h, ctypes.byref(m)))
+        return m.value
+
+    def Close(self) -> None:
+        if self._h:
+            self._lib.mlhip_g2_prepared_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
