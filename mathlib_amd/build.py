@@ -21,7 +21,11 @@ LIB = os.path.join(HERE, "libmlhip.so")
 ARCH = "gfx950"
 
 UNITS = [
-    "api.hip",
+    "rt.hip",
+    "api_msm.hip",
+    "api_bases.hip",
+    "api_pairing.hip",
+    "api_codec.hip",
     "tu_msm_bn254.hip",
     "tu_msm_bls381.hip",
     "tu_msm_bls377.hip",

@@ -1,0 +1,368 @@
+// api_bases.hip -- resident bases (mlhip_bases_* of include/mlhip.h): an uploaded point table with its plan, on one device
+// or cut into shards over several, and the batched MSMs over it.  No kernels here.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "mlhip_rt.h"
+#include "msm_body.h"
+
+using namespace mlhip;
+using namespace mlhip_rt;
+
+struct mlhip_bases {
+  mlhip_msm_plan* plan = nullptr;
+  void *d_pts = nullptr, *d_sc = nullptr;
+  size_t n = 0, ptsz = 0;
+  int curve = 0, group = 0, device = 0;
+  hipStream_t stream = nullptr;  // own non-blocking stream (see PoolEntry)
+  std::mutex mu;  // one MSM at a time per handle: the plan and the scalar buffer are shared state
+  mlhip_bases_batch_tables batch;  // mlhip_bases_msm_batch's per-base tables: built by the first batch call that wants them
+  // a table spread over several devices: contiguous shards, shard r = bases [lo[r], lo[r + 1]) on devs[r]
+  std::vector<mlhip_bases*> shards;
+  std::vector<size_t> lo;
+  std::vector<int> devs;
+};
+
+
+namespace {
+// Shifted-base tables for a table of n resident bases (msm_fold.h)?  They cost Wd rows per base (112 B a row for a 48-byte
+// field: 1.5 GB for 2^20 BLS12-381 G1 bases) and ~60 ms per 2^20 bases to build, and pay from the first few MSMs on.
+//   MLHIP_BASES_TABLES = 0: never; = 1: always (any size: what the tests use); unset: for tables of at least 2^10 bases
+//   created with window_c = 0 (an explicit window width asks for that Pippenger geometry) that fit a quarter of the free memory.
+//   MLHIP_FOLD_WINDOW = c: the digit width (default by size, see below); MLHIP_FOLD_TILE_LOG2 = t: tiles of 2^t bases (20).
+bool bases_want_tables(int group, size_t n, int window_c, int fr_bits, size_t ptsz, int* c_out, size_t* tile_out) {
+  const char* e = getenv("MLHIP_BASES_TABLES");
+  const bool forced = e && e[0] == '1';
+  if (e && e[0] == '0') return false;
+  // (G2 was measured from 2^20 bases down to 2^17 only: its small tables stay plain)
+  if (!forced && (n < ((size_t)1 << (group == MLHIP_GROUP_G1 ? 10 : 17)) || window_c != 0)) return false;
+  int lg_tile = 20;
+  if (const char* t = getenv("MLHIP_FOLD_TILE_LOG2")) {
+    const int v = atoi(t);
+    if (v >= 4 && v <= 24) lg_tile = v;
+  }
+  size_t tile = (size_t)1 << lg_tile;
+  if (n < tile) tile = n;
+  int c = 0;
+  if (const char* w = getenv("MLHIP_FOLD_WINDOW")) c = atoi(w);
+  // 20 bits (13 digits for a 253-255-bit group order) at every size from 2^16 on: narrower digits mean more of them and, in
+  // the even digit layout, most of the 2^(c-1) buckets half-used -- same-box runs (profiles/r04_fold.txt), BLS12-381 G1,
+  // resident scalars, c = 18 / 19 / 20 against the plain table: 2^17 1.11 / 0.83 / 0.80 (0.90) ms, 2^18 1.68 / 1.10 / 1.02
+  // (1.19), 2^19 - / 1.61 / 1.50 (1.75), 2^20 5.15 / 3.10 / 2.75 (3.16).  Below 2^16 bases an MSM is latency, not work -- the
+  // reduction's dependent chains grow with the bucket count, the accumulation's with the entries per bucket -- and what the
+  // tables save is mostly the host tail's 256 doublings (0.14 ms): 13 / 14 / 16 bits from 2^10 / 2^12 / 2^13 bases:
+  // 2^10 0.35 (plain 0.49) ms, 2^11 0.39 (0.52), 2^12 0.46 (0.56), 2^14 0.57 (0.67), 2^15 0.70 (0.72), 2^16 at 20 bits 0.75 (0.81)
+  if (c < 5 || c > 20) c = n < ((size_t)1 << 12) ? 13 : n < ((size_t)1 << 13) ? 14 : n < ((size_t)1 << 16) ? 16 : 20;
+  const size_t tiles = (n + tile - 1) / tile;
+  const size_t rows = tiles * (size_t)msm_num_windows(fr_bits, c) * tile;
+  if (!forced) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+    // carry-free rows: at most 5/4 of the boundary form's bytes a coordinate (10 x 4 B for a 32-byte field, 14 x 4 B for a 48-byte
+    // one); a G1 row may be a Niels triple (three coordinates instead of two); + one tile of boundary-form rows during the build
+    const size_t row_bytes = group == MLHIP_GROUP_G1 ? ptsz / 2 * 3 * 5 / 4 : ptsz * 5 / 4;
+    if (rows * row_bytes + (size_t)msm_num_windows(fr_bits, c) * tile * ptsz > free_b / 4) return false;
+  }
+  *c_out = c;
+  *tile_out = tile;
+  return true;
+}
+
+int bases_create_single(int curve, int group, const void* points, size_t n, int window_c, size_t ptsz,
+                               mlhip_bases** out, bool points_on_device = false) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  mlhip_bases* b = new mlhip_bases();
+  b->device = call_device();
+  b->curve = curve;
+  b->group = group;
+  b->n = n;
+  b->ptsz = ptsz;
+  const CurveOps* ops = curve_ops(curve);  // (every caller has checked the id)
+  {
+    int fold_c = 0;
+    size_t fold_tile = 0;
+    if (bases_want_tables(group, n, window_c, ops->fr_bits, ptsz, &fold_c, &fold_tile)) {
+      if (plan_create_ex(curve, group, n, fold_c, fold_tile, &b->plan) != 0) b->plan = nullptr;  // (the plain plan below)
+    }
+  }
+  rc = b->plan ? 0 : mlhip_msm_plan_create(curve, group, n, window_c, &b->plan);
+  if (!rc && (hipMalloc(&b->d_pts, n * b->ptsz) != hipSuccess || hipMalloc(&b->d_sc, n * 32) != hipSuccess))
+    rc = mlhip_rt::fail(MLHIP_ENOMEM, "hipMalloc of the bases failed");
+  if (!rc && hipMemcpy(b->d_pts, points, n * b->ptsz, points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
+    rc = mlhip_rt::fail(MLHIP_EHIP, "upload of the bases failed");
+  if (!rc && hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess)
+    rc = mlhip_rt::fail(MLHIP_EHIP, "hipStreamCreate failed");
+  if (rc) {
+    mlhip_bases_destroy(b);
+    return rc;
+  }
+  b->plan->points_static = true;  // the buffer is ours and never rewritten: convert it on the first MSM only
+  // BLS12-377 G1: a table whose every point is in the prime-order subgroup (what an SRS is; checked here, once, on the
+  // device: on the curve and phi(P) = [-x^2]P) has its buckets summed in twisted Edwards coordinates (ed28.h)
+  if (ops->g1_count_outside_subgroup && group == MLHIP_GROUP_G1) {
+    const char* e = getenv("MLHIP_EDWARDS");
+    if (!(e && e[0] == '0')) {
+      uint32_t* d_bad = nullptr;
+      uint32_t bad = 1;
+      if (hipMalloc(&d_bad, 4) == hipSuccess) {
+        if (hipMemsetAsync(d_bad, 0, 4, b->stream) == hipSuccess &&
+            ops->g1_count_outside_subgroup(b->d_pts, n, d_bad, b->stream) == 0 &&
+            hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, b->stream) == hipSuccess &&
+            hipStreamSynchronize(b->stream) == hipSuccess) {
+          b->plan->trust_subgroup = bad == 0;
+          if (bad == 0) plan_reserve_edwards(b->plan);
+        }
+        (void)hipFree(d_bad);
+      }
+    }
+  }
+  if (b->plan->fold) {
+    // the shifted-base table, in the form the plan will read (after the subgroup check: Niels triples or Weierstrass rows).
+    // If it cannot be built (memory), the handle falls back to a plain plan over the uploaded bases.
+    rc = ops->plan_fold_build(b->plan, b->d_pts, n, b->stream);
+    if (!rc && hipStreamSynchronize(b->stream) != hipSuccess) rc = MLHIP_EHIP;
+    if (rc) {
+      (void)hipGetLastError();
+      const bool trusted = b->plan->trust_subgroup;
+      mlhip_msm_plan_destroy(b->plan);
+      b->plan = nullptr;
+      rc = mlhip_msm_plan_create(curve, group, n, window_c, &b->plan);
+      if (rc) {
+        mlhip_bases_destroy(b);
+        return rc;
+      }
+      b->plan->points_static = true;
+      b->plan->trust_subgroup = trusted;
+      if (trusted) plan_reserve_edwards(b->plan);
+    }
+  }
+  *out = b;
+  return 0;
+}
+
+int bases_create_on(const std::vector<int>& devs, int curve, int group, const void* points, size_t n, int window_c,
+                           size_t ptsz, mlhip_bases** out) {
+  mlhip_bases* b = new mlhip_bases();
+  b->curve = curve;
+  b->group = group;
+  b->n = n;
+  b->ptsz = ptsz;
+  b->devs = devs;
+  b->shards.assign(devs.size(), nullptr);
+  b->lo.assign(devs.size() + 1, n);
+  int rc = run_on_devices(devs, n, [&](size_t r, size_t lo, size_t hi) {
+    b->lo[r] = lo;
+    return bases_create_single(curve, group, (const char*)points + lo * ptsz, hi - lo, window_c, ptsz, &b->shards[r]);
+  });
+  if (rc) {
+    std::string msg = mlhip_last_error();
+    mlhip_bases_destroy(b);
+    return mlhip_rt::fail(rc, msg);
+  }
+  *out = b;
+  return 0;
+}
+
+// the checks of a batch over a handle that need its size: every index below n (base_index given), or every segment at most n
+// pairs long (not given); *need = 1 + the largest base any pair reads (0: every segment is empty)
+int check_bases_batch_index(const mlhip_bases* b, const uint32_t* base_index, const uint64_t* offsets, size_t k,
+                                   size_t* need) {
+  size_t most = 0;
+  if (base_index) {
+    for (uint64_t i = 0; i < offsets[k]; i++) {
+      if (base_index[i] >= b->n) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: base index out of range");
+      most = std::max<size_t>(most, (size_t)base_index[i] + 1);
+    }
+  } else {
+    for (size_t s = 0; s < k; s++) {
+      const uint64_t m = offsets[s + 1] - offsets[s];
+      if (m > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: a segment is longer than the handle's bases");
+      most = std::max<size_t>(most, (size_t)m);
+    }
+  }
+  *need = most;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlhip_bases_destroy(mlhip_bases* b) {
+  if (!b) return 0;
+  for (mlhip_bases* sh : b->shards) mlhip_bases_destroy(sh);
+  if (b->shards.empty()) {
+    (void)hipSetDevice(b->device);
+    if (b->d_pts) (void)hipFree(b->d_pts);
+    if (b->d_sc) (void)hipFree(b->d_sc);
+    if (b->batch.buf) (void)hipFree(b->batch.buf);
+    if (b->plan) mlhip_msm_plan_destroy(b->plan);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+  }
+  delete b;
+  return 0;
+}
+
+int mlhip_bases_create(int curve, int group, const void* points, size_t n, int window_c, mlhip_bases** out) {
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  if (!points || n == 0) return mlhip_rt::fail(MLHIP_EINVAL, "bases need at least one point");
+  const std::vector<int> devs = spread_devices(n, false);
+  if (!devs.empty()) return bases_create_on(devs, curve, group, points, n, window_c, ptsz, out);
+  return bases_create_single(curve, group, points, n, window_c, ptsz, out);
+}
+
+int mlhip_bases_create_device(int curve, int group, const void* d_points, size_t n, int window_c, mlhip_bases** out) {
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  if (!d_points || n == 0) return mlhip_rt::fail(MLHIP_EINVAL, "bases need at least one point");
+  return bases_create_single(curve, group, d_points, n, window_c, ptsz, out, true);
+}
+
+int mlhip_bases_create_multi(int curve, int group, const int* devices, int n_devices, const void* points, size_t n,
+                             int window_c, mlhip_bases** out) {
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  if (!points || n == 0) return mlhip_rt::fail(MLHIP_EINVAL, "bases need at least one point");
+  if (n_devices < 1 || n_devices > 64 || !devices) return mlhip_rt::fail(MLHIP_EINVAL, "device list: 1 .. 64 entries");
+  std::vector<int> devs(devices, devices + n_devices);
+  for (int d : devs)
+    if (d < 0 || d >= MLHIP_MAX_DEVICES) return mlhip_rt::fail(MLHIP_EINVAL, "device list: index out of range (0 .. 63)");
+  if (devs.size() > n) devs.resize(n);
+  return bases_create_on(devs, curve, group, points, n, window_c, ptsz, out);
+}
+
+int mlhip_bases_checked_subgroup(mlhip_bases* b) {
+  if (!b) return 0;
+  if (!b->shards.empty()) {
+    for (mlhip_bases* s : b->shards)
+      if (!s || !mlhip_bases_checked_subgroup(s)) return 0;
+    return 1;
+  }
+  return b->plan && b->plan->trust_subgroup ? 1 : 0;
+}
+
+int mlhip_bases_msm(mlhip_bases* b, const void* scalars, int scalars_mont, size_t n, void* out_affine) {
+  if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
+  if (n == 0) {
+    memset(out_affine, 0, b->ptsz);
+    return 0;
+  }
+  if (!scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!b->shards.empty()) {
+    // every device adds up its part of the first n bases; the partial sums meet on the host (see msm_multi)
+    const size_t D = b->shards.size();
+    std::vector<char> partial(D * b->ptsz, 0);
+    int rc = run_on_devices(b->devs, D, [&](size_t r, size_t, size_t) {
+      const size_t lo = b->lo[r], hi = std::min(b->lo[r + 1], n);
+      if (lo >= hi) return 0;  // this shard's bases lie beyond the call's scalars: identity
+      return mlhip_bases_msm(b->shards[r], (const char*)scalars + lo * 32, scalars_mont, hi - lo, &partial[r * b->ptsz]);
+    });
+    if (rc) return rc;
+    return host_group_sum(b->curve, b->group, partial.data(), D, out_affine);
+  }
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  std::lock_guard<std::mutex> lk(b->mu);
+  {
+    // after the first MSM (which leaves the converted copy of the bases) large calls stream their scalars
+    const mlhip_msm_plan* p = b->plan;
+    const int segments = stream_segments(p->group, n, p);
+    if (segments > 1 && p->points_static && p->conv_src == b->d_pts && n <= p->conv_n) {
+      int rc = plan_stream(b->plan, b->d_pts, b->d_sc, nullptr, scalars, scalars_mont, n, segments, b->stream);
+      return rc ? rc : mlhip_msm_finish(b->plan, out_affine, nullptr);
+    }
+  }
+  if (hipMemcpy(b->d_sc, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess)
+    return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy of MSM scalars failed");
+  return mlhip_msm_run(b->plan, b->d_pts, b->d_sc, scalars_mont, n, b->stream, out_affine, nullptr);
+}
+
+int mlhip_bases_msm_device(mlhip_bases* b, const void* d_scalars, int scalars_mont, size_t n, void* stream, void* out_affine) {
+  if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_device: the handle is spread over several devices");
+  if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
+  if (n == 0) {
+    memset(out_affine, 0, b->ptsz);
+    return 0;
+  }
+  if (!d_scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  std::lock_guard<std::mutex> lk(b->mu);
+  return mlhip_msm_run(b->plan, b->d_pts, d_scalars, scalars_mont, n, stream, out_affine, nullptr);
+}
+
+int mlhip_bases_msm_batch_device(mlhip_bases* b, const void* d_scalars, int scalars_mont, const uint32_t* base_index,
+                                 const uint64_t* offsets, size_t k, void* stream, void* d_out_affine) {
+  if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
+  size_t need = 0;
+  rc = check_bases_batch_index(b, base_index, offsets, k, &need);
+  if (rc) return rc;
+  if (!d_out_affine || (offsets[k] && !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  std::lock_guard<std::mutex> lk(b->mu);
+  return curve_ops(b->curve)->bases_batch(b->group, &b->batch, b->d_pts, b->n, d_scalars, scalars_mont, base_index, offsets, k, need,
+                                          d_out_affine, (hipStream_t)stream);
+}
+
+int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont, const uint32_t* base_index, const uint64_t* offsets,
+                          size_t k, void* out_affine) {
+  if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
+  size_t need = 0;
+  rc = check_bases_batch_index(b, base_index, offsets, k, &need);
+  if (rc) return rc;
+  const size_t n = offsets[k];
+  if (!out_affine || (n && !scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  // the call's scratch comes from the process's device (HostCall); a handle made there before a later mlhip_init moved it
+  // elsewhere has to be driven through the device form
+  if (b->device != call_device()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle lives on another device");
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  HostCall hc;
+  hc.reserve(n * 32 + k * b->ptsz);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(k * b->ptsz);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_bases_msm_batch_device(b, ds, scalars_mont, base_index, offsets, k, hc.l.st, dout);
+  if (rc) return rc;
+  return hc.down(out_affine, dout, k * b->ptsz);
+}
+
+int mlhip_bases_batch_tabled(mlhip_bases* b, size_t* n_tabled) {
+  if (!b || !n_tabled) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!b->shards.empty()) {
+    *n_tabled = 0;
+    return 0;
+  }
+  std::lock_guard<std::mutex> lk(b->mu);
+  *n_tabled = b->batch.n_tabled;
+  return 0;
+}
+
+mlhip_msm_plan* mlhip_bases_plan(mlhip_bases* b) { return b && b->shards.empty() ? b->plan : nullptr; }
+
+}  // extern "C"

@@ -1,0 +1,706 @@
+// api_msm.hip -- the MSM entry points of include/mlhip.h: the pooled plans behind the host-buffer calls, the plan API, the
+// batched MSMs and scalar multiplications, and the host sums.  Argument checking and dispatch; no kernels here.
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "ec.h"
+#include "mlhip_rt.h"
+#include "msm_body.h"
+
+using namespace mlhip;
+using namespace mlhip_rt;
+
+namespace {
+int ilog2(size_t v) {
+  int l = 0;
+  while (v > 1) {
+    v >>= 1;
+    l++;
+  }
+  return l;
+}
+
+// ---- a small pool of plans + device input buffers for the host-buffer entry points ---------------------------
+// The reference's MultiScalarMul takes fresh host slices per call; creating and, above all, destroying a plan
+// (a dozen hipFree's, ~2.5 ms) and the input buffers per call cost as much as the kernels of a 2^20-point MSM.
+// Entries are reused across calls and threads when curve / group / window / device match and the size fits
+// (capacity between n and 4 n).  At most POOL_MAX entries and POOL_MAX_BYTES of device memory stay allocated (an entry
+// is ~0.6 GB at n = 2^20, ~10 GB at 2^24; many goroutines with small MSMs each find their own entry);
+// MLHIP_NO_PLAN_CACHE=1 disables the pool, mlhip_release_cache() empties it.
+struct PoolEntry {
+  mlhip_msm_plan* plan = nullptr;
+  void *d_pts = nullptr, *d_sc = nullptr;
+  hipStream_t stream = nullptr;  // the entry's own non-blocking stream: concurrent callers do not meet on the null stream
+  int curve = 0, group = 0, c = 0, device = 0;
+  size_t cap = 0;
+  bool busy = false, pooled = false;
+  unsigned long stamp = 0;
+  size_t bytes = 0;  // device memory the entry took (free memory before - after its creation)
+};
+constexpr size_t POOL_MAX = 16;  // per device
+constexpr size_t POOL_MAX_BYTES = (size_t)32 << 30;  // per device
+std::mutex g_pool_mu;
+std::vector<PoolEntry*> g_pool;
+unsigned long g_pool_clock = 0;
+
+void pool_free_entry(PoolEntry* e) {
+  (void)hipSetDevice(e->device);
+  if (e->d_pts) (void)hipFree(e->d_pts);
+  if (e->d_sc) (void)hipFree(e->d_sc);
+  if (e->plan) mlhip_msm_plan_destroy(e->plan);
+  if (e->stream) (void)hipStreamDestroy(e->stream);
+  delete e;
+}
+
+PoolEntry* pool_acquire(int curve, int group, int c, size_t n, size_t ptsz, int& rc) {
+  const char* off = getenv("MLHIP_NO_PLAN_CACHE");
+  const bool use_pool = !(off && off[0] == '1');
+  std::vector<PoolEntry*> victims;
+  if (use_pool) {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (PoolEntry* e : g_pool)
+      if (!e->busy && e->curve == curve && e->group == group && e->c == c && e->device == call_device() && e->cap >= n &&
+          e->cap <= 4 * n) {
+        e->busy = true;
+        e->stamp = ++g_pool_clock;
+        return e;
+      }
+    // evict this device's least recently used idle entries while its share of the pool is full or over budget
+    for (;;) {
+      size_t total = 0, count = 0;
+      for (PoolEntry* e : g_pool)
+        if (e->device == call_device()) {
+          total += e->bytes;
+          count++;
+        }
+      if (count < POOL_MAX && total <= POOL_MAX_BYTES) break;
+      size_t vi = g_pool.size();
+      for (size_t i = 0; i < g_pool.size(); i++)
+        if (g_pool[i]->device == call_device() && !g_pool[i]->busy && (vi == g_pool.size() || g_pool[i]->stamp < g_pool[vi]->stamp)) vi = i;
+      if (vi == g_pool.size()) break;  // everything is in use
+      victims.push_back(g_pool[vi]);
+      g_pool.erase(g_pool.begin() + vi);
+    }
+  }
+  for (PoolEntry* v : victims) pool_free_entry(v);
+  size_t free_before = 0, free_after = 0, total_mem = 0;
+  (void)hipMemGetInfo(&free_before, &total_mem);
+  PoolEntry* e = new PoolEntry();
+  e->curve = curve;
+  e->group = group;
+  e->c = c;
+  e->device = call_device();
+  e->cap = n;
+  e->busy = true;
+  for (int attempt = 0;; attempt++) {
+    rc = mlhip_msm_plan_create(curve, group, n, c, &e->plan);
+    if (!rc && (hipMalloc(&e->d_pts, n * ptsz) != hipSuccess || hipMalloc(&e->d_sc, n * 32) != hipSuccess))
+      rc = mlhip_rt::fail(MLHIP_ENOMEM, "hipMalloc of MSM inputs failed");
+    if (!rc || attempt == 1 || !use_pool) break;
+    // out of device memory with idle entries pooled: give them back and try once more
+    if (e->d_pts) (void)hipFree(e->d_pts);
+    if (e->d_sc) (void)hipFree(e->d_sc);
+    if (e->plan) mlhip_msm_plan_destroy(e->plan);
+    e->d_pts = e->d_sc = nullptr;
+    e->plan = nullptr;
+    (void)hipGetLastError();
+    mlhip_release_cache();
+  }
+  if (!rc && hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess)
+    rc = mlhip_rt::fail(MLHIP_EHIP, "hipStreamCreate failed");
+  if (rc) {
+    pool_free_entry(e);
+    return nullptr;
+  }
+  (void)hipMemGetInfo(&free_after, &total_mem);
+  e->bytes = free_before > free_after ? free_before - free_after : 0;
+  if (use_pool) {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    size_t count = 0;
+    for (PoolEntry* o : g_pool) count += o->device == e->device;
+    if (count < POOL_MAX) {
+      e->pooled = true;
+      e->stamp = ++g_pool_clock;
+      g_pool.push_back(e);
+    }
+  }
+  return e;
+}
+
+void pool_release(PoolEntry* e, bool failed) {
+  if (e->pooled && failed) {  // do not keep an entry whose last run ended in an error
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (size_t i = 0; i < g_pool.size(); i++)
+      if (g_pool[i] == e) {
+        g_pool.erase(g_pool.begin() + i);
+        break;
+      }
+    e->pooled = false;
+  }
+  if (!e->pooled) {
+    pool_free_entry(e);
+    return;
+  }
+  std::lock_guard<std::mutex> lk(g_pool_mu);
+  e->busy = false;
+}
+
+// can this plan run the segment train (plan_stream / plan_stream_shared)?  The condition stream_begin checks.
+bool plan_can_stream(const mlhip_msm_plan* p) {
+  return p->aux && p->d_points28;
+}
+
+// the shared-scalar train on two plans; h_* = nullptr: everything is already at the d_* pointers
+int plan_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d1, void* d2, void* dsc, const void* h1, const void* h2,
+                const void* hsc, int mont, size_t n, hipStream_t st) {
+  int rc = curve_ops(g1->curve)->plan_shared(g1, g2, d1, d2, dsc, h1, h2, hsc, mont, n, st);
+  if (rc) {  // as mlhip_msm_launch: drain what was queued (copies from the caller's buffers too) and leave both plans reusable
+    (void)hipStreamSynchronize(st);
+    if (g1->aux) (void)hipStreamSynchronize(g1->aux);
+    if (g1->sort_stream) (void)hipStreamSynchronize(g1->sort_stream);
+    if (g2->aux) (void)hipStreamSynchronize(g2->aux);
+    (void)hipGetLastError();
+    g1->pending = g2->pending = false;
+  }
+  return rc;
+}
+
+}  // namespace
+
+namespace mlhip_rt {
+// measured optimum on one MI355X (tools/sweep_window.py, profiles/r02_sweep_window.txt).  With the balanced window
+// layout (msm_body.h: msm_win_layout) every width splits the scalar evenly, so the mid sizes no longer have to jump
+// from 8 to 16: 13-14 bits win from 2^11 to 2^15 points (2^14: 0.81 ms instead of 1.11), 16 from 2^16 on.  For large n on
+// the curves whose 254 / 255 scalar bits fit 15 windows of 17 bits (BLS12-377, BN254) one window less is one addition
+// per scalar less (BLS12-377 2^22: 12.5 ms instead of 13.5); BLS12-381's 256 bits need 16 windows either way.
+// Round 4 (profiles/r04_sweep_window.txt, the same sweep on this round's kernels): 10 bits from 2^10 to 2^11 points
+// (0.47 / 0.49 ms against 0.50 at c = 8 / 0.53 at c = 13), and for BN254 (254-bit order, 10-limb field: its reduction weighs
+// more against its additions) 15 bits from 2^16 to 2^17 points (0.505 / 0.587 ms against 0.554 / 0.617 at c = 16) -- not for
+// BLS12-377, whose 253 bits also fit 17 windows of 15: 0.93 / 1.14 ms against 0.88 / 1.00 at c = 16.
+int pick_window(size_t n, int fr_bits) {
+  if (n <= 128) return 4;
+  if (n <= 512) return 8;
+  if (n <= 2048) return 10;
+  if (n <= 8192) return 13;
+  if (n <= 32768) return 14;
+  if (n < ((size_t)1 << 18) && fr_bits == 254) return 15;
+  if (n >= ((size_t)1 << 22) && msm_num_windows(fr_bits, 17) < msm_num_windows(fr_bits, 16)) return 17;
+  return 16;
+}
+
+// fold_tile != 0: a plan over shifted-base tables (msm_fold.h, mlhip_internal.h) -- window_c is the digit width, the
+// 2^(c-1) buckets all digits share are cut into groups of at most 2^15 for the reduction; the table itself is built by
+// mlhip_tu_plan_fold_build_* (mlhip_bases_create).
+int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out) {
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null plan pointer");
+  *out = nullptr;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!ops->point_size(group)) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  if (max_n == 0 || max_n > ((size_t)1 << 27)) return mlhip_rt::fail(MLHIP_EINVAL, "max_n out of range (1 .. 2^27)");
+  if (window_c == 0) window_c = pick_window(max_n, ops->fr_bits);
+  if (window_c < 4 || window_c > 20) return mlhip_rt::fail(MLHIP_EINVAL, "window_c out of range (4 .. 20)");
+  const int digits = msm_num_windows(ops->fr_bits, window_c);
+  // sorted-entry offsets, cursors and scans are 32-bit: W * max_n entries must be addressable
+  if (!fold_tile && (size_t)digits * max_n > 0xFFFFFFFFull)
+    return mlhip_rt::fail(MLHIP_EINVAL, "window_c too small for max_n: W * max_n entries exceed 2^32 - 1");
+  if (fold_tile) {
+    // an entry = table row index (below Wd fold_tile) | sign: 31 bits + 1; the tiles of one MSM are its segments
+    if ((size_t)digits * fold_tile > ((size_t)1 << 30)) return mlhip_rt::fail(MLHIP_EINVAL, "shifted-base tables: tile too long");
+    // the sort's per-block bin counts are 16-bit and a block of 1024 scalars may put all its 1024 Wd entries into one bin
+    if ((size_t)digits * 1024 >= 65536) return mlhip_rt::fail(MLHIP_EINVAL, "shifted-base tables: digit width below 5 bits");
+    if ((max_n + fold_tile - 1) / fold_tile > MLHIP_MAX_SEGMENTS) return mlhip_rt::fail(MLHIP_EINVAL, "shifted-base tables: too many tiles");
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  mlhip_msm_plan* p = new mlhip_msm_plan();
+  p->curve = curve;
+  p->group = group;
+  p->device = call_device();
+  p->c = window_c;
+  p->Wd = digits;
+  p->max_n = max_n;
+  if (fold_tile) {
+    p->fold = 1;
+    p->fold_tile = fold_tile;
+    const uint32_t nbuckets = 1u << (window_c - 1);
+    p->M = nbuckets < 32768u ? nbuckets : 32768u;
+    p->W = (int)(nbuckets / p->M);
+  } else {
+    p->W = digits;
+    p->M = 1u << (window_c - 1);
+  }
+  // buckets per level-1 reduction chunk: 16 for G1 (the quad-lane kernels are bound by work, and a longer chunk
+  // halves the second level), 8 for G2 on the boundary-form curves and for tiny windows
+  // (and for small bucket sets, where the chunk pass is a dependent chain rather than work: 2^12 points, c = 13:
+  // reduction 0.25 -> 0.22 ms)
+  // G2 (carry-free lane-pair reduction): 16 as well -- BLS12-381: reduction 1.43 -> 1.31 ms at c = 16
+  const bool chunks16 = true;
+  p->lgL = (chunks16 && p->M >= 256 && (size_t)p->W * p->M >= ((size_t)1 << 17)) ? 4 : 3;
+  if (const char* e = getenv("MLHIP_CHUNK_LOG2")) {
+    int v = atoi(e);
+    if (v >= 1 && v <= 6 && (1u << v) <= p->M) p->lgL = v;
+  }
+  p->L = 1 << p->lgL;
+  p->T = p->M / p->L;
+  p->nb = ilog2(p->T);
+  p->nsel = 4 + p->nb;  // two half-sums of W0, two of A, nb bit-masked sums
+  rc = ops->plan_alloc(p);
+  if (!rc && p->fold && (p->sort_low <= 0 || !p->reduce28))
+    rc = mlhip_rt::fail(MLHIP_EINVAL, "shifted-base tables need the two-level sort and the carry-free kernels");
+  if (rc) {
+    mlhip_msm_plan_destroy(p);
+    return rc;
+  }
+  *out = p;
+  return 0;
+}
+
+// Room for the twisted Edwards form of the points (168-byte Niels triples instead of 112-byte rows) in a plan that may take
+// that path; called when the SRS promise is made, with nothing in flight on the plan.  A failed allocation is not an error:
+// the plan keeps (or gets back) the smaller buffer and stays on the Weierstrass kernels (plan_use_edwards checks the size).
+void plan_reserve_edwards(mlhip_msm_plan* p) {
+  if (!p->points28_elem_ed || p->points28_elem >= p->points28_elem_ed || !p->d_points28 || p->fold) return;
+  const char* e = getenv("MLHIP_EDWARDS");
+  if (e && e[0] == '0') return;
+  (void)hipSetDevice(p->device);
+  if (p->aux) (void)hipStreamSynchronize(p->aux);
+  void* bigger = nullptr;
+  if (hipMalloc(&bigger, p->max_n * p->points28_elem_ed) != hipSuccess) {
+    (void)hipGetLastError();
+    return;
+  }
+  (void)hipFree(p->d_points28);
+  p->d_points28 = bigger;
+  p->points28_elem = p->points28_elem_ed;
+  p->conv_src = nullptr;
+}
+
+// Number of segments a host-buffer MSM is streamed in (1 = one upload, one pass).  Measured on MI355X / PCIe gen5
+// (tools/perf_hostapi.py): from 2^19 points the transfer is worth hiding; MLHIP_STREAM_SEGMENTS overrides (0/1 = off).
+int stream_segments(int group, size_t n, const mlhip_msm_plan* plan) {
+  // G1 and G2 stream through the carry-free kernels and their bucket state (always there unless MLHIP_ACC32=1, which runs
+  // one pass) -- the condition stream_begin checks
+  (void)group;
+  if (!plan->aux || !plan->d_points28) return 1;
+  if (getenv("MLHIP_STREAM_SCHEDULE")) return n >= 2 ? 2 : 1;  // explicit segment weights (msm_plan.h: stream_schedule), any n
+  if (const char* e = getenv("MLHIP_STREAM_SEGMENTS")) {
+    int v = atoi(e);
+    if (v < 2) return 1;
+    if (v > MLHIP_MAX_SEGMENTS) v = MLHIP_MAX_SEGMENTS;
+    return n >= (size_t)v ? v : 1;
+  }
+  // segments of 2^18 pairs: at 2^20 the call drops from 5.9 to 4.5 ms, at 2^22 from 21.9 to 12.8 ms (the device-only time)
+  // G2 (BLS12-381): segments of 2^17 pairs, 14.9 -> 11.4 ms at 2^20.  For G1 from 2^20 pairs on the count returned here only
+  // says "stream": plan_stream replaces the equal segments by a growing schedule (stream_schedule, round 4)
+  const size_t k = n >> (group == MLHIP_GROUP_G1 ? 18 : 17);
+  return k < 2 ? 1 : (k > MLHIP_MAX_SEGMENTS ? MLHIP_MAX_SEGMENTS : (int)k);
+}
+
+int plan_stream(mlhip_msm_plan* p, void* d_pts, void* d_sc, const void* points, const void* scalars, int mont, size_t n,
+                int segments, hipStream_t st) {
+  int rc = curve_ops(p->curve)->plan_stream(p, d_pts, d_sc, points, scalars, mont, n, segments, st);
+  if (rc) {
+    // a failure part-way: copies from the caller's buffers may still be queued -- let them drain before the caller gets
+    // its memory back, and leave the plan reusable
+    (void)hipDeviceSynchronize();
+    p->pending = false;
+  }
+  return rc;
+}
+
+int host_group_sum(int curve, int group, const void* pts, size_t n, void* out) {
+  return group == MLHIP_GROUP_G1 ? mlhip_g1_sum(curve, pts, n, out) : mlhip_g2_sum(curve, pts, n, out);
+}
+
+// offsets of a batch: k + 1 nondecreasing host entries from 0 (k = 0: nothing to check)
+int check_batch_offsets(const uint64_t* offsets, size_t k) {
+  if (k == 0) return 0;
+  if (!offsets) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets is null");
+  if (offsets[0] != 0) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets[0] must be 0");
+  for (size_t i = 0; i < k; i++)
+    if (offsets[i + 1] < offsets[i]) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: offsets decrease");
+  return 0;
+}
+
+
+void release_plan_pool() {
+  std::vector<PoolEntry*> idle;
+  {
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    for (size_t i = 0; i < g_pool.size();)
+      if (!g_pool[i]->busy) {
+        idle.push_back(g_pool[i]);
+        g_pool.erase(g_pool.begin() + i);
+      } else {
+        i++;
+      }
+  }
+  for (PoolEntry* e : idle) pool_free_entry(e);
+}
+}  // namespace mlhip_rt
+
+namespace {
+int msm_host_buffers(int curve, int group, const void* points, const void* scalars, int mont, size_t n, int window_c,
+                     void* out);
+
+// One MSM over several devices (reference semantics math.go:960-969 /
+// driver/gurvy/bls12381/bls12-381.go:766-783): contiguous shards of the pairs, one host thread per device running the
+// whole single-device pipeline on its shard (its own pooled plan, its own PCIe link), the per-device partial sums --
+// already in host memory, where each shard's Horner tail leaves them -- added on the host.  The caller wants the sum in
+// host memory, so there is nothing for a device-side collective to do here; the RCCL all-gather lives in the
+// process-per-GPU form (mathlib_amd/dist.py), where every rank wants the total.
+int msm_multi(const std::vector<int>& devs, int curve, int group, const void* points, const void* scalars, int mont,
+              size_t n, int window_c, void* out, size_t ptsz) {
+  std::vector<char> partial(devs.size() * ptsz);
+  int rc = run_on_devices(devs, n, [&](size_t r, size_t lo, size_t hi) {
+    return msm_host_buffers(curve, group, (const char*)points + lo * ptsz, (const char*)scalars + lo * 32, mont, hi - lo,
+                            window_c, &partial[r * ptsz]);
+  });
+  if (rc) return rc;
+  return host_group_sum(curve, group, partial.data(), devs.size(), out);
+}
+
+int msm_host_buffers(int curve, int group, const void* points, const void* scalars, int mont, size_t n, int window_c,
+                     void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  const size_t ptsz = ops->point_size(group);
+  if (n == 0) {
+    // the point at infinity, as gnark's MultiExp gives for empty slices (and, via the dropped
+    // error, for mismatched lengths: bls12-381.go:777)
+    memset(out, 0, ptsz);
+    return 0;
+  }
+  if (!points || !scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  {
+    const std::vector<int> devs = spread_devices(n, false);
+    if (!devs.empty()) return msm_multi(devs, curve, group, points, scalars, mont, n, window_c, out, ptsz);
+  }
+  if (window_c == 0) window_c = pick_window(n, ops->fr_bits);
+  int rc = ensure_device();
+  if (rc) return rc;
+  PoolEntry* e = pool_acquire(curve, group, window_c, n, ptsz, rc);
+  if (!e) return rc;
+  const int segments = stream_segments(group, n, e->plan);
+  do {
+    if (segments > 1) {
+      // large G1 MSMs: upload, sort and accumulate segment by segment, so the PCIe transfer hides under the kernels
+      rc = plan_stream(e->plan, e->d_pts, e->d_sc, points, scalars, mont, n, segments, e->stream);
+      if (!rc) rc = mlhip_msm_finish(e->plan, out, nullptr);
+      break;
+    }
+    // scalars first (the sort needs only them); the points follow on the plan's auxiliary stream while the sort runs
+    if (hipMemcpy(e->d_sc, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess) {
+      rc = mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy of MSM scalars failed");
+      break;
+    }
+    e->plan->upload_src = points;
+    e->plan->upload_bytes = n * ptsz;
+    rc = mlhip_msm_run(e->plan, e->d_pts, e->d_sc, mont, n, e->stream, out, nullptr);
+    e->plan->upload_src = nullptr;
+  } while (0);
+  pool_release(e, rc != 0);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlhip_msm_multi(int curve, int group, const int* devices, int n_devices, const void* points, const void* scalars,
+                    int scalars_mont, size_t n, int window_c, void* out_affine) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  if (!out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  if (n_devices < 1 || n_devices > 64 || !devices) return mlhip_rt::fail(MLHIP_EINVAL, "device list: 1 .. 64 entries");
+  if (n == 0) {
+    memset(out_affine, 0, ptsz);
+    return 0;
+  }
+  if (!points || !scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  std::vector<int> devs(devices, devices + n_devices);
+  for (int d : devs)
+    if (d < 0 || d >= MLHIP_MAX_DEVICES) return mlhip_rt::fail(MLHIP_EINVAL, "device list: index out of range (0 .. 63)");
+  if (devs.size() > n) devs.resize(n);
+  return msm_multi(devs, curve, group, points, scalars, scalars_mont, n, window_c, out_affine, ptsz);
+}
+
+int mlhip_msm_plan_create(int curve, int group, size_t max_n, int window_c, mlhip_msm_plan** out) {
+  return plan_create_ex(curve, group, max_n, window_c, 0, out);
+}
+
+int mlhip_msm_plan_destroy(mlhip_msm_plan* p) {
+  if (!p) return 0;
+  (void)hipSetDevice(p->device);
+  void* ptrs[] = {p->d_digits, p->d_sorted, p->d_zero, p->d_offsets, p->d_biglist, p->d_buckets, p->d_A, p->d_W0, p->d_out,
+                  p->d_order, p->d_hist, p->d_tilesums, p->d_coarse_off, p->d_points28, p->d_blockhist, p->d_state28, p->d_bigprefix, p->d_bigpart, p->d_binprefix};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  if (p->h_out) (void)hipHostFree(p->h_out);
+  for (int i = 0; i < 5; i++)
+    if (p->ev[i]) (void)hipEventDestroy(p->ev[i]);
+  if (p->done) (void)hipEventDestroy(p->done);
+  if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
+  if (p->ev_join) (void)hipEventDestroy(p->ev_join);
+  for (hipEvent_t e : p->ev_seg)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : p->ev_seg_sc)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& tile : p->ev_tile)
+    for (hipEvent_t e : tile)
+      if (e) (void)hipEventDestroy(e);
+  if (p->aux) (void)hipStreamDestroy(p->aux);
+  for (int i = 0; i < 2; i++) {
+    if (p->sort_helper[i]) (void)mlhip_msm_plan_destroy(p->sort_helper[i]);
+    if (p->ev_sorted[i]) (void)hipEventDestroy(p->ev_sorted[i]);
+    if (p->ev_lists_free[i]) (void)hipEventDestroy(p->ev_lists_free[i]);
+  }
+  if (p->sort_stream) (void)hipStreamDestroy(p->sort_stream);
+  delete p;
+  return 0;
+}
+
+int mlhip_msm_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, int scalars_mont, size_t n,
+                     void* stream) {
+  if (!p) return mlhip_rt::fail(MLHIP_EINVAL, "null plan");
+  if (p->pending) return mlhip_rt::fail(MLHIP_EINVAL, "plan already has a pending launch; call mlhip_msm_finish first");
+  if (n > p->max_n) return mlhip_rt::fail(MLHIP_EINVAL, "n exceeds the plan's max_n");
+  if (n && (!d_points || !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null device pointer");
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t st = (hipStream_t)stream;
+  int rc = curve_ops(p->curve)->plan_launch(p, d_points, d_scalars, scalars_mont, n, st);
+  if (rc) {
+    // a failure part-way through the launch train: `done` may never have been recorded, so a later finish must not
+    // read h_out.  Drain what was queued (the error text survives: the drain calls do not go through fail()) and leave
+    // the plan reusable, as plan_stream does.
+    (void)hipStreamSynchronize(st);
+    if (p->aux) (void)hipStreamSynchronize(p->aux);
+    if (p->sort_stream) (void)hipStreamSynchronize(p->sort_stream);
+    (void)hipGetLastError();
+    p->pending = false;
+    p->upload_src = nullptr;
+  }
+  return rc;
+}
+
+int mlhip_msm_launch_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, const void* d_points_g1, const void* d_points_g2,
+                            const void* d_scalars, int scalars_mont, size_t n, void* stream) {
+  if (!g1 || !g2) return mlhip_rt::fail(MLHIP_EINVAL, "null plan");
+  if (g1->group != MLHIP_GROUP_G1 || g2->group != MLHIP_GROUP_G2 || g1->curve != g2->curve || g1->device != g2->device)
+    return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM needs a G1 plan and a G2 plan of one curve on one device");
+  if (g1->pending || g2->pending)
+    return mlhip_rt::fail(MLHIP_EINVAL, "plan already has a pending launch; call mlhip_msm_finish first");
+  if (n > g1->max_n || n > g2->max_n) return mlhip_rt::fail(MLHIP_EINVAL, "n exceeds a plan's max_n");
+  if (n && (!d_points_g1 || !d_points_g2 || !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null device pointer");
+  const bool share = n != 0 && g1->c == g2->c && plan_can_stream(g1) && plan_can_stream(g2);
+  if (!share) {  // nothing to share (or a plan on a second-implementation path): two ordinary launches, one after the other
+    int rc = mlhip_msm_launch(g1, d_points_g1, d_scalars, scalars_mont, n, stream);
+    if (rc) return rc;
+    rc = mlhip_msm_launch(g2, d_points_g2, d_scalars, scalars_mont, n, stream);
+    if (rc) {  // leave neither plan pending: the caller gets one error for the pair
+      (void)hipStreamSynchronize((hipStream_t)stream);
+      g1->pending = false;
+    }
+    return rc;
+  }
+  HIPCHK(hipSetDevice(g1->device));
+  hipStream_t st = (hipStream_t)stream;
+  void *p1 = const_cast<void*>(d_points_g1), *p2 = const_cast<void*>(d_points_g2), *sc = const_cast<void*>(d_scalars);
+  return plan_shared(g1, g2, p1, p2, sc, nullptr, nullptr, nullptr, scalars_mont, n, st);
+}
+
+int mlhip_msm_g1g2(int curve, const void* points_g1, const void* points_g2, const void* scalars, int scalars_mont, size_t n,
+                   int window_c, void* out_g1, void* out_g2) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!out_g1 || !out_g2) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  if (n == 0) {  // the points at infinity, as for mlhip_msm_g1 / _g2
+    memset(out_g1, 0, ops->g1);
+    memset(out_g2, 0, ops->g2);
+    return 0;
+  }
+  if (!points_g1 || !points_g2 || !scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!spread_devices(n, false).empty()) {
+    // spread over the device list: every device sorts its own shard anyway -- two sharded MSMs; the caller's window_c
+    // travels as given (0 = each shard picks the width of its own size)
+    int rc = msm_host_buffers(curve, MLHIP_GROUP_G1, points_g1, scalars, scalars_mont, n, window_c, out_g1);
+    if (rc) return rc;
+    return msm_host_buffers(curve, MLHIP_GROUP_G2, points_g2, scalars, scalars_mont, n, window_c, out_g2);
+  }
+  if (window_c == 0) window_c = pick_window(n, ops->fr_bits);
+  int rc = ensure_device();
+  if (rc) return rc;
+  PoolEntry* e1 = pool_acquire(curve, MLHIP_GROUP_G1, window_c, n, ops->g1, rc);
+  if (!e1) return rc;
+  PoolEntry* e2 = pool_acquire(curve, MLHIP_GROUP_G2, window_c, n, ops->g2, rc);
+  if (!e2) {
+    pool_release(e1, false);
+    return rc;
+  }
+  if (plan_can_stream(e1->plan) && plan_can_stream(e2->plan)) {
+    rc = plan_shared(e1->plan, e2->plan, e1->d_pts, e2->d_pts, e1->d_sc, points_g1, points_g2, scalars, scalars_mont, n,
+                        e1->stream);
+    if (!rc) rc = mlhip_msm_finish(e1->plan, out_g1, nullptr);
+    if (!rc) rc = mlhip_msm_finish(e2->plan, out_g2, nullptr);
+    if (rc) {  // whatever is still queued reads the caller's buffers: let it drain, leave the plans reusable
+      (void)hipDeviceSynchronize();
+      e1->plan->pending = e2->plan->pending = false;
+    }
+    pool_release(e2, rc != 0);
+    pool_release(e1, rc != 0);
+    return rc;
+  }
+  // a second-implementation path (MLHIP_ACC32=1 ...): nothing to share
+  pool_release(e2, false);
+  pool_release(e1, false);
+  rc = msm_host_buffers(curve, MLHIP_GROUP_G1, points_g1, scalars, scalars_mont, n, window_c, out_g1);
+  if (rc) return rc;
+  return msm_host_buffers(curve, MLHIP_GROUP_G2, points_g2, scalars, scalars_mont, n, window_c, out_g2);
+}
+
+int mlhip_msm_finish(mlhip_msm_plan* p, void* out_affine, void* out_xyzz) {
+  if (!p || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  HIPCHK(hipSetDevice(p->device));
+  return curve_ops(p->curve)->plan_finish(p, out_affine, out_xyzz);
+}
+
+int mlhip_msm_run(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, int scalars_mont, size_t n,
+                  void* stream, void* out_affine, void* out_xyzz) {
+  if (!p || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = mlhip_msm_launch(p, d_points, d_scalars, scalars_mont, n, stream);
+  if (rc) return rc;
+  return mlhip_msm_finish(p, out_affine, out_xyzz);
+}
+
+int mlhip_msm_plan_set_profiling(mlhip_msm_plan* p, int on) {
+  if (!p) return mlhip_rt::fail(MLHIP_EINVAL, "null plan");
+  p->profiling = on != 0;
+  return 0;
+}
+
+int mlhip_msm_plan_assume_srs(mlhip_msm_plan* p, int on) {
+  if (!p) return mlhip_rt::fail(MLHIP_EINVAL, "null plan");
+  if (p->pending) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_plan_assume_srs with a launch pending");
+  if (p->fold) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_plan_assume_srs: this plan reads the tables of a mlhip_bases handle");
+  p->conv_src = nullptr;  // whatever carry-free copy the plan holds was made under the other promise
+  p->points_static = p->trust_subgroup = on != 0;
+  if (on) plan_reserve_edwards(p);
+  return 0;
+}
+
+int mlhip_msm_plan_timings(mlhip_msm_plan* p, float* ms, int cap) {
+  if (!p || !ms) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int k = cap < 11 ? cap : 11;
+  for (int i = 0; i < k && i < 6; i++) ms[i] = p->ms[i];
+  if (k >= 7) ms[6] = p->tiles_timed > 0 ? (float)p->tiles_timed : 1.0f;
+  if (k >= 8) ms[7] = (float)p->c;
+  if (k >= 9) ms[8] = (float)p->Wd;
+  if (k >= 10) ms[9] = p->last_ed ? 1.0f : 0.0f;
+  if (k >= 11) ms[10] = p->fold ? 1.0f : 0.0f;
+  return k;
+}
+
+int mlhip_msm_g1(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
+                 void* out_affine) {
+  return msm_host_buffers(curve, MLHIP_GROUP_G1, points, scalars, scalars_mont, n, window_c, out_affine);
+}
+
+int mlhip_msm_g2(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
+                 void* out_affine) {
+  return msm_host_buffers(curve, MLHIP_GROUP_G2, points, scalars, scalars_mont, n, window_c, out_affine);
+}
+
+int mlhip_scalar_mul_device(int curve, int group, const void* d_points, size_t point_stride, const void* d_scalars,
+                            int mont, size_t n, void* d_out, void* stream) {
+  if (group != MLHIP_GROUP_G1 && group != MLHIP_GROUP_G2) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  if (point_stride > 1) return mlhip_rt::fail(MLHIP_EINVAL, "point_stride must be 0 or 1");
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->scalar_mul(group, d_points, point_stride, d_scalars, mont, n, d_out, (hipStream_t)stream);
+}
+
+int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stride, const void* scalars, int mont,
+                     size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  if (n == 0) return 0;
+  if (!points || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  const size_t npts = point_stride ? n : 1;
+  HostCall hc;
+  hc.reserve(npts * ptsz + n * 32 + n * ptsz);
+  void* dp = hc.up(points, npts * ptsz);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(n * ptsz);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_scalar_mul_device(curve, group, dp, point_stride, ds, mont, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ptsz);
+}
+
+int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
+                           const uint64_t* offsets, size_t k, void* d_out_affine, void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!ops->point_size(group)) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  if (!d_out_affine || (offsets[k] && (!d_points || !d_scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  rc = ensure_device();
+  if (rc) return rc;
+  return ops->msm_batch(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, (hipStream_t)stream);
+}
+
+int mlhip_msm_batch(int curve, int group, const void* points, const void* scalars, int scalars_mont, const uint64_t* offsets,
+                    size_t k, void* out_affine) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
+  int rc = check_batch_offsets(offsets, k);
+  if (rc) return rc;
+  if (k == 0) return 0;
+  const size_t n = offsets[k];
+  if (!out_affine || (n && (!points || !scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(n * ptsz + n * 32 + k * ptsz);
+  void* dp = hc.up(points, n * ptsz);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(k * ptsz);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_msm_batch_device(curve, group, dp, ds, scalars_mont, offsets, k, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out_affine, dout, k * ptsz);
+}
+
+int mlhip_g1_sum(int curve, const void* pts, size_t n, void* out) {
+  if (!out || (n && !pts)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->g1_sum(pts, n, out);
+}
+
+int mlhip_g2_sum(int curve, const void* pts, size_t n, void* out) {
+  if (!out || (n && !pts)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->g2_sum(pts, n, out);
+}
+
+}  // extern "C"

@@ -1,0 +1,324 @@
+// api_pairing.hip -- the pairing, Gt and prepared-G2 entry points of include/mlhip.h (and the field-multiplication probe):
+// argument checking, host-buffer staging and dispatch.  No kernels here.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mlhip_rt.h"
+
+using namespace mlhip_rt;
+
+namespace {
+// host-buffer wrapper around the pairing kernels: upload, run, download
+int pairing_host(int curve, int what, const void* g1, const void* g2, size_t ppp, size_t n, const void* in, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!out || (what == 1 ? !in : (!g1 || !g2))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  {
+    // independent per element: a large batch is split over the process's devices, no exchange at all
+    const std::vector<int> devs = spread_devices(n, true);
+    if (!devs.empty())
+      return run_on_devices(devs, n, [&](size_t, size_t lo, size_t hi) {
+        return pairing_host(curve, what, g1 ? (const char*)g1 + lo * ppp * ops->g1 : nullptr,
+                            g2 ? (const char*)g2 + lo * ppp * ops->g2 : nullptr, ppp, hi - lo,
+                            in ? (const char*)in + lo * ops->gt : nullptr, (char*)out + lo * ops->gt);
+      });
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  void *d1 = nullptr, *d2 = nullptr, *din = nullptr;
+  if (what == 1) {
+    hc.reserve(2 * n * ops->gt);
+    din = hc.up(in, n * ops->gt);
+  } else {
+    hc.reserve(n * ppp * (ops->g1 + ops->g2) + n * ops->gt);
+    d1 = hc.up(g1, n * ppp * ops->g1);
+    d2 = hc.up(g2, n * ppp * ops->g2);
+  }
+  void* dout = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = ops->pairing(what, d1, d2, ppp, n, din, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ops->gt);
+}
+
+
+// the same on device pointers, in order on `stream`
+int pairing_device(int curve, int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out,
+                   void* stream) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->pairing(what, d_g1, d_g2, ppp, n, d_in, d_out, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" {
+
+int mlhip_miller_loop(int curve, const void* g1, const void* g2, size_t ppp, size_t n_products, void* out_gt) {
+  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
+  return pairing_host(curve, 0, g1, g2, ppp, n_products, nullptr, out_gt);
+}
+
+int mlhip_final_exp(int curve, const void* in_gt, size_t n, void* out_gt) {
+  return pairing_host(curve, 1, nullptr, nullptr, 1, n, in_gt, out_gt);
+}
+
+int mlhip_pairing_batch(int curve, const void* g1, const void* g2, size_t n, void* out_gt) {
+  return pairing_host(curve, 2, g1, g2, 1, n, nullptr, out_gt);
+}
+
+int mlhip_miller_loop_device(int curve, const void* d_g1, const void* d_g2, size_t ppp, size_t n_products,
+                             void* d_out_gt, void* stream) {
+  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
+  return pairing_device(curve, 0, d_g1, d_g2, ppp, n_products, nullptr, d_out_gt, stream);
+}
+
+int mlhip_final_exp_device(int curve, const void* d_in_gt, size_t n, void* d_out_gt, void* stream) {
+  return pairing_device(curve, 1, nullptr, nullptr, 1, n, d_in_gt, d_out_gt, stream);
+}
+
+int mlhip_pairing_batch_device(int curve, const void* d_g1, const void* d_g2, size_t n, void* d_out_gt, void* stream) {
+  return pairing_device(curve, 2, d_g1, d_g2, 1, n, nullptr, d_out_gt, stream);
+}
+
+// ---- prepared G2 handles (include/mlhip.h; kernels: pairing_prepared_kernels.h) ---------------------------------------------
+struct mlhip_g2_prepared {
+  mlhip_g2_prepared_tables t;
+  const CurveOps* ops = nullptr;
+  int device = 0;
+};
+
+int mlhip_g2_prepared_destroy(mlhip_g2_prepared* h) {
+  if (!h) return 0;
+  (void)hipSetDevice(h->device);
+  if (h->t.d_q) (void)hipFree(h->t.d_q);
+  if (h->t.d_t28) (void)hipFree(h->t.d_t28);
+  if (h->t.d_t32) (void)hipFree(h->t.d_t32);
+  if (h->t.d_inf) (void)hipFree(h->t.d_inf);
+  delete h;
+  return 0;
+}
+
+static int g2_prepared_create(int curve, const void* points, bool on_device, size_t m, mlhip_g2_prepared** out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  *out = nullptr;
+  if (m == 0) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_g2_prepared_create: m must be at least 1");
+  if (!points) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  mlhip_g2_prepared* h = new mlhip_g2_prepared;
+  h->ops = ops;
+  h->device = call_device();
+  h->t.m = m;
+  auto body = [&]() -> int {
+    HIPCHK(hipMalloc(&h->t.d_q, m * ops->g2));
+    HostCall hc;  // a leased stream: the build does not meet other callers on the null stream
+    if (hc.rc) return hc.rc;
+    HIPCHK(hipMemcpyAsync(h->t.d_q, points, m * ops->g2, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, hc.l.st));
+    int r = ops->g2_prepared(&h->t, -1, nullptr, nullptr, 0, 0, nullptr, hc.l.st);
+    if (r) return r;
+    HIPCHK(hipStreamSynchronize(hc.l.st));
+    return 0;
+  };
+  rc = body();
+  if (rc) {
+    mlhip_g2_prepared_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return 0;
+}
+
+int mlhip_g2_prepared_create(int curve, const void* g2_points, size_t m, mlhip_g2_prepared** h) {
+  return g2_prepared_create(curve, g2_points, false, m, h);
+}
+
+int mlhip_g2_prepared_create_device(int curve, const void* d_g2_points, size_t m, mlhip_g2_prepared** h) {
+  return g2_prepared_create(curve, d_g2_points, true, m, h);
+}
+
+int mlhip_g2_prepared_count(mlhip_g2_prepared* h, size_t* m) {
+  if (!h || !m) return mlhip_rt::fail(MLHIP_EINVAL, h ? "null pointer" : "null handle");
+  *m = h->t.m;
+  return 0;
+}
+
+// every argument error of the four entry points, before anything is launched; 1 = nothing to do
+static int g2_prepared_check(const mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
+                             const void* out) {
+  if (!h) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
+  if (q_index) {
+    for (size_t j = 0; j < ppp; j++)
+      if (q_index[j] >= h->t.m) return mlhip_rt::fail(MLHIP_EINVAL, "q_index entry beyond the handle's points");
+  } else if (ppp > h->t.m) {
+    return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product exceeds the handle's points (no q_index)");
+  }
+  if (n == 0) return 1;
+  if (!g1 || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  return 0;
+}
+
+static int g2_prepared_device(mlhip_g2_prepared* h, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,
+                              void* d_out, void* stream) {
+  int rc = g2_prepared_check(h, d_g1, q_index, ppp, n, d_out);
+  if (rc) return rc < 0 ? rc : 0;
+  // the launch needs the handle's device current; the caller gets its own current device back (`stream` and the pointers
+  // must belong to the handle's device: multi-device handles are out of scope)
+  int prev = h->device;
+  (void)hipGetDevice(&prev);
+  if (prev != h->device && hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  rc = h->ops->g2_prepared(&h->t, what, d_g1, q_index, ppp, n, d_out, (hipStream_t)stream);
+  if (prev != h->device) (void)hipSetDevice(prev);
+  return rc;
+}
+
+static int g2_prepared_host(mlhip_g2_prepared* h, int what, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
+                            void* out) {
+  int rc = g2_prepared_check(h, g1, q_index, ppp, n, out);
+  if (rc) return rc < 0 ? rc : 0;
+  if (hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  call_device() = h->device;  // thread_local (the device of this thread's call in progress): the call's scratch is leased on the handle's device
+  HostCall hc;
+  hc.reserve(n * ppp * h->ops->g1 + n * h->ops->gt);
+  void* d1 = hc.up(g1, n * ppp * h->ops->g1);
+  void* dout = hc.dev(n * h->ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = h->ops->g2_prepared(&h->t, what, d1, q_index, ppp, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * h->ops->gt);
+}
+
+int mlhip_miller_loop_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n_products,
+                               void* out_gt) {
+  return g2_prepared_host(h, 0, g1, q_index, ppp, n_products, out_gt);
+}
+
+int mlhip_miller_loop_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                      size_t n_products, void* d_out_gt, void* stream) {
+  return g2_prepared_device(h, 0, d_g1, q_index, ppp, n_products, d_out_gt, stream);
+}
+
+int mlhip_pairing_prepared(mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n_products,
+                           void* out_gt) {
+  return g2_prepared_host(h, 2, g1, q_index, ppp, n_products, out_gt);
+}
+
+int mlhip_pairing_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                                  size_t n_products, void* d_out_gt, void* stream) {
+  return g2_prepared_device(h, 2, d_g1, q_index, ppp, n_products, d_out_gt, stream);
+}
+
+int mlhip_gt_mul_device(int curve, const void* d_a, const void* d_b, size_t n, void* d_out, void* stream) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->gt_mul(d_a, d_b, n, d_out, (hipStream_t)stream);
+}
+
+int mlhip_gt_mul(int curve, const void* a, const void* b, size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!a || !b || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(3 * n * ops->gt);
+  void* da = hc.up(a, n * ops->gt);
+  void* db = hc.up(b, n * ops->gt);
+  void* dout = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_gt_mul_device(curve, da, db, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ops->gt);
+}
+
+int mlhip_gt_exp_device(int curve, const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, void* stream) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->gt_exp(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream);
+}
+
+int mlhip_gt_exp(int curve, const void* in, const void* scalars, int mont, size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!in || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(2 * n * ops->gt + n * 32);
+  void* din = hc.up(in, n * ops->gt);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = mlhip_gt_exp_device(curve, din, ds, mont, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ops->gt);
+}
+
+int mlhip_pairing_product(int curve, const void* g1, const void* g2, size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  if (n && (!g1 || !g2)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  // n == 0: the empty product, FExp(1) = 1; run it through the same kernels with one infinity pair
+  const size_t m0 = n ? n : 1;
+  HostCall hc;
+  hc.reserve(m0 * (ops->g1 + ops->g2 + ops->gt));
+  void *d1, *d2;
+  if (n) {
+    d1 = hc.up(g1, n * ops->g1);
+    d2 = hc.up(g2, n * ops->g2);
+  } else {
+    d1 = hc.dev(ops->g1);
+    d2 = hc.dev(ops->g2);
+    if (!hc.rc && (hipMemsetAsync(d1, 0, ops->g1, hc.l.st) != hipSuccess || hipMemsetAsync(d2, 0, ops->g2, hc.l.st) != hipSuccess))
+      hc.rc = mlhip_rt::fail(MLHIP_EHIP, "hipMemset failed");
+  }
+  void* dgt = hc.dev(m0 * ops->gt);
+  if (hc.rc) return hc.rc;
+  // One Miller loop per lane pair while the pairs do not fill the GPU (latency: 7 pairs take 21 ms this way, 45 ms
+  // grouped -- measured); beyond 2^17 pairs four pairs share one accumulator's squarings (throughput).
+  const size_t per = m0 >= ((size_t)1 << 17) ? 4 : 1;
+  const size_t groups = m0 / per, rest = m0 % per;
+  rc = ops->pairing(0, d1, d2, per, groups, nullptr, dgt, hc.l.st);
+  if (!rc && rest)
+    rc = ops->pairing(0, (const char*)d1 + per * groups * ops->g1, (const char*)d2 + per * groups * ops->g2, rest, 1,
+                    nullptr, (char*)dgt + groups * ops->gt, hc.l.st);
+  // tree product: fold the upper part onto the lower part until one value is left
+  size_t m = groups + (rest ? 1 : 0);
+  while (m > 1 && rc == 0) {
+    size_t half = m / 2;
+    rc = mlhip_gt_mul_device(curve, dgt, (const char*)dgt + (m - half) * ops->gt, half, dgt, hc.l.st);
+    m -= half;
+  }
+  if (!rc) rc = ops->pairing(1, nullptr, nullptr, 1, 1, dgt, dgt, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dgt, ops->gt);
+}
+
+int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, void* stream) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (n == 0) return 0;
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  return ops->fp_mul(d_a, d_b, n, repeat, d_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

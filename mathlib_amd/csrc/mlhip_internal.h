@@ -14,7 +14,7 @@ int fail(int code, const std::string& msg);
 // all are there.  fn must be a pure function of the `in_bytes` bytes at `in` (the call copies them: a worker never touches
 // the caller's memory) writing `out_stride` bytes.  The workers are started on first use (MLHIP_HOST_THREADS = threads per
 // call incl. the caller, default min(8, cores); 1 = none); a call that finds them busy with another caller's jobs, or
-// njobs < 2, computes everything itself, and a job a worker is slow with is computed by the caller as well (api.hip).
+// njobs < 2, computes everything itself, and a job a worker is slow with is computed by the caller as well (rt.hip).
 // Used by the host tail of an MSM (msm_plan.h: host_tail): the per-window sums are independent of each other.
 void host_parallel(int njobs, void (*fn)(const void*, int, void*), const void* in, size_t in_bytes, void* out, size_t out_stride);
 }
@@ -78,7 +78,7 @@ struct mlhip_msm_plan {
   void* d_points28 = nullptr;  // G1: the points in the carry-free 28-bit-limb form (ec28.h), rewritten every MSM
   // bytes per point d_points28 was allocated with, and what the twisted Edwards form (Niels triples, ed28.h) would need
   // (0: this curve / group has none).  A BLS12-377 G1 plan starts with the 112-byte Weierstrass rows and grows to 168 bytes
-  // only when the caller makes the SRS promise (api.hip: plan_reserve_edwards) -- at 2^24 points that is 0.9 GB not spent
+  // only when the caller makes the SRS promise (api_msm.hip: plan_reserve_edwards) -- at 2^24 points that is 0.9 GB not spent
   // on plans that never take the Edwards path
   size_t points28_elem = 0, points28_elem_ed = 0;
   bool profiling = false;
@@ -138,39 +138,70 @@ struct mlhip_g2_prepared_tables {
   size_t m = 0;
 };
 
-// per-curve entry points, defined in tu_msm_<curve>.hip / tu_pairing_<curve>.hip
-#define MLHIP_DECLARE_CURVE(NAME)                                                                                   \
-  int mlhip_tu_plan_alloc_##NAME(mlhip_msm_plan* p);                                                                \
-  int mlhip_tu_plan_launch_##NAME(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, int mont,        \
-                                  size_t n, hipStream_t st);                                                       \
-  int mlhip_tu_plan_finish_##NAME(mlhip_msm_plan* p, void* out_affine, void* out_xyzz);                            \
-  int mlhip_tu_plan_stream_##NAME(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points,         \
-                                  const void* h_scalars, int mont, size_t n, int segments, hipStream_t st);         \
-  int mlhip_tu_plan_shared_##NAME(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d_points_g1, void* d_points_g2,     \
-                                  void* d_scalars, const void* h_points_g1, const void* h_points_g2,                \
-                                  const void* h_scalars, int mont, size_t n, hipStream_t st);                       \
-  int mlhip_tu_pairing_##NAME(int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, \
-                              void* d_out, hipStream_t st);                                                         \
-  int mlhip_tu_fp_mul_##NAME(const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st);   \
-  int mlhip_tu_gt_mul_##NAME(const void* d_a, const void* d_b, size_t n, void* d_out, hipStream_t st);             \
-  int mlhip_tu_gt_exp_##NAME(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out,             \
-                             hipStream_t st);                                                                      \
-  int mlhip_tu_wire_codec_##NAME(int group, int encode, const void* d_in, size_t n, int compressed, int subgroup,   \
-                                 void* d_out, void* d_status, hipStream_t st);                                     \
-  int mlhip_tu_scalar_mul_##NAME(int group, const void* d_points, size_t point_stride, const void* d_scalars,     \
-                                 int mont, size_t n, void* d_out, hipStream_t st);                                 \
-  int mlhip_tu_plan_fold_build_##NAME(mlhip_msm_plan* p, const void* d_points, size_t n, hipStream_t st);          \
-  int mlhip_tu_msm_batch_##NAME(int group, const void* d_points, const void* d_scalars, int mont,                 \
-                                const uint64_t* offsets, size_t k, void* d_out, hipStream_t st);                   \
-  int mlhip_tu_bases_batch_##NAME(int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases,       \
-                                  const void* d_scalars, int mont, const uint32_t* base_index, const uint64_t* offsets, \
-                                  size_t k, size_t need, void* d_out, hipStream_t st);                              \
-  /* what = -1: build t's tables from t->d_q ; 0 / 2: Miller loops / fused pairings of n products against them */    \
-  int mlhip_tu_g2_prepared_##NAME(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, \
-                                  size_t ppp, size_t n, void* d_out, hipStream_t st);                               \
-  void mlhip_tu_release_cache_##NAME(void);
+// ---- the per-curve operations -------------------------------------------------------------------------------------------
+// One line per operation: X(curve, result, name, (parameters)) declares mlhip_tu_<name>_<Curve> for the three curves, gives
+// CurveOps its `name` member and fills that member's slot in the three rows of the table (rt.hip).  The bodies are written
+// once, against MLHIP_TU_CURVE, in tu_msm.inc / tu_pairing.inc / tu_codec.inc; tu_<kind>_<curve>.hip instantiates them.
+#define MLHIP_TU_OPS(X, C)                                                                                                \
+  X(C, int, plan_alloc, (mlhip_msm_plan * p))                                                                             \
+  X(C, int, plan_launch,                                                                                                  \
+    (mlhip_msm_plan * p, const void* d_points, const void* d_scalars, int mont, size_t n, hipStream_t st))                \
+  X(C, int, plan_finish, (mlhip_msm_plan * p, void* out_affine, void* out_xyzz))                                          \
+  X(C, int, plan_stream,                                                                                                  \
+    (mlhip_msm_plan * p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,          \
+     size_t n, int segments, hipStream_t st))                                                                             \
+  X(C, int, plan_shared,                                                                                                  \
+    (mlhip_msm_plan * g1, mlhip_msm_plan * g2, void* d_points_g1, void* d_points_g2, void* d_scalars,                     \
+     const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n, hipStream_t st))        \
+  X(C, int, pairing,                                                                                                      \
+    (int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out, hipStream_t st))  \
+  X(C, int, fp_mul, (const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st))                \
+  X(C, int, gt_mul, (const void* d_a, const void* d_b, size_t n, void* d_out, hipStream_t st))                            \
+  X(C, int, gt_exp, (const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st))           \
+  X(C, int, wire_codec,                                                                                                   \
+    (int group, int encode, const void* d_in, size_t n, int compressed, int subgroup, void* d_out, void* d_status,        \
+     hipStream_t st))                                                                                                     \
+  X(C, int, scalar_mul,                                                                                                   \
+    (int group, const void* d_points, size_t point_stride, const void* d_scalars, int mont, size_t n, void* d_out,        \
+     hipStream_t st))                                                                                                     \
+  X(C, int, plan_fold_build, (mlhip_msm_plan * p, const void* d_points, size_t n, hipStream_t st))                        \
+  X(C, int, msm_batch,                                                                                                    \
+    (int group, const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,    \
+     hipStream_t st))                                                                                                     \
+  X(C, int, bases_batch,                                                                                                  \
+    (int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars, int mont,          \
+     const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out, hipStream_t st))            \
+  /* what = -1: build t's tables from t->d_q ; 0 / 2: Miller loops / fused pairings of n products against them */         \
+  X(C, int, g2_prepared,                                                                                                  \
+    (mlhip_g2_prepared_tables * t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,             \
+     void* d_out, hipStream_t st))                                                                                        \
+  X(C, void, release_cache, (void))
+
+#define MLHIP_OP_DECLARE(C, ret, name, params) ret mlhip_tu_##name##_##C params;
+#define MLHIP_OP_MEMBER(C, ret, name, params) ret(*name) params;
+#define MLHIP_OP_ROW(C, ret, name, params) mlhip_tu_##name##_##C,
+MLHIP_TU_OPS(MLHIP_OP_DECLARE, Bn254)
+MLHIP_TU_OPS(MLHIP_OP_DECLARE, Bls381)
+MLHIP_TU_OPS(MLHIP_OP_DECLARE, Bls377)
 // G1 points outside the prime-order subgroup (or off the curve) in an array of affine points: mlhip_bases_create's check
 int mlhip_tu_g1_count_outside_subgroup_Bls377(const void* d_pts, size_t n, uint32_t* d_bad, hipStream_t st);
-MLHIP_DECLARE_CURVE(Bn254)
-MLHIP_DECLARE_CURVE(Bls381)
-MLHIP_DECLARE_CURVE(Bls377)
+
+// mlhip_tu_<name>_<MLHIP_TU_CURVE>: the name a tu_*.inc body defines
+#define MLHIP_TU_PASTE_(name, C) mlhip_tu_##name##_##C
+#define MLHIP_TU_PASTE(name, C) MLHIP_TU_PASTE_(name, C)
+#define MLHIP_TU_FN(name) MLHIP_TU_PASTE(name, MLHIP_TU_CURVE)
+
+namespace mlhip_rt {
+// what the API layer knows about a curve: plain static data, one row per curve id (rt.hip)
+struct CurveOps {
+  size_t fp, g1, g2, gt;  // bytes of an Fp element, an affine G1 / G2 point, a Gt value
+  int fr_bits;
+  MLHIP_TU_OPS(MLHIP_OP_MEMBER, )
+  int (*g1_sum)(const void* pts, size_t n, void* out);  // host sums of n affine points (mlhip_g1_sum / mlhip_g2_sum)
+  int (*g2_sum)(const void* pts, size_t n, void* out);
+  int (*g1_count_outside_subgroup)(const void* d_pts, size_t n, uint32_t* d_bad, hipStream_t st);  // null except BLS12-377
+  // bytes of an affine point of `group`; 0: the group is neither MLHIP_GROUP_G1 nor MLHIP_GROUP_G2
+  size_t point_size(int group) const { return group == MLHIP_GROUP_G1 ? g1 : group == MLHIP_GROUP_G2 ? g2 : 0; }
+};
+const CurveOps* curve_ops(int curve);  // null: unknown curve id
+}  // namespace mlhip_rt

@@ -278,7 +278,7 @@ void bases_batch_launch_free(const void* d_pts, const void* d_scalars, int mont,
         (XYZZ<Fp2Field<C>>*)d_partials);
 }
 
-// mlhip_bases_msm_batch_device behind its checks (api.hip): k >= 1 checked offsets, base_index (host, may be null) within the
+// mlhip_bases_msm_batch_device behind its checks (api_bases.hip): k >= 1 checked offsets, base_index (host, may be null) within the
 // handle's n_bases points, need = 1 + the largest base a pair reads (0: no pair)
 template <class C, class F>
 int bases_batch_device(mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars, int mont,

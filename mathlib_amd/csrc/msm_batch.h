@@ -355,7 +355,7 @@ int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes
   return 0;
 }
 
-// offsets: k + 1 checked host entries (api.hip: mlhip_msm_batch_device), k >= 1
+// offsets: k + 1 checked host entries (api_msm.hip: mlhip_msm_batch_device), k >= 1
 template <class C, class F>
 int msm_batch_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
                      hipStream_t st) {

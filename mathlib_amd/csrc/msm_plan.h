@@ -1119,7 +1119,7 @@ int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1
   if (p1->fold || p2->fold) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
   int K = 1;
   if (h_scalars) {
-    // uploads to hide: segments of 2^17 pairs, as a host-buffer G2 MSM (api.hip: stream_segments)
+    // uploads to hide: segments of 2^17 pairs, as a host-buffer G2 MSM (api_msm.hip: stream_segments)
     K = (int)std::min<size_t>(std::max<size_t>(n >> 17, 1), MLHIP_MAX_SEGMENTS);
     if (const char* e = getenv("MLHIP_STREAM_SEGMENTS")) {
       const int v = atoi(e);

@@ -1,8 +1,3 @@
 // Wire-format codec kernels instantiated for Bn254.
-#include "codec_kernels.h"
-using namespace mlhip;
-int mlhip_tu_wire_codec_Bn254(int group, int encode, const void* d_in, size_t n, int compressed, int subgroup, void* d_out,
-                             void* d_status, hipStream_t st) {
-  if (group == 2) return wire_codec_device<G2Wire<Bn254>>(encode, d_in, n, compressed, subgroup, d_out, d_status, st);
-  return wire_codec_device<G1Wire<Bn254>>(encode, d_in, n, compressed, subgroup, d_out, d_status, st);
-}
+#define MLHIP_TU_CURVE Bn254
+#include "tu_codec.inc"

@@ -1,0 +1,23 @@
+// The pairing and Gt operations of one curve (mlhip_internal.h: MLHIP_TU_OPS): tu_pairing_<curve>.hip defines MLHIP_TU_CURVE and
+// includes this.
+#include "pairing_kernels.h"
+#include "pairing_prepared_kernels.h"
+using namespace mlhip;
+int MLHIP_TU_FN(pairing)(int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in,
+                        void* d_out, hipStream_t st) {
+  return pairing_device<MLHIP_TU_CURVE>(what, d_g1, d_g2, ppp, n, d_in, d_out, st);
+}
+int MLHIP_TU_FN(fp_mul)(const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st) {
+  return fp_mul_device<MLHIP_TU_CURVE>(d_a, d_b, n, repeat, d_out, st);
+}
+int MLHIP_TU_FN(gt_mul)(const void* d_a, const void* d_b, size_t n, void* d_out, hipStream_t st) {
+  return gt_mul_device<MLHIP_TU_CURVE>(d_a, d_b, n, d_out, st);
+}
+int MLHIP_TU_FN(gt_exp)(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
+  return gt_exp_device<MLHIP_TU_CURVE>(d_in, d_scalars, mont, n, d_out, st);
+}
+int MLHIP_TU_FN(g2_prepared)(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
+                            size_t n, void* d_out, hipStream_t st) {
+  if (what < 0) return g2_prepared_build<MLHIP_TU_CURVE>(t, st);
+  return g2_prepared_run<MLHIP_TU_CURVE>(t, what, d_g1, q_index, ppp, n, d_out, st, pairing_device<MLHIP_TU_CURVE>);
+}

@@ -32,7 +32,7 @@ def test_shipped_code_objects_are_clean():
 
         build.build(verbose=False)
     findings, stats = check_codeobj.check_file(LIB, jobs=4)
-    assert stats["code_objects"] == 9, stats  # one per translation unit with kernels (api.hip has none)
+    assert stats["code_objects"] == 9, stats  # one per translation unit with kernels (rt.hip and api_*.hip have none)
     assert stats["kernels"] > 150 and stats["kernels_with_calls"] > 50 and stats["flat_insns"] > 1000, stats
     assert not findings, "\n".join(findings[:20])
 

@@ -164,7 +164,7 @@ def test_bench_multi_rank_rehearsal_is_self_explaining(config, ranks):
 
 
 def test_host_pool_is_sized_per_rank():
-    """api.hip: host_pool_start -- the host-tail worker pool is sized from the process's affinity mask divided by
+    """rt.hip: host_pool_start -- the host-tail worker pool is sized from the process's affinity mask divided by
     LOCAL_WORLD_SIZE (8 ranks of `bench.py --gpus 8` share one host), halved when ranks share the host; MLHIP_HOST_THREADS
     overrides.  The workers are named, so a fresh process can count them after one MSM."""
     import subprocess

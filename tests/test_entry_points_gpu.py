@@ -282,3 +282,135 @@ def test_msm_pipelined_two_plans_two_streams(lib, mlhip, group):
     assert lib.mlhip_msm_finish(plans[0], out, None) == mlhip.EINVAL  # nothing pending
     for h in plans:
         assert lib.mlhip_msm_plan_destroy(h) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# an unknown curve id through every entry point that takes one
+# ---------------------------------------------------------------------------------------------------------------------
+def _curve_entry_points():
+    """the exported functions whose first parameter is `int curve`, from include/mlhip.h (as tests/test_api_coverage.py)"""
+    import os
+    import re
+
+    from conftest import ROOT
+
+    with open(os.path.join(ROOT, "include", "mlhip.h")) as f:
+        text = f.read()
+    return sorted(re.findall(r"^MLHIP_API\b[^(;]*?\b(mlhip_\w+)\s*\(\s*int\s+curve\b", text, flags=re.M))
+
+
+# (return code, mlhip_last_error() contains "unknown curve id") of each of them for curve id 7 and n = k = ppp = 1, as the
+# library answered when every entry point dispatched through its own `switch (curve)`: with n = 1 each of them reaches its
+# curve check (curve_sizes, or the switch's default) before anything else can fail or return early; -1 = MLHIP_EINVAL
+_UNKNOWN_CURVE = {
+    "mlhip_bases_create": (-1, True),
+    "mlhip_bases_create_device": (-1, True),
+    "mlhip_bases_create_multi": (-1, True),
+    "mlhip_final_exp": (-1, True),
+    "mlhip_final_exp_device": (-1, True),
+    "mlhip_fp_mul_device": (-1, True),
+    "mlhip_g1_from_bytes": (-1, True),
+    "mlhip_g1_from_bytes_device": (-1, True),
+    "mlhip_g1_sum": (-1, True),
+    "mlhip_g1_to_bytes": (-1, True),
+    "mlhip_g1_to_bytes_device": (-1, True),
+    "mlhip_g2_from_bytes": (-1, True),
+    "mlhip_g2_from_bytes_device": (-1, True),
+    "mlhip_g2_prepared_create": (-1, True),
+    "mlhip_g2_prepared_create_device": (-1, True),
+    "mlhip_g2_sum": (-1, True),
+    "mlhip_g2_to_bytes": (-1, True),
+    "mlhip_g2_to_bytes_device": (-1, True),
+    "mlhip_gt_exp": (-1, True),
+    "mlhip_gt_exp_device": (-1, True),
+    "mlhip_gt_mul": (-1, True),
+    "mlhip_gt_mul_device": (-1, True),
+    "mlhip_miller_loop": (-1, True),
+    "mlhip_miller_loop_device": (-1, True),
+    "mlhip_msm_batch": (-1, True),
+    "mlhip_msm_batch_device": (-1, True),
+    "mlhip_msm_g1": (-1, True),
+    "mlhip_msm_g1g2": (-1, True),
+    "mlhip_msm_g2": (-1, True),
+    "mlhip_msm_multi": (-1, True),
+    "mlhip_msm_plan_create": (-1, True),
+    "mlhip_pairing_batch": (-1, True),
+    "mlhip_pairing_batch_device": (-1, True),
+    "mlhip_pairing_product": (-1, True),
+    "mlhip_scalar_mul": (-1, True),
+    "mlhip_scalar_mul_device": (-1, True),
+    "mlhip_sizes": (-1, True),
+}
+
+
+def test_unknown_curve_id_every_entry_point(lib, mlhip):
+    """curve id 7 with n = 1 (k = 1, ppp = 1) through every exported function that takes a curve: the return code and whether
+    the error text names the curve, against the table above.  Every pointer is a real zero-filled buffer larger than any
+    curve's Gt value, so a check that moved cannot become a wild access; nothing is launched."""
+    import torch
+
+    bad = 7
+    big = 4096  # bytes: a Gt value of the 48-byte fields is 576
+    hb = [ctypes.create_string_buffer(big) for _ in range(5)]  # host buffers, zero-filled
+    db = [torch.zeros(big, dtype=torch.uint8, device="cuda") for _ in range(4)]
+    torch.cuda.synchronize()
+    h0, h1, h2, h3, h4 = hb
+    d0, d1, d2, d3 = (t.data_ptr() for t in db)
+    st = torch.cuda.Stream().cuda_stream
+    offs = mlhip.batch_offsets([1])
+    devs = (ctypes.c_int * 1)(0)
+    sizes = [ctypes.c_size_t() for _ in range(4)]
+    handle = ctypes.c_void_p()
+    hp = ctypes.byref(handle)
+    calls = {
+        "mlhip_sizes": lambda: lib.mlhip_sizes(bad, *(ctypes.byref(s) for s in sizes)),
+        "mlhip_msm_g1": lambda: lib.mlhip_msm_g1(bad, h0, h1, 0, 1, 0, h2),
+        "mlhip_msm_g2": lambda: lib.mlhip_msm_g2(bad, h0, h1, 0, 1, 0, h2),
+        "mlhip_msm_g1g2": lambda: lib.mlhip_msm_g1g2(bad, h0, h1, h2, 0, 1, 0, h3, h4),
+        "mlhip_msm_multi": lambda: lib.mlhip_msm_multi(bad, 1, devs, 1, h0, h1, 0, 1, 0, h2),
+        "mlhip_msm_plan_create": lambda: lib.mlhip_msm_plan_create(bad, 1, 1, 0, hp),
+        "mlhip_msm_batch": lambda: lib.mlhip_msm_batch(bad, 1, h0, h1, 0, offs, 1, h2),
+        "mlhip_msm_batch_device": lambda: lib.mlhip_msm_batch_device(bad, 1, d0, d1, 0, offs, 1, d2, st),
+        "mlhip_scalar_mul": lambda: lib.mlhip_scalar_mul(bad, 1, h0, 1, h1, 0, 1, h2),
+        "mlhip_scalar_mul_device": lambda: lib.mlhip_scalar_mul_device(bad, 1, d0, 1, d1, 0, 1, d2, st),
+        "mlhip_g1_sum": lambda: lib.mlhip_g1_sum(bad, h0, 1, h1),
+        "mlhip_g2_sum": lambda: lib.mlhip_g2_sum(bad, h0, 1, h1),
+        "mlhip_bases_create": lambda: lib.mlhip_bases_create(bad, 1, h0, 1, 0, hp),
+        "mlhip_bases_create_device": lambda: lib.mlhip_bases_create_device(bad, 1, d0, 1, 0, hp),
+        "mlhip_bases_create_multi": lambda: lib.mlhip_bases_create_multi(bad, 1, devs, 1, h0, 1, 0, hp),
+        "mlhip_miller_loop": lambda: lib.mlhip_miller_loop(bad, h0, h1, 1, 1, h2),
+        "mlhip_final_exp": lambda: lib.mlhip_final_exp(bad, h0, 1, h1),
+        "mlhip_pairing_batch": lambda: lib.mlhip_pairing_batch(bad, h0, h1, 1, h2),
+        "mlhip_pairing_product": lambda: lib.mlhip_pairing_product(bad, h0, h1, 1, h2),
+        "mlhip_miller_loop_device": lambda: lib.mlhip_miller_loop_device(bad, d0, d1, 1, 1, d2, st),
+        "mlhip_final_exp_device": lambda: lib.mlhip_final_exp_device(bad, d0, 1, d1, st),
+        "mlhip_pairing_batch_device": lambda: lib.mlhip_pairing_batch_device(bad, d0, d1, 1, d2, st),
+        "mlhip_gt_mul": lambda: lib.mlhip_gt_mul(bad, h0, h1, 1, h2),
+        "mlhip_gt_mul_device": lambda: lib.mlhip_gt_mul_device(bad, d0, d1, 1, d2, st),
+        "mlhip_gt_exp": lambda: lib.mlhip_gt_exp(bad, h0, h1, 0, 1, h2),
+        "mlhip_gt_exp_device": lambda: lib.mlhip_gt_exp_device(bad, d0, d1, 0, 1, d2, st),
+        "mlhip_fp_mul_device": lambda: lib.mlhip_fp_mul_device(bad, d0, d1, 1, 1, d2, st),
+        "mlhip_g2_prepared_create": lambda: lib.mlhip_g2_prepared_create(bad, h0, 1, hp),
+        "mlhip_g2_prepared_create_device": lambda: lib.mlhip_g2_prepared_create_device(bad, d0, 1, hp),
+        "mlhip_g1_from_bytes": lambda: lib.mlhip_g1_from_bytes(bad, h0, 1, 1, 1, h1, h2),
+        "mlhip_g2_from_bytes": lambda: lib.mlhip_g2_from_bytes(bad, h0, 1, 1, 1, h1, h2),
+        "mlhip_g1_to_bytes": lambda: lib.mlhip_g1_to_bytes(bad, h0, 1, 1, h1),
+        "mlhip_g2_to_bytes": lambda: lib.mlhip_g2_to_bytes(bad, h0, 1, 1, h1),
+        "mlhip_g1_from_bytes_device": lambda: lib.mlhip_g1_from_bytes_device(bad, d0, 1, 1, 1, d1, d2, st),
+        "mlhip_g2_from_bytes_device": lambda: lib.mlhip_g2_from_bytes_device(bad, d0, 1, 1, 1, d1, d2, st),
+        "mlhip_g1_to_bytes_device": lambda: lib.mlhip_g1_to_bytes_device(bad, d0, 1, 1, d1, st),
+        "mlhip_g2_to_bytes_device": lambda: lib.mlhip_g2_to_bytes_device(bad, d0, 1, 1, d1, st),
+    }
+    names = _curve_entry_points()
+    assert len(names) >= 37 and set(names) == set(calls) == set(_UNKNOWN_CURVE), sorted(set(names) ^ set(calls))
+    got = {}
+    for name in names:
+        assert lib.mlhip_set_device(99) == mlhip.EINVAL  # changes nothing but the thread's error text
+        assert b"unknown curve id" not in lib.mlhip_last_error()
+        rc = calls[name]()
+        got[name] = (rc, b"unknown curve id" in lib.mlhip_last_error())
+        print("%-34s rc %d  text %s" % ((name,) + got[name]))
+        assert not handle.value, name  # no call made a handle
+    torch.cuda.synchronize()
+    assert got == _UNKNOWN_CURVE, {n: (got[n], _UNKNOWN_CURVE[n]) for n in names if got[n] != _UNKNOWN_CURVE[n]}
+    assert all(bytes(b.raw) == bytes(big) for b in hb) and all(not t.any().item() for t in db)  # and nothing was written

@@ -1,7 +1,7 @@
 """Every pairing path against the oracle (oracle/cref, byte-exact; oracle/pyref for Gt.Exp).
 
 pairing_device (mathlib_amd/csrc/pairing_kernels.h) picks a kernel from what is asked (Miller loop, final exponentiation,
-fused pairing), the pairs per product (1 .. 4), the curve and the batch size; mlhip_pairing_product (api.hip) groups four
+fused pairing), the pairs per product (1 .. 4), the curve and the batch size; mlhip_pairing_product (api_pairing.hip) groups four
 pairs per Miller loop from 2^17 pairs on.  The points are P_i = [a_i]G1 and Q_i = [b_i]G2 with known logs
 (cref.gen_points), so any product of pairings has an exact expected value: e(G1, G2)^S with S = sum a_i b_i mod r is ONE
 oracle pairing of [S]G1 with G2.  Raw Miller values are not canonical; they are compared after a final exponentiation."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Best Pippenger window per problem size on this GPU (feeds pick_window in api.hip): resident inputs, best of 3."""
+"""Best Pippenger window per problem size on this GPU (feeds pick_window in api_msm.hip): resident inputs, best of 3."""
 import os
 import sys
 import time
