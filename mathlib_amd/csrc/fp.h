@@ -248,7 +248,8 @@ inline void fp_mul_host64(Fp<C>& r, const Fp<C>& a, const Fp<C>& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
 // gfx950 body: product-scanning Montgomery multiplication, one v_mad_u64_u32 + one v_addc_co_u32 per
 // limb product (generated: tools/gen_fp_comba.py).  Same result as fp_mul_inline, bit for bit
-// (checked on the GPU by tests/test_gpu_parity.py::test_fp_mul_kernel_* and everything built on it).
+// (checked on the GPU by tests/test_devmath_gpu.py::test_saturated_product_every_entry, which runs both forms on the
+// device over structured and random operands, and by tests/test_gpu_parity.py::test_fp_mul_kernel_*).
 #include "fp_mul_comba.inc"
 template <class C>
 __device__ __forceinline__ void fp_mul_device(Fp<C>& r, const Fp<C>& a, const Fp<C>& b) {

@@ -327,6 +327,46 @@ struct Ops {
     memcpy(out, &r, sizeof(F));
     return 0;
   }
+  // the same functions on RAW limb arrays (int32_t[N28] per operand: non-canonical, weighted, negative-limbed values),
+  // with the op codes of tests/devmath/devmath.hip: 16 mul, 17 sqr, 18 mul2 (a b + c d), 19 k2mul ((a, b, c, d) = (a0, a1,
+  // b0, b1) -> out, out2), 20 normalize, 21 reduce, 22 from_fp (a: uint32_t[N]), 23 to_fp (out: uint32_t[N]).  This build
+  // has no __HIP_DEVICE_COMPILE__: the products are fp28_mont / fp28_k2mul_portable.
+  static int fp28_raw(int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, int32_t* out2) {
+    const int32_t* in[4] = {a, b, c, d};
+    Fp28<C> v[4], r, r2;
+    const int arity = (op == 18 || op == 19) ? 4 : op == 16 ? 2 : 1;
+    for (int i = 0; i < arity; i++) {
+      if (!in[i]) return -3;
+      if (op != 22) memcpy(&v[i], in[i], sizeof(Fp28<C>));
+    }
+    switch (op) {
+      case 16: fp28_mul<C>(r, v[0], v[1]); break;
+      case 17: fp28_sqr<C>(r, v[0]); break;
+      case 18: fp28_mul2<C>(r, v[0], v[1], v[2], v[3]); break;
+      case 19:
+        if (!out2) return -3;
+        fp28_k2mul<C>(r, r2, v[0], v[1], v[2], v[3]);
+        memcpy(out2, &r2, sizeof(r2));
+        break;
+      case 20: fp28_normalize<C>(r, v[0]); break;
+      case 21: fp28_reduce<C>(r, v[0]); break;
+      case 22: {
+        F x;
+        memcpy(&x, a, sizeof(F));
+        fp28_from_fp<C>(r, x);
+        break;
+      }
+      case 23: {
+        F x;
+        fp28_to_fp<C>(x, v[0]);
+        memcpy(out, &x, sizeof(F));
+        return 0;
+      }
+      default: return -1;
+    }
+    memcpy(out, &r, sizeof(r));
+    return 0;
+  }
   // bucket accumulation through xyzz28_madd: sum of +-points, returned affine in the boundary form
   static int madd28_chain(const void* pts, const uint8_t* neg, int n, void* out) {
     const A1* p = (const A1*)pts;
@@ -932,6 +972,9 @@ int hm_chunks(int curve, const void* pts, int n_chunks, void* outA, void* outW0)
 int hm_g1_decode(int curve, const uint8_t* w, int compressed, int subgroup, void* out) { DISPATCH(curve, g1dec(w, compressed, subgroup, out)) }
 int hm_g1_encode(int curve, const void* pt, int compressed, uint8_t* w) { DISPATCH(curve, g1enc(pt, compressed, w)) }
 int hm_fp28_op(int curve, int op, const void* a, const void* b, const void* c, const void* d, void* out) { DISPATCH(curve, fp28_op(op, a, b, c, d, out)) }
+int hm_fp28_raw(int curve, int op, const int32_t* a, const int32_t* b, const int32_t* c, const int32_t* d, int32_t* out, int32_t* out2) {
+  DISPATCH(curve, fp28_raw(op, a, b, c, d, out, out2))
+}
 int hm_madd28_chain(int curve, const void* pts, const uint8_t* neg, int n, void* out) { DISPATCH(curve, madd28_chain(pts, neg, n, out)) }
 int hm_quad_chain(int curve, const void* pts, const void* zs, int n, void* out) { DISPATCH(curve, quad_chain(pts, zs, n, out)) }
 int hm_quad28_chain(int curve, const void* pts, const void* zs, int n, void* out) { DISPATCH(curve, quad28_chain(pts, zs, n, out)) }
