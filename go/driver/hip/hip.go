@@ -459,6 +459,35 @@ func (c *Curve) ExpBatch(gts []driver.Gt, b []driver.Zr) []driver.Gt {
 	return out
 }
 
+// ExpBatchGt is ExpBatch for values the caller knows to be members of Gt (FExp outputs, GenGt, products and powers of
+// these): the same results from cyclotomic squarings and a Frobenius split of the scalar (mlhip_gt_exp_cyclo).  A value
+// outside Gt, such as a Pairing or Pairing2 output before FExp, gives an undefined result; Gt.Exp and ExpBatch accept any.
+func (c *Curve) ExpBatchGt(gts []driver.Gt, b []driver.Zr) []driver.Gt {
+	n := len(gts)
+	if len(b) != n {
+		panic("hip: ExpBatchGt length mismatch")
+	}
+	if n == 0 {
+		return nil
+	}
+	in := make([]bls12381.GT, n)
+	scalars := make([]fr.Element, n)
+	for i := range gts {
+		in[i] = gts[i].(*gurvy381.Gt).GT
+		scalars[i] = gurvy381.ZrValue(b[i])
+	}
+	res := make([]bls12381.GT, n)
+	check(func() C.int {
+		return C.mlhip_gt_exp_cyclo(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&in[0]), unsafe.Pointer(&scalars[0]), 1, C.size_t(n),
+			unsafe.Pointer(&res[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range res {
+		out[i] = &gurvy381.Gt{GT: res[i]}
+	}
+	return out
+}
+
 // NewG1sFromCompressed decodes n compressed G1 points (the wire form of G1.Compressed, bls12-381.go:292-296)
 // on the device: decompression, curve check and subgroup check per point.  It is the bulk form of
 // NewG1FromCompressed (bls12-381.go:551-559) and panics like it on the first invalid encoding, with gnark's

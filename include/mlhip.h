@@ -127,6 +127,12 @@ MLHIP_API int mlhip_gt_mul(int curve, const void* a_gt, const void* b_gt, size_t
 /* out[i] = in[i]^(scalars[i]) in Gt (Gt.Exp, driver/gurvy/bls12381/bls12-381.go:399-407), element-wise over n;
  * valid for any Gt value.  Scalars as for the MSM entry points. */
 MLHIP_API int mlhip_gt_exp(int curve, const void* in_gt, const void* scalars, int scalars_mont, size_t n, void* out_gt);
+/* out[i] = in[i]^(scalars[i]) for in[i] in Gt (the subgroup of order r): same bytes as mlhip_gt_exp on such inputs, in a
+ * fraction of the time -- cyclotomic squarings and a split of the scalar over the Frobenius map.
+ * The caller PROMISES membership (FExp outputs, GenGt, products / powers of members; 1 is a member).  An input outside Gt
+ * gives an undefined RESULT, never a fault.  curve_id is a MLHIP_CURVE_* value; scalars as for mlhip_gt_exp (scalars_mont, any
+ * 256-bit value, reduced mod r). */
+MLHIP_API int mlhip_gt_exp_cyclo(int curve_id, const void* in_gt, const void* scalars, int scalars_mont, size_t n, void* out_gt);
 /* out = FExp( prod_i MillerLoop(g1[i], g2[i]) ): a multi-pairing product with ONE shared final exponentiation
  * (what a verifier computes before IsUnity: perf_test.go:254-259).  n Miller loops run one per lane, the
  * product is a log-depth tree of Gt multiplications on the device. */
@@ -189,6 +195,8 @@ MLHIP_API int mlhip_pairing_batch_device(int curve, const void* d_g1, const void
 MLHIP_API int mlhip_gt_mul_device(int curve, const void* d_a_gt, const void* d_b_gt, size_t n, void* d_out_gt, void* stream);
 MLHIP_API int mlhip_gt_exp_device(int curve, const void* d_in_gt, const void* d_scalars, int scalars_mont, size_t n,
                         void* d_out_gt, void* stream);
+MLHIP_API int mlhip_gt_exp_cyclo_device(int curve_id, const void* d_in_gt, const void* d_scalars, int scalars_mont, size_t n,
+                                        void* d_out_gt, void* stream);
 
 /* out[i] = [scalars[i]] points[i * point_stride]: batched single-scalar multiplication (G1.Mul / G2.Mul,
  * driver/gurvy/bls12381/bls12-381.go:238-247, :342-351).  point_stride = 0 multiplies one base point by

@@ -16,7 +16,7 @@
 //   Curve::FExp(gt)                      driver/math.go:56-57                         -> mlhip_final_exp
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
-//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch,
+//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt,
 //             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch
 #pragma once
 #include <array>
@@ -525,6 +525,23 @@ class Curve {
     Bytes in, sc, o(gt_bytes * gts.size());
     pack(gts, scalars, in, sc);
     check(mlhip_gt_exp(id, in.data(), sc.data(), scalars_mont ? 1 : 0, gts.size(), o.data()));
+    for (size_t i = 0; i < gts.size(); i++) {
+      Gt g = new_gt();
+      memcpy(g.raw.data(), o.data() + i * gt_bytes, gt_bytes);
+      out.push_back(g);
+    }
+    return out;
+  }
+  // ExpBatch for values the caller knows to be MEMBERS of Gt (FExp outputs, GenGt, products and powers of these): the same
+  // results from cyclotomic squarings and a Frobenius split of the scalar (mlhip_gt_exp_cyclo).  A value outside Gt -- a raw
+  // Pairing / Pairing2 output before FExp -- gives an undefined result; Gt.Exp and ExpBatch accept any.
+  std::vector<Gt> ExpBatchGt(const std::vector<Gt>& gts, const std::vector<Zr>& scalars) const {
+    if (gts.size() != scalars.size()) throw std::invalid_argument("ExpBatchGt: length mismatch");
+    std::vector<Gt> out;
+    if (gts.empty()) return out;
+    Bytes in, sc, o(gt_bytes * gts.size());
+    pack(gts, scalars, in, sc);
+    check(mlhip_gt_exp_cyclo(id, in.data(), sc.data(), scalars_mont ? 1 : 0, gts.size(), o.data()));
     for (size_t i = 0; i < gts.size(); i++) {
       Gt g = new_gt();
       memcpy(g.raw.data(), o.data() + i * gt_bytes, gt_bytes);

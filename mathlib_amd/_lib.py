@@ -37,6 +37,7 @@ SYMBOLS = [
     "mlhip_pairing_batch",
     "mlhip_gt_mul",
     "mlhip_gt_exp",
+    "mlhip_gt_exp_cyclo",
     "mlhip_pairing_product",
     "mlhip_msm_plan_create",
     "mlhip_msm_plan_destroy",
@@ -53,6 +54,7 @@ SYMBOLS = [
     "mlhip_pairing_batch_device",
     "mlhip_gt_mul_device",
     "mlhip_gt_exp_device",
+    "mlhip_gt_exp_cyclo_device",
     "mlhip_scalar_mul_device",
     "mlhip_scalar_mul",
     "mlhip_msm_batch_device",
@@ -186,8 +188,10 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.mlhip_pairing_batch.argtypes = [ci, vp, vp, sz, vp]
     lib.mlhip_gt_mul.argtypes = [ci, vp, vp, sz, vp]
     lib.mlhip_gt_exp.argtypes = [ci, vp, vp, ci, sz, vp]
+    lib.mlhip_gt_exp_cyclo.argtypes = [ci, vp, vp, ci, sz, vp]
     lib.mlhip_pairing_product.argtypes = [ci, vp, vp, sz, vp]
     lib.mlhip_gt_exp_device.argtypes = [ci, vp, vp, ci, sz, vp, vp]
+    lib.mlhip_gt_exp_cyclo_device.argtypes = [ci, vp, vp, ci, sz, vp, vp]
     lib.mlhip_msm_plan_create.argtypes = [ci, ci, sz, ci, POINTER(vp)]
     lib.mlhip_msm_plan_destroy.argtypes = [vp]
     lib.mlhip_msm_run.argtypes = [vp, vp, vp, ci, sz, vp, vp, vp]

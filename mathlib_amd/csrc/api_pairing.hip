@@ -269,6 +269,35 @@ int mlhip_gt_exp(int curve, const void* in, const void* scalars, int mont, size_
   return hc.down(out, dout, n * ops->gt);
 }
 
+// Gt.Exp for members of Gt (gt_exp_cyclo.h).  Both forms check their arguments before they look for a device.
+int mlhip_gt_exp_cyclo_device(int curve, const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!d_in || !d_scalars || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  return ops->gt_exp_cyclo(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream);
+}
+
+int mlhip_gt_exp_cyclo(int curve, const void* in, const void* scalars, int mont, size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!in || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(2 * n * ops->gt + n * 32);
+  void* din = hc.up(in, n * ops->gt);
+  void* ds = hc.up(scalars, n * 32);
+  void* dout = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = ops->gt_exp_cyclo(din, ds, mont, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ops->gt);
+}
+
 int mlhip_pairing_product(int curve, const void* g1, const void* g2, size_t n, void* out) {
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");

@@ -158,6 +158,8 @@ struct mlhip_g2_prepared_tables {
   X(C, int, fp_mul, (const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st))                \
   X(C, int, gt_mul, (const void* d_a, const void* d_b, size_t n, void* d_out, hipStream_t st))                            \
   X(C, int, gt_exp, (const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st))           \
+  /* the same for inputs the caller promises to lie in Gt (gt_exp_cyclo.h) */                                            \
+  X(C, int, gt_exp_cyclo, (const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st))     \
   X(C, int, wire_codec,                                                                                                   \
     (int group, int encode, const void* d_in, size_t n, int compressed, int subgroup, void* d_out, void* d_status,        \
      hipStream_t st))                                                                                                     \

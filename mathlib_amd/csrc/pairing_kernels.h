@@ -10,6 +10,7 @@
 #include "fp2_lanes28.h"
 #include "pairing_quad.h"
 #include "pairing.h"
+#include "gt_exp_cyclo.h"
 
 namespace mlhip {
 
@@ -685,6 +686,57 @@ int gt_exp_device(const void* d_in, const void* d_scalars, int mont, size_t n, v
     k_gt_exp_lp<C><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
                                                                           mont, n, (Fp12<C>*)d_out);
   }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- Gt.Exp for members of Gt (gt_exp_cyclo.h): the scalar split into digits of |x| (BN254: 6 x^2),
+// a 15-entry table of products of Frobenius images in scratch (the footprint of the kernels above) and 64 steps of one
+// cyclotomic squaring (BN254: two) and at most one product.  One exponentiation per quad of lanes ...
+template <class C>
+__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_cyclo_q28(const Fp12<C>* __restrict__ in,
+                                                                      const uint32_t* __restrict__ scalars, int mont, size_t n,
+                                                                      Fp12<C>* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t >> 2;  // quad-uniform exit
+  if (i >= n) return;
+  typedef Fp2L28<C> E2;
+  uint32_t s[8], dig[8];
+  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+  gt_exp_split<C>(dig, s);
+  Fp12Q<C, E2> tab[15], acc;
+  q28_load_gt<C>(tab[0], in, i);
+  gt_exp_cyclo_chain<C, GtOpsQ<C, E2>>(acc, tab, dig);
+  q28_store_gt<C>(out, i, acc);
+}
+// ... and per lane pair (MLHIP_PAIRING_QUAD=0, as for mlhip_gt_exp): the second implementation of the parity tests
+template <class C>
+__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_cyclo_lp28(const Fp12<C>* __restrict__ in,
+                                                                       const uint32_t* __restrict__ scalars, int mont, size_t n,
+                                                                       Fp12<C>* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t >> 1;  // pair-uniform exit
+  if (i >= n) return;
+  typedef Fp2L28<C> E2;
+  uint32_t s[8], dig[8];
+  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+  gt_exp_split<C>(dig, s);
+  Fp12<C, E2> tab[15], acc;
+  lp28_load_gt<C>(tab[0], in, i);
+  gt_exp_cyclo_chain<C, GtOpsLp<C, E2>>(acc, tab, dig);
+  lp28_store_gt<C>(out, i, acc);
+}
+
+template <class C>
+int gt_exp_cyclo_device(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
+  // quads unless MLHIP_PAIRING_QUAD=0, at every size, as gt_exp_device (no one-lane or saturated form of this chain exists)
+  const char* qe = getenv("MLHIP_PAIRING_QUAD");
+  if (!(qe && qe[0] == '0'))
+    k_gt_exp_cyclo_q28<C><<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
+                                                                                 mont, n, (Fp12<C>*)d_out);
+  else
+    k_gt_exp_cyclo_lp28<C><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in,
+                                                                                  (const uint32_t*)d_scalars, mont, n, (Fp12<C>*)d_out);
   HIPCHK(hipGetLastError());
   return 0;
 }

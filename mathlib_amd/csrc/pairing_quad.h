@@ -287,6 +287,71 @@ MLHIP_Q28_FN void fp12q_sqr(Fp12Q<C, E>& r, const Fp12Q<C, E>& a) {
   fp6_reduce<C>(r.v);
 }
 
+// r = a^2 for a in the cyclotomic subgroup: the Granger-Scott squaring of tower.h (fp12_cyclo_sqr) with its nine Fp2
+// squarings in FIVE rounds.  With a = (a0, a1, a2) + (b0, b1, b2) w, coefficient j of the quad form holds (aj | bj):
+//     S0 = (a0^2 | b0^2)   S1 = (a1^2 | b1^2)   S2 = (a2^2 | b2^2)         the six plain squares, three rounds
+//     R4 = ((a0 + b1)^2 | (b0 + a2)^2)                                     2 a0 b1 | 2 b0 a2 after subtracting the squares
+//     R5 = (  --        | (b2 + a1)^2)                                     2 b2 a1 on pair B, where xi times it is needed
+// and the results   c0' = (3 (xi b1^2 + a0^2) - 2 a0 | 3 xi 2 b2 a1 + 2 b0)
+//                   c1' = (3 (xi a2^2 + b0^2) - 2 a1 | 3 2 a0 b1 + 2 b1)
+//                   c2' = (3 (xi b2^2 + a1^2) - 2 a2 | 3 2 b0 a2 + 2 b2)
+// take two xi-multiples (of S2 and of a per-pair mix) instead of four.  Weights in the comments, as in tower.h.
+template <class C, class E>
+MLHIP_Q28_FN void fp12q_cyclo_sqr(Fp12Q<C, E>& r, const Fp12Q<C, E>& a) {
+  E S0, S1, S2, R4, R5, x, y, w, P67, SS1, XS2, V, M0, M1, M2, t, n;
+  fp2_sqr<C>(S0, a.v.c0);
+  fp2_sqr<C>(S1, a.v.c1);
+  fp2_sqr<C>(S2, a.v.c2);
+  quad_sel_b<C>(y, a.v.c1, a.v.c2);  // a2 | b1
+  quad_swap<C>(y, y);                // b1 | a2
+  fp2_add<C>(x, a.v.c0, y);          // a0 + b1 | b0 + a2   (2)
+  fp2_norm<C>(x);
+  fp2_sqr<C>(R4, x);
+  quad_swap<C>(y, a.v.c1);   // b1 | a1
+  fp2_add<C>(x, a.v.c2, y);  // a2 + b1 | b2 + a1   (2)
+  fp2_norm<C>(x);
+  fp2_sqr<C>(R5, x);
+  quad_sel_b<C>(w, S1, S2);  // a2^2 | b1^2
+  quad_swap<C>(w, w);        // b1^2 | a2^2
+  fp2_sub<C>(P67, R4, w);
+  fp2_sub<C>(P67, P67, S0);  // 2 a0 b1 | 2 b0 a2   (3)
+  quad_swap<C>(SS1, S1);     // b1^2 | a1^2
+  fp2_sub<C>(V, R5, S2);
+  fp2_sub<C>(V, V, SS1);        // -- | 2 b2 a1   (3)
+  quad_sel_b<C>(V, V, SS1);     // b1^2 | 2 b2 a1
+  fp2_mul_xi<C>(V, V);          // (<= 6)
+  fp2_add<C>(t, V, S0);         // xi b1^2 + a0^2 | --   (<= 7)
+  quad_sel_b<C>(M0, V, t);
+  fp2_mul_xi<C>(XS2, S2);       // xi a2^2 | xi b2^2   (<= 2)
+  quad_swap<C>(t, S0);          // b0^2 | a0^2
+  fp2_add<C>(t, XS2, t);        // xi a2^2 + b0^2 | --   (<= 3)
+  quad_swap<C>(w, P67);         // 2 b0 a2 | 2 a0 b1
+  quad_sel_b<C>(M1, w, t);
+  quad_swap<C>(t, XS2);         // xi b2^2 | xi a2^2
+  fp2_add<C>(t, t, S1);         // xi b2^2 + a1^2 | --   (<= 3)
+  quad_sel_b<C>(M2, P67, t);
+  // one propagation each before the 3 m -/+ 2 a combinations (5), as fp12_cyclo_sqr
+  fp2_norm<C>(M0);
+  fp2_norm<C>(M1);
+  fp2_norm<C>(M2);
+  const E* src[3] = {&a.v.c0, &a.v.c1, &a.v.c2};
+  const E* m[3] = {&M0, &M1, &M2};
+  E o[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    fp2_neg<C>(n, *src[j]);
+    quad_sel_b<C>(t, *src[j], n);  // -a | +b
+    fp2_add<C>(t, *m[j], t);
+    fp2_dbl<C>(t, t);
+    fp2_add<C>(o[j], t, *m[j]);
+    // the +-2 a terms are linear in the input: reduced mod p so that a chain of squarings does not double the value
+    fp2_reduce<C>(o[j]);
+  }
+  r.v.c0 = o[0];
+  r.v.c1 = o[1];
+  r.v.c2 = o[2];
+}
+
 // r = 1 / a = conj(a) / (a0^2 - v a1^2)
 template <class C, class E>
 MLHIP_HD_NOINLINE void fp12q_inv(Fp12Q<C, E>& r, const Fp12Q<C, E>& a) {

@@ -16,6 +16,9 @@ int MLHIP_TU_FN(gt_mul)(const void* d_a, const void* d_b, size_t n, void* d_out,
 int MLHIP_TU_FN(gt_exp)(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
   return gt_exp_device<MLHIP_TU_CURVE>(d_in, d_scalars, mont, n, d_out, st);
 }
+int MLHIP_TU_FN(gt_exp_cyclo)(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
+  return gt_exp_cyclo_device<MLHIP_TU_CURVE>(d_in, d_scalars, mont, n, d_out, st);
+}
 int MLHIP_TU_FN(g2_prepared)(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
                             size_t n, void* d_out, hipStream_t st) {
   if (what < 0) return g2_prepared_build<MLHIP_TU_CURVE>(t, st);

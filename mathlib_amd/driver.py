@@ -518,6 +518,19 @@ class Curve:
         check(load().mlhip_gt_exp(self.id, b"".join(g.raw for g in gts), self._scalars(scalars), 1 if self.scalars_mont else 0, n, out))
         return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
 
+    def ExpBatchGt(self, gts: Sequence[Gt], scalars: Sequence[Zr]) -> List[Gt]:
+        """ExpBatch for values the caller knows to be MEMBERS of Gt (FExp outputs, GenGt, products and powers of these): the
+        same results from cyclotomic squarings and a Frobenius split of the scalar (mlhip_gt_exp_cyclo).  A value outside
+        Gt -- a raw Pairing / Pairing2 output before FExp -- gives an undefined result; Gt.Exp and ExpBatch accept any."""
+        if len(gts) != len(scalars):
+            raise ValueError("ExpBatchGt: length mismatch")
+        n = len(gts)
+        if n == 0:
+            return []
+        out = ctypes.create_string_buffer(self.gt_bytes * n)
+        check(load().mlhip_gt_exp_cyclo(self.id, b"".join(g.raw for g in gts), self._scalars(scalars), 1 if self.scalars_mont else 0, n, out))
+        return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
+
     def PairingProduct(self, g2s: Sequence[G2], g1s: Sequence[G1]) -> Gt:
         """FExp(prod_i Pairing(g2s[i], g1s[i])) with one shared final exponentiation (additive API)."""
         if len(g2s) != len(g1s):
