@@ -488,6 +488,128 @@ func (c *Curve) ExpBatchGt(gts []driver.Gt, b []driver.Zr) []driver.Gt {
 	return out
 }
 
+// gtStatusError is gnark's message class for a Gt encoding the device refused: 1 = a coordinate >= p, 3 = not in Gt.
+func gtStatusError(st byte) string {
+	if st == 3 {
+		return "set bytes failed [invalid Gt: subgroup check failed]"
+	}
+	return "set bytes failed [invalid fp.Element encoding]"
+}
+
+// NewGtFromBytes decodes gnark's GT.Bytes() on the device (mlhip_gt_from_bytes) without the subgroup check, as GT.SetBytes
+// does, and panics like the embedded driver on a malformed encoding (bls12-381.go:571-579).
+func (c *Curve) NewGtFromBytes(b []byte) driver.Gt {
+	gts, st := c.NewGtFromBytesBatch(b, false)
+	if len(gts) != 1 {
+		panic("set bytes failed [invalid length]")
+	}
+	if st[0] != 0 {
+		panic(gtStatusError(st[0]))
+	}
+	return gts[0]
+}
+
+// NewGtFromBytesBatch decodes len(raw) / 576 encodings in one call.  With subgroupCheck each value is also tested for
+// membership of Gt (mlhip_gt_is_member's test).  statuses[i] is 0 (ok), 1 (malformed) or 3 (not in Gt); a value whose
+// status is not 0 is zero.
+func (c *Curve) NewGtFromBytesBatch(raw []byte, subgroupCheck bool) ([]driver.Gt, []byte) {
+	const sz = bls12381.SizeOfGT
+	if len(raw)%sz != 0 {
+		panic("set bytes failed [invalid length]")
+	}
+	n := len(raw) / sz
+	if n == 0 {
+		return nil, nil
+	}
+	res := make([]bls12381.GT, n)
+	st := make([]byte, n)
+	chk := 0
+	if subgroupCheck {
+		chk = 1
+	}
+	check(func() C.int {
+		return C.mlhip_gt_from_bytes(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&raw[0]), C.size_t(n), C.int(chk),
+			unsafe.Pointer(&res[0]), (*C.uchar)(unsafe.Pointer(&st[0])))
+	})
+	out := make([]driver.Gt, n)
+	for i := range res {
+		out[i] = &gurvy381.Gt{GT: res[i]}
+	}
+	return out, st
+}
+
+// gtValues copies the values behind a slice of driver.Gt
+func gtValues(gts []driver.Gt) []bls12381.GT {
+	in := make([]bls12381.GT, len(gts))
+	for i := range gts {
+		in[i] = gts[i].(*gurvy381.Gt).GT
+	}
+	return in
+}
+
+// GtBytesBatch is Gt.Bytes of every value in one call (mlhip_gt_to_bytes): n x 576 bytes.
+func (c *Curve) GtBytesBatch(gts []driver.Gt) []byte {
+	n := len(gts)
+	if n == 0 {
+		return nil
+	}
+	in := gtValues(gts)
+	out := make([]byte, n*bls12381.SizeOfGT)
+	check(func() C.int {
+		return C.mlhip_gt_to_bytes(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&in[0]), C.size_t(n), unsafe.Pointer(&out[0]))
+	})
+	return out
+}
+
+// IsInSubGroupBatch reports for every value whether it is a member of Gt (gnark's GT.IsInSubGroup; mlhip_gt_is_member):
+// what ExpBatchGt asks its caller to know about a value that arrived as bytes or from another party.
+func (c *Curve) IsInSubGroupBatch(gts []driver.Gt) []bool {
+	n := len(gts)
+	if n == 0 {
+		return nil
+	}
+	in := gtValues(gts)
+	st := make([]byte, n)
+	check(func() C.int {
+		return C.mlhip_gt_is_member(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&in[0]), C.size_t(n), (*C.uchar)(unsafe.Pointer(&st[0])))
+	})
+	out := make([]bool, n)
+	for i := range st {
+		out[i] = st[i] == 0
+	}
+	return out
+}
+
+// InverseBatch is Gt.Inverse of every value in one call, not in place (mlhip_gt_inverse; bls12-381.go:413-415).  Any Fp12
+// value is accepted, as by gnark's E12.Inverse; the inverse of 0 is 0.
+func (c *Curve) InverseBatch(gts []driver.Gt) []driver.Gt {
+	n := len(gts)
+	if n == 0 {
+		return nil
+	}
+	in := gtValues(gts)
+	res := make([]bls12381.GT, n)
+	check(func() C.int {
+		return C.mlhip_gt_inverse(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&in[0]), C.size_t(n), unsafe.Pointer(&res[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range res {
+		out[i] = &gurvy381.Gt{GT: res[i]}
+	}
+	return out
+}
+
+// Inverse replaces g by its inverse on the device: Gt.Inverse (bls12-381.go:413-415) for a value of this curve.
+func (c *Curve) Inverse(g driver.Gt) {
+	v := g.(*gurvy381.Gt)
+	check(func() C.int {
+		res := v.GT
+		rc := C.mlhip_gt_inverse(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&v.GT), 1, unsafe.Pointer(&res))
+		v.GT = res
+		return rc
+	})
+}
+
 // NewG1sFromCompressed decodes n compressed G1 points (the wire form of G1.Compressed, bls12-381.go:292-296)
 // on the device: decompression, curve check and subgroup check per point.  It is the bulk form of
 // NewG1FromCompressed (bls12-381.go:551-559) and panics like it on the first invalid encoding, with gnark's

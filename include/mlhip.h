@@ -123,14 +123,18 @@ MLHIP_API int mlhip_final_exp(int curve, const void* in_gt, size_t n, void* out_
 MLHIP_API int mlhip_pairing_batch(int curve, const void* g1, const void* g2, size_t n, void* out_gt);
 /* out[i] = a[i] * b[i] in Gt (Gt.Mul, driver/gurvy/bls12381/bls12-381.go:417-419), element-wise over n */
 MLHIP_API int mlhip_gt_mul(int curve, const void* a_gt, const void* b_gt, size_t n, void* out_gt);
+/* out[i] = 1 / in[i] in Fp12 (Gt.Inverse, driver/gurvy/bls12381/bls12-381.go:413-415), element-wise over n: any Fp12 value, as
+ * gnark's E12.Inverse, not only members of Gt; the inverse of 0 is 0.  curve_id is a MLHIP_CURVE_* value. */
+MLHIP_API int mlhip_gt_inverse(int curve_id, const void* in_gt, size_t n, void* out_gt);
 
 /* out[i] = in[i]^(scalars[i]) in Gt (Gt.Exp, driver/gurvy/bls12381/bls12-381.go:399-407), element-wise over n;
  * valid for any Gt value.  Scalars as for the MSM entry points. */
 MLHIP_API int mlhip_gt_exp(int curve, const void* in_gt, const void* scalars, int scalars_mont, size_t n, void* out_gt);
 /* out[i] = in[i]^(scalars[i]) for in[i] in Gt (the subgroup of order r): same bytes as mlhip_gt_exp on such inputs, in a
  * fraction of the time -- cyclotomic squarings and a split of the scalar over the Frobenius map.
- * The caller PROMISES membership (FExp outputs, GenGt, products / powers of members; 1 is a member).  An input outside Gt
- * gives an undefined RESULT, never a fault.  curve_id is a MLHIP_CURVE_* value; scalars as for mlhip_gt_exp (scalars_mont, any
+ * The caller PROMISES membership (FExp outputs, GenGt, products / powers of members; 1 is a member); for a value that arrived
+ * as bytes or from another party, mlhip_gt_is_member (or mlhip_gt_from_bytes with the check) earns the promise.  An input
+ * outside Gt gives an undefined RESULT, never a fault.  curve_id is a MLHIP_CURVE_* value; scalars as for mlhip_gt_exp (scalars_mont, any
  * 256-bit value, reduced mod r). */
 MLHIP_API int mlhip_gt_exp_cyclo(int curve_id, const void* in_gt, const void* scalars, int scalars_mont, size_t n, void* out_gt);
 /* out = FExp( prod_i MillerLoop(g1[i], g2[i]) ): a multi-pairing product with ONE shared final exponentiation
@@ -193,6 +197,7 @@ MLHIP_API int mlhip_final_exp_device(int curve, const void* d_in_gt, size_t n, v
 MLHIP_API int mlhip_pairing_batch_device(int curve, const void* d_g1, const void* d_g2, size_t n, void* d_out_gt,
                                void* stream);
 MLHIP_API int mlhip_gt_mul_device(int curve, const void* d_a_gt, const void* d_b_gt, size_t n, void* d_out_gt, void* stream);
+MLHIP_API int mlhip_gt_inverse_device(int curve_id, const void* d_in_gt, size_t n, void* d_out_gt, void* stream);
 MLHIP_API int mlhip_gt_exp_device(int curve, const void* d_in_gt, const void* d_scalars, int scalars_mont, size_t n,
                         void* d_out_gt, void* stream);
 MLHIP_API int mlhip_gt_exp_cyclo_device(int curve_id, const void* d_in_gt, const void* d_scalars, int scalars_mont, size_t n,
@@ -369,6 +374,24 @@ MLHIP_API int mlhip_g2_to_bytes(int curve, const void* affine, size_t n, int com
 MLHIP_API int mlhip_g2_from_bytes_device(int curve, const void* d_wire, size_t n, int compressed, int subgroup_check,
                                void* d_out_affine, unsigned char* d_status, void* stream);
 MLHIP_API int mlhip_g2_to_bytes_device(int curve, const void* d_affine, size_t n, int compressed, void* d_wire, void* stream);
+/* Gt (NewGtFromBytes, driver/gurvy/bls12381/bls12-381.go:571-579; Gt.Bytes, :432-436): gnark's GT.Bytes() -- 12 fp-sized
+ * big-endian values per element in the order C1.B2.A1, C1.B2.A0, ..., C0.B0.A0 (always 12 x fp bytes; there is no compressed
+ * form).  Status byte per element, the codes of the point decoders: 0 ok | 1 malformed (a coordinate >= p) | 3 not in Gt; 2 is
+ * never returned for Gt.  Malformed takes precedence; out_gt[i] is all zero unless status[i] == 0.  subgroup_check: 0 only
+ * decodes, as gnark's SetBytes does (status 0 or 1); 1 also runs the membership test of mlhip_gt_is_member.  curve_id is a
+ * MLHIP_CURVE_* value. */
+MLHIP_API int mlhip_gt_from_bytes(int curve_id, const void* wire, size_t n, int subgroup_check, void* out_gt, unsigned char* status);
+MLHIP_API int mlhip_gt_to_bytes(int curve_id, const void* gt, size_t n, void* wire);
+MLHIP_API int mlhip_gt_from_bytes_device(int curve_id, const void* d_wire, size_t n, int subgroup_check, void* d_out_gt,
+                                         unsigned char* d_status, void* stream);
+MLHIP_API int mlhip_gt_to_bytes_device(int curve_id, const void* d_gt, size_t n, void* d_wire, void* stream);
+/* status[i] = 0 if gt[i] (in-memory layout) lies in Gt, the subgroup of order r of Fp12* -- exactly: 0 iff gt[i]^r = 1 --
+ * and 3 otherwise (gnark's GT.IsInSubGroup; the counterpart of the subgroup checks of the point decoders).  The test:
+ * gt != 0, frob^2(frob^2(f)) f = frob^2(f) (the cyclotomic subgroup) and frob(f) = f^x (BLS12) / f^(6 x^2) (BN254) by
+ * cyclotomic squarings; any Fp12 value gives a status, never a fault.  A value that passes may be
+ * handed to mlhip_gt_exp_cyclo. */
+MLHIP_API int mlhip_gt_is_member(int curve_id, const void* gt, size_t n, unsigned char* status);
+MLHIP_API int mlhip_gt_is_member_device(int curve_id, const void* d_gt, size_t n, unsigned char* d_status, void* stream);
 
 /* ---- group helpers (host, O(n) tiny): combine per-GPU partial results after the RCCL all-gather */
 MLHIP_API int mlhip_g1_sum(int curve, const void* affine_points, size_t n, void* out_affine);

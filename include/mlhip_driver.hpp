@@ -16,7 +16,8 @@
 //   Curve::FExp(gt)                      driver/math.go:56-57                         -> mlhip_final_exp
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
-//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt,
+//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
+//   IsInSubGroupBatch, InverseBatch,
 //             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch
 #pragma once
 #include <array>
@@ -233,6 +234,7 @@ class Gt {
   const Curve* curve = nullptr;
   bool Equals(const Gt& o) const { return raw == o.raw; }
   void Mul(const Gt& o);
+  void Inverse();  // in place, as Mul; any Fp12 value, the inverse of 0 is 0 (bls12-381.go:413-415)
   Gt Exp(const Zr& x) const;
   bool IsUnity() const;
   Bytes ToBytes() const;  // gnark GT.Bytes(): 12 big-endian Fp, C1.B2.A1 first
@@ -343,6 +345,66 @@ class Curve {
     check(mlhip_g2_from_bytes(id, b.data(), 1, compressed ? 1 : 0, 1, g.raw.data(), &st));
     if (st) throw std::invalid_argument(std::string("set bytes failed [status ") + std::to_string((int)st) + "]");
     return g;
+  }
+  // NewGtFromBytes (bls12-381.go:571-579): gnark's GT.SetBytes -- decoded without the subgroup check; a coordinate >= p throws
+  Gt NewGtFromBytes(const Bytes& b) const {
+    std::vector<unsigned char> st;
+    std::vector<Gt> g = NewGtFromBytesBatch({b}, st, false);
+    if (st[0]) throw std::invalid_argument("set bytes failed [invalid fp.Element encoding]");
+    return g[0];
+  }
+  // n encodings in one call (mlhip_gt_from_bytes): statuses[i] = 0 ok, 1 malformed, 3 not in Gt (with the check only); a value
+  // whose status is not 0 is all zero
+  std::vector<Gt> NewGtFromBytesBatch(const std::vector<Bytes>& blobs, std::vector<unsigned char>& statuses,
+                                      bool subgroup_check = true) const {
+    Bytes in, o(gt_bytes * blobs.size());
+    for (auto& b : blobs) {
+      if (b.size() != gt_bytes) throw std::invalid_argument("set bytes failed [invalid length]");
+      in.insert(in.end(), b.begin(), b.end());
+    }
+    statuses.assign(blobs.size(), 0);
+    if (!blobs.empty()) check(mlhip_gt_from_bytes(id, in.data(), blobs.size(), subgroup_check ? 1 : 0, o.data(), statuses.data()));
+    return unpack_gts(o, blobs.size());
+  }
+  // Gt.Bytes of every value in one call (mlhip_gt_to_bytes)
+  std::vector<Bytes> GtBytesBatch(const std::vector<Gt>& gts) const {
+    std::vector<Bytes> out;
+    if (gts.empty()) return out;
+    Bytes in = pack_gts(gts), o(gt_bytes * gts.size());
+    check(mlhip_gt_to_bytes(id, in.data(), gts.size(), o.data()));
+    for (size_t i = 0; i < gts.size(); i++) out.emplace_back(o.begin() + i * gt_bytes, o.begin() + (i + 1) * gt_bytes);
+    return out;
+  }
+  // is each value a member of Gt (order r)?  What ExpBatchGt asks its caller to know (mlhip_gt_is_member)
+  std::vector<bool> IsInSubGroupBatch(const std::vector<Gt>& gts) const {
+    std::vector<bool> out;
+    if (gts.empty()) return out;
+    Bytes in = pack_gts(gts);
+    std::vector<unsigned char> st(gts.size());
+    check(mlhip_gt_is_member(id, in.data(), gts.size(), st.data()));
+    for (unsigned char b : st) out.push_back(b == 0);
+    return out;
+  }
+  // Gt.Inverse of every value in one call, not in place (mlhip_gt_inverse)
+  std::vector<Gt> InverseBatch(const std::vector<Gt>& gts) const {
+    if (gts.empty()) return {};
+    Bytes in = pack_gts(gts), o(gt_bytes * gts.size());
+    check(mlhip_gt_inverse(id, in.data(), gts.size(), o.data()));
+    return unpack_gts(o, gts.size());
+  }
+  Bytes pack_gts(const std::vector<Gt>& gts) const {
+    Bytes in;
+    for (auto& g : gts) in.insert(in.end(), g.raw.begin(), g.raw.end());
+    return in;
+  }
+  std::vector<Gt> unpack_gts(const Bytes& o, size_t n) const {
+    std::vector<Gt> out;
+    for (size_t i = 0; i < n; i++) {
+      Gt g = new_gt();
+      memcpy(g.raw.data(), o.data() + i * gt_bytes, gt_bytes);
+      out.push_back(g);
+    }
+    return out;
   }
   G2 NewG2FromBytes(const Bytes& b) const { return g2_from_wire(b, false); }       // bls12-381.go:541-549
   G2 NewG2FromCompressed(const Bytes& b) const { return g2_from_wire(b, true); }  // bls12-381.go:561-569
@@ -886,6 +948,11 @@ inline void G2::Add(const G2& o) {
 inline void Gt::Mul(const Gt& o) {
   Bytes out(curve->gt_bytes);
   check(mlhip_gt_mul(curve->id, raw.data(), o.raw.data(), 1, out.data()));
+  raw = out;
+}
+inline void Gt::Inverse() {
+  Bytes out(curve->gt_bytes);
+  check(mlhip_gt_inverse(curve->id, raw.data(), 1, out.data()));
   raw = out;
 }
 inline Gt Gt::Exp(const Zr& x) const {

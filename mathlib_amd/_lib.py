@@ -55,6 +55,14 @@ SYMBOLS = [
     "mlhip_gt_mul_device",
     "mlhip_gt_exp_device",
     "mlhip_gt_exp_cyclo_device",
+    "mlhip_gt_from_bytes",
+    "mlhip_gt_to_bytes",
+    "mlhip_gt_from_bytes_device",
+    "mlhip_gt_to_bytes_device",
+    "mlhip_gt_is_member",
+    "mlhip_gt_is_member_device",
+    "mlhip_gt_inverse",
+    "mlhip_gt_inverse_device",
     "mlhip_scalar_mul_device",
     "mlhip_scalar_mul",
     "mlhip_msm_batch_device",
@@ -192,6 +200,14 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.mlhip_pairing_product.argtypes = [ci, vp, vp, sz, vp]
     lib.mlhip_gt_exp_device.argtypes = [ci, vp, vp, ci, sz, vp, vp]
     lib.mlhip_gt_exp_cyclo_device.argtypes = [ci, vp, vp, ci, sz, vp, vp]
+    lib.mlhip_gt_from_bytes.argtypes = [ci, vp, sz, ci, vp, vp]
+    lib.mlhip_gt_to_bytes.argtypes = [ci, vp, sz, vp]
+    lib.mlhip_gt_from_bytes_device.argtypes = [ci, vp, sz, ci, vp, vp, vp]
+    lib.mlhip_gt_to_bytes_device.argtypes = [ci, vp, sz, vp, vp]
+    lib.mlhip_gt_is_member.argtypes = [ci, vp, sz, vp]
+    lib.mlhip_gt_is_member_device.argtypes = [ci, vp, sz, vp, vp]
+    lib.mlhip_gt_inverse.argtypes = [ci, vp, sz, vp]
+    lib.mlhip_gt_inverse_device.argtypes = [ci, vp, sz, vp, vp]
     lib.mlhip_msm_plan_create.argtypes = [ci, ci, sz, ci, POINTER(vp)]
     lib.mlhip_msm_plan_destroy.argtypes = [vp]
     lib.mlhip_msm_run.argtypes = [vp, vp, vp, ci, sz, vp, vp, vp]

@@ -298,6 +298,119 @@ int mlhip_gt_exp_cyclo(int curve, const void* in, const void* scalars, int mont,
   return hc.down(out, dout, n * ops->gt);
 }
 
+// ---- Gt wire codec, membership test and inverse (gt_codec.h).  Every form checks its arguments before it looks for a device.
+int mlhip_gt_from_bytes_device(int curve, const void* d_wire, size_t n, int subgroup_check, void* d_out, unsigned char* d_status,
+                               void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!d_wire || !d_out || !d_status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  return ops->gt_decode(d_wire, n, subgroup_check ? 1 : 0, d_out, d_status, (hipStream_t)stream);
+}
+
+int mlhip_gt_from_bytes(int curve, const void* wire, size_t n, int subgroup_check, void* out, unsigned char* status) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!wire || !out || !status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(2 * n * ops->gt + n);
+  void* dw = hc.up(wire, n * ops->gt);
+  void* dout = hc.dev(n * ops->gt);
+  void* dst = hc.dev(n);
+  if (hc.rc) return hc.rc;
+  rc = ops->gt_decode(dw, n, subgroup_check ? 1 : 0, dout, dst, hc.l.st);
+  if (rc) return rc;
+  if (hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, hc.l.st) != hipSuccess)
+    return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy D2H failed");
+  return hc.down(out, dout, n * ops->gt);
+}
+
+int mlhip_gt_to_bytes_device(int curve, const void* d_gt, size_t n, void* d_wire, void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!d_gt || !d_wire) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  return ops->gt_encode(d_gt, n, d_wire, (hipStream_t)stream);
+}
+
+int mlhip_gt_to_bytes(int curve, const void* gt, size_t n, void* wire) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!gt || !wire) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(2 * n * ops->gt);
+  void* din = hc.up(gt, n * ops->gt);
+  void* dw = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = ops->gt_encode(din, n, dw, hc.l.st);
+  if (rc) return rc;
+  return hc.down(wire, dw, n * ops->gt);
+}
+
+int mlhip_gt_is_member_device(int curve, const void* d_gt, size_t n, unsigned char* d_status, void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!d_gt || !d_status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  return ops->gt_is_member(d_gt, n, d_status, nullptr, (hipStream_t)stream);
+}
+
+int mlhip_gt_is_member(int curve, const void* gt, size_t n, unsigned char* status) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!gt || !status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(n * ops->gt + n);
+  void* din = hc.up(gt, n * ops->gt);
+  void* dst = hc.dev(n);
+  if (hc.rc) return hc.rc;
+  rc = ops->gt_is_member(din, n, dst, nullptr, hc.l.st);
+  if (rc) return rc;
+  return hc.down(status, dst, n);
+}
+
+int mlhip_gt_inverse_device(int curve, const void* d_in, size_t n, void* d_out, void* stream) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!d_in || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  return ops->gt_inverse(d_in, n, d_out, (hipStream_t)stream);
+}
+
+int mlhip_gt_inverse(int curve, const void* in, size_t n, void* out) {
+  const CurveOps* ops = curve_ops(curve);
+  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (n == 0) return 0;
+  if (!in || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  int rc = ensure_device();
+  if (rc) return rc;
+  HostCall hc;
+  hc.reserve(2 * n * ops->gt);
+  void* din = hc.up(in, n * ops->gt);
+  void* dout = hc.dev(n * ops->gt);
+  if (hc.rc) return hc.rc;
+  rc = ops->gt_inverse(din, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, n * ops->gt);
+}
+
 int mlhip_pairing_product(int curve, const void* g1, const void* g2, size_t n, void* out) {
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");

@@ -104,6 +104,11 @@ struct GtOpsLp {
   static MLHIP_HD void frob(T& r, const T& a) {
     fp12_frob<C, K>(r, a);
   }
+  // what the membership test and Gt.Inverse add (gt_codec.h): the inverse of any Fp12 value, the Fp2 coefficients as an
+  // array, and how many lanes share one value on the device (a verdict is combined over them)
+  static MLHIP_HD void inv(T& r, const T& a) { fp12_inv<C>(r, a); }
+  static constexpr int COEFFS = 6, DEVICE_LANES = 2;
+  static MLHIP_HD const E* coeffs(const T& a) { return &a.c0.c0; }
 };
 // quads (pairing_quad.h): pair A holds the c0 half, pair B the c1 half
 template <class C, class E>
@@ -117,6 +122,9 @@ struct GtOpsQ {
   static MLHIP_HD void frob(T& r, const T& a) {
     fp12q_frob<C, K>(r, a);
   }
+  static MLHIP_HD void inv(T& r, const T& a) { fp12q_inv<C>(r, a); }
+  static constexpr int COEFFS = 3, DEVICE_LANES = 4;
+  static MLHIP_HD const E* coeffs(const T& a) { return &a.v.c0; }
 };
 
 // acc = tab[0]^s for tab[0] in Gt, dig = gt_exp_split(s).  tab[1 .. 14] are scratch: the table has the footprint of the

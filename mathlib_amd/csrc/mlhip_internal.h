@@ -160,6 +160,11 @@ struct mlhip_g2_prepared_tables {
   X(C, int, gt_exp, (const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st))           \
   /* the same for inputs the caller promises to lie in Gt (gt_exp_cyclo.h) */                                            \
   X(C, int, gt_exp_cyclo, (const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st))     \
+  /* Gt wire codec, membership test and inverse (gt_codec.h); d_decoded: null, or the values to zero where the test fails */ \
+  X(C, int, gt_decode, (const void* d_wire, size_t n, int subgroup_check, void* d_out, void* d_status, hipStream_t st))   \
+  X(C, int, gt_encode, (const void* d_in, size_t n, void* d_wire, hipStream_t st))                                        \
+  X(C, int, gt_is_member, (const void* d_in, size_t n, void* d_status, void* d_decoded, hipStream_t st))                  \
+  X(C, int, gt_inverse, (const void* d_in, size_t n, void* d_out, hipStream_t st))                                        \
   X(C, int, wire_codec,                                                                                                   \
     (int group, int encode, const void* d_in, size_t n, int compressed, int subgroup, void* d_out, void* d_status,        \
      hipStream_t st))                                                                                                     \

@@ -758,3 +758,6 @@ int fp_mul_device(const void* d_a, const void* d_b, size_t n, int repeat, void* 
 }
 
 }  // namespace mlhip
+
+// the Gt wire codec, the membership test and Gt.Inverse: kernels over the load / store helpers above
+#include "gt_codec.h"

@@ -19,6 +19,18 @@ int MLHIP_TU_FN(gt_exp)(const void* d_in, const void* d_scalars, int mont, size_
 int MLHIP_TU_FN(gt_exp_cyclo)(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
   return gt_exp_cyclo_device<MLHIP_TU_CURVE>(d_in, d_scalars, mont, n, d_out, st);
 }
+int MLHIP_TU_FN(gt_decode)(const void* d_wire, size_t n, int subgroup_check, void* d_out, void* d_status, hipStream_t st) {
+  return gt_decode_device<MLHIP_TU_CURVE>(d_wire, n, subgroup_check, d_out, d_status, st);
+}
+int MLHIP_TU_FN(gt_encode)(const void* d_in, size_t n, void* d_wire, hipStream_t st) {
+  return gt_encode_device<MLHIP_TU_CURVE>(d_in, n, d_wire, st);
+}
+int MLHIP_TU_FN(gt_is_member)(const void* d_in, size_t n, void* d_status, void* d_decoded, hipStream_t st) {
+  return gt_is_member_device<MLHIP_TU_CURVE>(d_in, n, d_status, d_decoded, st);
+}
+int MLHIP_TU_FN(gt_inverse)(const void* d_in, size_t n, void* d_out, hipStream_t st) {
+  return gt_inverse_device<MLHIP_TU_CURVE>(d_in, n, d_out, st);
+}
 int MLHIP_TU_FN(g2_prepared)(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
                             size_t n, void* d_out, hipStream_t st) {
   if (what < 0) return g2_prepared_build<MLHIP_TU_CURVE>(t, st);

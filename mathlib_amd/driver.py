@@ -261,6 +261,12 @@ class Gt(_Element):
         check(load().mlhip_gt_exp(c.id, self.raw, x.le_bytes(c.scalars_mont), 1 if c.scalars_mont else 0, 1, out))
         return Gt(out.raw, c)
 
+    def Inverse(self) -> None:
+        """in place, as Mul; any Fp12 value, the inverse of 0 is 0 (bls12-381.go:413-415)"""
+        out = ctypes.create_string_buffer(self.curve.gt_bytes)
+        check(load().mlhip_gt_inverse(self.curve.id, self.raw, 1, out))
+        self.raw = out.raw
+
     def IsUnity(self) -> bool:
         return self.raw == self.curve._gt_one
 
@@ -331,6 +337,53 @@ class Curve:
     def NewG2FromCompressed(self, b: bytes) -> G2:
         """bls12-381.go:561-569"""
         return self._from_wire(2, b, True)
+
+    def NewGtFromBytes(self, b: bytes) -> Gt:
+        """gnark's GT.SetBytes: decoded without the subgroup check, a coordinate >= p raises (bls12-381.go:571-579)"""
+        gts, st = self.NewGtFromBytesBatch([b], subgroup_check=False)
+        if st[0]:
+            raise ValueError("set bytes failed [invalid fp.Element encoding]")
+        return gts[0]
+
+    def NewGtFromBytesBatch(self, blobs: Sequence[bytes], subgroup_check: bool = True):
+        """(values, statuses) of len(blobs) encodings in one call (mlhip_gt_from_bytes): status 0 ok, 1 malformed, 3 not in Gt
+        (with the check only); a value whose status is not 0 is all zero"""
+        n = len(blobs)
+        if any(len(b) != self.gt_bytes for b in blobs):
+            raise ValueError("set bytes failed [invalid length]")
+        if n == 0:
+            return [], []
+        out = ctypes.create_string_buffer(self.gt_bytes * n)
+        st = ctypes.create_string_buffer(n)
+        check(load().mlhip_gt_from_bytes(self.id, b"".join(bytes(b) for b in blobs), n, 1 if subgroup_check else 0, out, st))
+        return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)], list(st.raw)
+
+    def GtBytesBatch(self, gts: Sequence[Gt]) -> List[bytes]:
+        """Gt.Bytes of every value in one call (mlhip_gt_to_bytes)"""
+        n = len(gts)
+        if n == 0:
+            return []
+        out = ctypes.create_string_buffer(self.gt_bytes * n)
+        check(load().mlhip_gt_to_bytes(self.id, b"".join(g.raw for g in gts), n, out))
+        return [out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes] for i in range(n)]
+
+    def IsInSubGroupBatch(self, gts: Sequence[Gt]) -> List[bool]:
+        """is each value a member of Gt (order r)?  What ExpBatchGt asks its caller to know (mlhip_gt_is_member)"""
+        n = len(gts)
+        if n == 0:
+            return []
+        st = ctypes.create_string_buffer(n)
+        check(load().mlhip_gt_is_member(self.id, b"".join(g.raw for g in gts), n, st))
+        return [b == 0 for b in st.raw]
+
+    def InverseBatch(self, gts: Sequence[Gt]) -> List[Gt]:
+        """Gt.Inverse of every value in one call, not in place (mlhip_gt_inverse)"""
+        n = len(gts)
+        if n == 0:
+            return []
+        out = ctypes.create_string_buffer(self.gt_bytes * n)
+        check(load().mlhip_gt_inverse(self.id, b"".join(g.raw for g in gts), n, out))
+        return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
 
     def NewG1FromBytes(self, b: bytes) -> G1:
         """uncompressed wire form, subgroup-checked (driver/gurvy/bls12381/bls12-381.go:531-539)"""
