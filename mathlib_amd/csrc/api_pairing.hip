@@ -1,6 +1,7 @@
 // api_pairing.hip -- the pairing, Gt and prepared-G2 entry points of include/mlhip.h (and the field-multiplication probe):
 // argument checking, host-buffer staging and dispatch.  No kernels here.
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -9,50 +10,99 @@
 using namespace mlhip_rt;
 
 namespace {
-// host-buffer wrapper around the pairing kernels: upload, run, download
-int pairing_host(int curve, int what, const void* g1, const void* g2, size_t ppp, size_t n, const void* in, void* out) {
+// ---- what every entry point with a curve id begins with --------------------------------------------------------------------
+// The ops row of the curve, or null with `rc` the status to return at once (0: n == 0, nothing to do).  The ORDER of the
+// checks is behaviour (a machine without a device tells the orders apart; tests/test_gt_api_status_host.py):
+//   ARGS_THEN_DEVICE  curve, n == 0, null pointers, the device: the host forms and the newer _device forms
+//   ARGS_ONLY         curve, n == 0, null pointers: pairing_host, which looks for the device after it has spread the batch
+//   DEVICE_N_CURVE    the device, n == 0, the curve, no pointer checks: mlhip_gt_mul_device, _gt_exp_device, _fp_mul_device
+//   DEVICE_CURVE      the device, the curve, no pointer checks: the three pairing _device forms (n == 0 is the launcher's)
+enum CheckOrder { ARGS_THEN_DEVICE, ARGS_ONLY, DEVICE_N_CURVE, DEVICE_CURVE };
+const CurveOps* begin_call(CheckOrder order, int curve, size_t n, bool any_null, int& rc) {
+  const bool device_first = order == DEVICE_N_CURVE || order == DEVICE_CURVE;
+  rc = device_first ? ensure_device() : 0;
+  if (rc || (order == DEVICE_N_CURVE && n == 0)) return nullptr;
   const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!out || (what == 1 ? !in : (!g1 || !g2))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  {
-    // independent per element: a large batch is split over the process's devices, no exchange at all
-    const std::vector<int> devs = spread_devices(n, true);
-    if (!devs.empty())
-      return run_on_devices(devs, n, [&](size_t, size_t lo, size_t hi) {
-        return pairing_host(curve, what, g1 ? (const char*)g1 + lo * ppp * ops->g1 : nullptr,
-                            g2 ? (const char*)g2 + lo * ppp * ops->g2 : nullptr, ppp, hi - lo,
-                            in ? (const char*)in + lo * ops->gt : nullptr, (char*)out + lo * ops->gt);
-      });
+  if (!ops) {
+    rc = mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+    return nullptr;
   }
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  void *d1 = nullptr, *d2 = nullptr, *din = nullptr;
-  if (what == 1) {
-    hc.reserve(2 * n * ops->gt);
-    din = hc.up(in, n * ops->gt);
-  } else {
-    hc.reserve(n * ppp * (ops->g1 + ops->g2) + n * ops->gt);
-    d1 = hc.up(g1, n * ppp * ops->g1);
-    d2 = hc.up(g2, n * ppp * ops->g2);
+  if (device_first) return ops;
+  if (n == 0) return nullptr;
+  if (any_null) {
+    rc = mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+    return nullptr;
   }
-  void* dout = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = ops->pairing(what, d1, d2, ppp, n, din, dout, hc.l.st);
-  if (rc) return rc;
-  return hc.down(out, dout, n * ops->gt);
+  if (order == ARGS_THEN_DEVICE) rc = ensure_device();
+  return rc ? nullptr : ops;
 }
 
+// ---- one host-buffer call on this thread's device: upload, run, download ---------------------------------------------------
+// n elements of `each` bytes behind every host pointer, at most MAX_BUFS pointers a list.  The arena is reserved for the sum
+// of the two lists, the inputs are uploaded and the outputs allocated in list order, run(d_in, d_out, stream) launches on the
+// device copies, and the outputs are brought back: all copies queued, one wait for the stream (HostCall::down) at the end.
+struct HostIn {
+  const void* p;
+  size_t each;
+};
+struct HostOut {
+  void* p;
+  size_t each;
+};
+constexpr size_t MAX_BUFS = 4;
+template <class Run>
+int staged_call(size_t n, std::initializer_list<HostIn> ins, std::initializer_list<HostOut> outs, Run run) {
+  if (ins.size() > MAX_BUFS || outs.size() > MAX_BUFS || outs.size() == 0) return mlhip_rt::fail(MLHIP_EINVAL, "internal: staged_call lists");
+  HostCall hc;
+  size_t total = 0;
+  for (const HostIn& b : ins) total += n * b.each;
+  for (const HostOut& b : outs) total += n * b.each;
+  hc.reserve(total);
+  void *din[MAX_BUFS] = {}, *dout[MAX_BUFS] = {};
+  size_t k = 0;
+  for (const HostIn& b : ins) din[k++] = hc.up(b.p, n * b.each);
+  k = 0;
+  for (const HostOut& b : outs) dout[k++] = hc.dev(n * b.each);
+  if (hc.rc) return hc.rc;
+  const int rc = run(din, dout, hc.l.st);
+  if (rc) return rc;
+  const HostOut* o = outs.begin();
+  for (k = 0; k + 1 < outs.size(); k++)
+    if (hipMemcpyAsync(o[k].p, dout[k], n * o[k].each, hipMemcpyDeviceToHost, hc.l.st) != hipSuccess)
+      return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy D2H failed");
+  return hc.down(o[k].p, dout[k], n * o[k].each);
+}
+
+// host-buffer wrapper around the pairing kernels
+int pairing_host(int curve, int what, const void* g1, const void* g2, size_t ppp, size_t n, const void* in, void* out) {
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_ONLY, curve, n, !out || (what == 1 ? !in : (!g1 || !g2)), rc);
+  if (!ops) return rc;
+  // independent per element: a large batch is split over the process's devices, no exchange at all
+  const std::vector<int> devs = spread_devices(n, true);
+  if (!devs.empty())
+    return run_on_devices(devs, n, [&](size_t, size_t lo, size_t hi) {
+      return pairing_host(curve, what, g1 ? (const char*)g1 + lo * ppp * ops->g1 : nullptr,
+                          g2 ? (const char*)g2 + lo * ppp * ops->g2 : nullptr, ppp, hi - lo,
+                          in ? (const char*)in + lo * ops->gt : nullptr, (char*)out + lo * ops->gt);
+    });
+  rc = ensure_device();
+  if (rc) return rc;
+  if (what == 1)
+    return staged_call(n, {{in, ops->gt}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+      return ops->pairing(what, nullptr, nullptr, ppp, n, d[0], o[0], st);
+    });
+  return staged_call(n, {{g1, ppp * ops->g1}, {g2, ppp * ops->g2}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->pairing(what, d[0], d[1], ppp, n, nullptr, o[0], st);
+  });
+}
 
 // the same on device pointers, in order on `stream`
 int pairing_device(int curve, int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out,
                    void* stream) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  return ops->pairing(what, d_g1, d_g2, ppp, n, d_in, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(DEVICE_CURVE, curve, n, false, rc);
+  return ops ? ops->pairing(what, d_g1, d_g2, ppp, n, d_in, d_out, (hipStream_t)stream) : rc;
 }
 }  // namespace
 
@@ -216,199 +266,112 @@ int mlhip_pairing_prepared_device(mlhip_g2_prepared* h, const void* d_g1, const 
 }
 
 int mlhip_gt_mul_device(int curve, const void* d_a, const void* d_b, size_t n, void* d_out, void* stream) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (n == 0) return 0;
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  return ops->gt_mul(d_a, d_b, n, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(DEVICE_N_CURVE, curve, n, false, rc);
+  return ops ? ops->gt_mul(d_a, d_b, n, d_out, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_mul(int curve, const void* a, const void* b, size_t n, void* out) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!a || !b || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(3 * n * ops->gt);
-  void* da = hc.up(a, n * ops->gt);
-  void* db = hc.up(b, n * ops->gt);
-  void* dout = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = mlhip_gt_mul_device(curve, da, db, n, dout, hc.l.st);
-  if (rc) return rc;
-  return hc.down(out, dout, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !a || !b || !out, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{a, ops->gt}, {b, ops->gt}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_mul(d[0], d[1], n, o[0], st);
+  });
 }
 
 int mlhip_gt_exp_device(int curve, const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, void* stream) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (n == 0) return 0;
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  return ops->gt_exp(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(DEVICE_N_CURVE, curve, n, false, rc);
+  return ops ? ops->gt_exp(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_exp(int curve, const void* in, const void* scalars, int mont, size_t n, void* out) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!in || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(2 * n * ops->gt + n * 32);
-  void* din = hc.up(in, n * ops->gt);
-  void* ds = hc.up(scalars, n * 32);
-  void* dout = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = mlhip_gt_exp_device(curve, din, ds, mont, n, dout, hc.l.st);
-  if (rc) return rc;
-  return hc.down(out, dout, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !in || !scalars || !out, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{in, ops->gt}, {scalars, 32}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_exp(d[0], d[1], mont, n, o[0], st);
+  });
 }
 
-// Gt.Exp for members of Gt (gt_exp_cyclo.h).  Both forms check their arguments before they look for a device.
+// Gt.Exp for members of Gt (gt_exp_cyclo.h)
 int mlhip_gt_exp_cyclo_device(int curve, const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, void* stream) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!d_in || !d_scalars || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  return ops->gt_exp_cyclo(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !d_in || !d_scalars || !d_out, rc);
+  return ops ? ops->gt_exp_cyclo(d_in, d_scalars, mont, n, d_out, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_exp_cyclo(int curve, const void* in, const void* scalars, int mont, size_t n, void* out) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!in || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(2 * n * ops->gt + n * 32);
-  void* din = hc.up(in, n * ops->gt);
-  void* ds = hc.up(scalars, n * 32);
-  void* dout = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = ops->gt_exp_cyclo(din, ds, mont, n, dout, hc.l.st);
-  if (rc) return rc;
-  return hc.down(out, dout, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !in || !scalars || !out, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{in, ops->gt}, {scalars, 32}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_exp_cyclo(d[0], d[1], mont, n, o[0], st);
+  });
 }
 
-// ---- Gt wire codec, membership test and inverse (gt_codec.h).  Every form checks its arguments before it looks for a device.
+// ---- Gt wire codec, membership test and inverse (gt_codec.h) ---------------------------------------------------------------
 int mlhip_gt_from_bytes_device(int curve, const void* d_wire, size_t n, int subgroup_check, void* d_out, unsigned char* d_status,
                                void* stream) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!d_wire || !d_out || !d_status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  return ops->gt_decode(d_wire, n, subgroup_check ? 1 : 0, d_out, d_status, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !d_wire || !d_out || !d_status, rc);
+  return ops ? ops->gt_decode(d_wire, n, subgroup_check ? 1 : 0, d_out, d_status, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_from_bytes(int curve, const void* wire, size_t n, int subgroup_check, void* out, unsigned char* status) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!wire || !out || !status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(2 * n * ops->gt + n);
-  void* dw = hc.up(wire, n * ops->gt);
-  void* dout = hc.dev(n * ops->gt);
-  void* dst = hc.dev(n);
-  if (hc.rc) return hc.rc;
-  rc = ops->gt_decode(dw, n, subgroup_check ? 1 : 0, dout, dst, hc.l.st);
-  if (rc) return rc;
-  if (hipMemcpyAsync(status, dst, n, hipMemcpyDeviceToHost, hc.l.st) != hipSuccess)
-    return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy D2H failed");
-  return hc.down(out, dout, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !wire || !out || !status, rc);
+  if (!ops) return rc;
+  // (the statuses first: their small copy is queued, the wait is for the values)
+  return staged_call(n, {{wire, ops->gt}}, {{status, 1}, {out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_decode(d[0], n, subgroup_check ? 1 : 0, o[1], o[0], st);
+  });
 }
 
 int mlhip_gt_to_bytes_device(int curve, const void* d_gt, size_t n, void* d_wire, void* stream) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!d_gt || !d_wire) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  return ops->gt_encode(d_gt, n, d_wire, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !d_gt || !d_wire, rc);
+  return ops ? ops->gt_encode(d_gt, n, d_wire, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_to_bytes(int curve, const void* gt, size_t n, void* wire) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!gt || !wire) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(2 * n * ops->gt);
-  void* din = hc.up(gt, n * ops->gt);
-  void* dw = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = ops->gt_encode(din, n, dw, hc.l.st);
-  if (rc) return rc;
-  return hc.down(wire, dw, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !gt || !wire, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{gt, ops->gt}}, {{wire, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_encode(d[0], n, o[0], st);
+  });
 }
 
 int mlhip_gt_is_member_device(int curve, const void* d_gt, size_t n, unsigned char* d_status, void* stream) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!d_gt || !d_status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  return ops->gt_is_member(d_gt, n, d_status, nullptr, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !d_gt || !d_status, rc);
+  return ops ? ops->gt_is_member(d_gt, n, d_status, nullptr, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_is_member(int curve, const void* gt, size_t n, unsigned char* status) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!gt || !status) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(n * ops->gt + n);
-  void* din = hc.up(gt, n * ops->gt);
-  void* dst = hc.dev(n);
-  if (hc.rc) return hc.rc;
-  rc = ops->gt_is_member(din, n, dst, nullptr, hc.l.st);
-  if (rc) return rc;
-  return hc.down(status, dst, n);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !gt || !status, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{gt, ops->gt}}, {{status, 1}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_is_member(d[0], n, o[0], nullptr, st);
+  });
 }
 
 int mlhip_gt_inverse_device(int curve, const void* d_in, size_t n, void* d_out, void* stream) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!d_in || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  return ops->gt_inverse(d_in, n, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !d_in || !d_out, rc);
+  return ops ? ops->gt_inverse(d_in, n, d_out, (hipStream_t)stream) : rc;
 }
 
 int mlhip_gt_inverse(int curve, const void* in, size_t n, void* out) {
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  if (n == 0) return 0;
-  if (!in || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int rc = ensure_device();
-  if (rc) return rc;
-  HostCall hc;
-  hc.reserve(2 * n * ops->gt);
-  void* din = hc.up(in, n * ops->gt);
-  void* dout = hc.dev(n * ops->gt);
-  if (hc.rc) return hc.rc;
-  rc = ops->gt_inverse(din, n, dout, hc.l.st);
-  if (rc) return rc;
-  return hc.down(out, dout, n * ops->gt);
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_THEN_DEVICE, curve, n, !in || !out, rc);
+  if (!ops) return rc;
+  return staged_call(n, {{in, ops->gt}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->gt_inverse(d[0], n, o[0], st);
+  });
 }
 
 int mlhip_pairing_product(int curve, const void* g1, const void* g2, size_t n, void* out) {
@@ -455,12 +418,9 @@ int mlhip_pairing_product(int curve, const void* g1, const void* g2, size_t n, v
 }
 
 int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, void* stream) {
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (n == 0) return 0;
-  const CurveOps* ops = curve_ops(curve);
-  if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  return ops->fp_mul(d_a, d_b, n, repeat, d_out, (hipStream_t)stream);
+  int rc;
+  const CurveOps* ops = begin_call(DEVICE_N_CURVE, curve, n, false, rc);
+  return ops ? ops->fp_mul(d_a, d_b, n, repeat, d_out, (hipStream_t)stream) : rc;
 }
 
 }  // extern "C"

@@ -154,36 +154,7 @@ __global__ void __launch_bounds__(GT_CODEC_BLOCK) k_gt_encode(const Fp<C>* __res
   fp_to_be<C>(wire + t * (size_t)(4 * C::N), v);
 }
 
-// ---- membership and inverse: one value per quad of lanes (QUAD) or per lane pair, the shapes, launch bounds and occupancy
-// cap of k_gt_exp_cyclo_*
-template <class C, bool QUAD>
-struct GtShape {
-  typedef Fp2L28<C> E2;
-  typedef typename std::conditional<QUAD, GtOpsQ<C, E2>, GtOpsLp<C, E2>>::type G;
-  typedef typename G::T T;
-  static constexpr int LANES = QUAD ? 4 : 2;
-  static __device__ __forceinline__ void load(T& f, const Fp12<C>* in, size_t i) {
-    if constexpr (QUAD)
-      q28_load_gt<C>(f, in, i);
-    else
-      lp28_load_gt<C>(f, in, i);
-  }
-  static __device__ __forceinline__ void store(Fp12<C>* out, size_t i, const T& f) {
-    if constexpr (QUAD)
-      q28_store_gt<C>(out, i, f);
-    else
-      lp28_store_gt<C>(out, i, f);
-  }
-  static __device__ __forceinline__ void zero(T& f) {
-    if constexpr (QUAD) {
-      fp6_zero<C>(f.v);
-    } else {
-      fp6_zero<C>(f.c0);
-      fp6_zero<C>(f.c1);
-    }
-  }
-};
-
+// ---- membership and inverse over GtShape (pairing_kernels.h), launched by gt_launch
 // status[i] = in[i] in Gt ? 0 : 3.  With `decoded` (the second launch of a checking mlhip_gt_from_bytes: in == decoded) a
 // status the decoder set stays, and a value that fails the test is overwritten with zeros.
 template <class C, bool QUAD>
@@ -219,32 +190,15 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_inverse(const Fp12<C>* i
   S::store(out, i, r);
 }
 
-// quads unless MLHIP_PAIRING_QUAD=0, at every size, as gt_exp_cyclo_device
-inline bool gt_codec_quads() {
-  const char* qe = getenv("MLHIP_PAIRING_QUAD");
-  return !(qe && qe[0] == '0');
-}
-
 template <class C>
 int gt_is_member_device(const void* d_in, size_t n, void* d_status, void* d_decoded, hipStream_t st) {
-  if (gt_codec_quads())
-    k_gt_member<C, true><<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, n, (uint8_t*)d_status,
-                                                                                (Fp12<C>*)d_decoded);
-  else
-    k_gt_member<C, false><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, n, (uint8_t*)d_status,
-                                                                                 (Fp12<C>*)d_decoded);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return gt_launch<C>(k_gt_member<C, true>, k_gt_member<C, false>, n, st, (const Fp12<C>*)d_in, n, (uint8_t*)d_status,
+                      (Fp12<C>*)d_decoded);
 }
 
 template <class C>
 int gt_inverse_device(const void* d_in, size_t n, void* d_out, hipStream_t st) {
-  if (gt_codec_quads())
-    k_gt_inverse<C, true><<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, n, (Fp12<C>*)d_out);
-  else
-    k_gt_inverse<C, false><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, n, (Fp12<C>*)d_out);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return gt_launch<C>(k_gt_inverse<C, true>, k_gt_inverse<C, false>, n, st, (const Fp12<C>*)d_in, n, (Fp12<C>*)d_out);
 }
 
 // decode, then -- with the check -- the membership kernel over the decoded values on the same stream (two launches: the

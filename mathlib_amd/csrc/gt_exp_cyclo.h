@@ -1,5 +1,6 @@
-// gt_exp_cyclo.h -- Gt.Exp for MEMBERS of Gt (the subgroup of order r of Fp12*): the scalar split and the chain behind
-// mlhip_gt_exp_cyclo.  Included by pairing_kernels.h; host-testable (tests/hostmath_gtexp).
+// gt_exp_cyclo.h -- the chains of Gt.Exp over the two shapes of a Gt value (GtOpsLp, GtOpsQ): the 4-bit windowed chain behind
+// mlhip_gt_exp, valid for any Fp12 value, and, for MEMBERS of Gt (the subgroup of order r of Fp12*), the scalar split and the
+// chain behind mlhip_gt_exp_cyclo.  Included by pairing_kernels.h; host-testable (tests/hostmath_gtexp).
 //
 // On Gt the Frobenius map f -> f^p is exponentiation by p mod r, and members of Gt lie in the cyclotomic subgroup, where a
 // squaring is the Granger-Scott one (nine Fp2 squarings) and the inverse is the conjugate.  So f^s is computed as
@@ -98,6 +99,7 @@ struct GtOpsLp {
   typedef Fp12<C, E> T;
   static MLHIP_HD void one(T& r) { fp12_one<C>(r); }
   static MLHIP_HD void mul(T& r, const T& a, const T& b) { fp12_mul<C>(r, a, b); }
+  static MLHIP_HD void sqr(T& r, const T& a) { fp12_sqr<C>(r, a); }
   static MLHIP_HD void cyclo_sqr(T& r, const T& a) { fp12_cyclo_sqr<C>(r, a); }
   static MLHIP_HD void conj(T& r, const T& a) { fp12_conj<C>(r, a); }
   template <int K>
@@ -116,6 +118,7 @@ struct GtOpsQ {
   typedef Fp12Q<C, E> T;
   static MLHIP_HD void one(T& r) { fp12q_one<C>(r); }
   static MLHIP_HD void mul(T& r, const T& a, const T& b) { fp12q_mul<C>(r, a, b); }
+  static MLHIP_HD void sqr(T& r, const T& a) { fp12q_sqr<C>(r, a); }
   static MLHIP_HD void cyclo_sqr(T& r, const T& a) { fp12q_cyclo_sqr<C>(r, a); }
   static MLHIP_HD void conj(T& r, const T& a) { fp12q_conj<C>(r, a); }
   template <int K>
@@ -126,6 +129,35 @@ struct GtOpsQ {
   static constexpr int COEFFS = 3, DEVICE_LANES = 4;
   static MLHIP_HD const E* coeffs(const T& a) { return &a.v.c0; }
 };
+
+// acc = tab[0]^s for ANY Fp12 value tab[0] (raw Miller-loop outputs included, like gnark's GT.Exp) and s < 2^256: 4-bit
+// fixed windows.  tab[1 .. 14] become base^2 .. base^15 (in scratch on the device: 4.3 KB per lane, one 288-byte read per
+// window), then 4 generic squarings and at most one product per window -- 255 squarings + <= 78 products instead of ~128.
+// `acc` is a reference so that a kernel can keep it where it likes (k_gt_exp_lp: an LDS slot).  Every branch depends on the
+// scalar only: uniform over the lanes of one exponentiation.
+template <class C, class G>
+MLHIP_HD void gt_exp_window_chain(typename G::T& acc, typename G::T (&tab)[15], const uint32_t (&s)[8]) {
+#pragma unroll 1
+  for (int k = 1; k < 15; k++) G::mul(tab[k], tab[k - 1], tab[0]);
+  G::one(acc);
+  bool started = false;
+#pragma unroll 1
+  for (int w = 63; w >= 0; w--) {
+    if (started) {
+#pragma unroll 1
+      for (int d = 0; d < 4; d++) G::sqr(acc, acc);
+    }
+    const uint32_t nib = (s[w >> 3] >> ((w & 7) * 4)) & 15u;
+    if (nib) {
+      if (started)
+        G::mul(acc, acc, tab[nib - 1]);
+      else {
+        acc = tab[nib - 1];
+        started = true;
+      }
+    }
+  }
+}
 
 // acc = tab[0]^s for tab[0] in Gt, dig = gt_exp_split(s).  tab[1 .. 14] are scratch: the table has the footprint of the
 // generic kernels' 15 powers.  Every branch depends on the scalar only: uniform over the lanes of one exponentiation.

@@ -3,6 +3,7 @@
 // Pairing, Pairing2 and FExp (driver/gurvy/bls12381/bls12-381.go:448-468, bn254.go:247-267, bls12-377.go:244-264).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "mlhip_internal.h"
 #include "msm_body.h"
@@ -336,6 +337,36 @@ __device__ __forceinline__ void q28_store_gt(Fp12<C>* out, size_t i, const Fp12Q
   o[4] = w;
 }
 
+// ---- the two shapes of a Gt value in the carry-free kernels: one value per quad of lanes (QUAD) or per lane pair.  Every Gt
+// kernel over them is one template over <C, QUAD> with __launch_bounds__(64) and MLHIP_LP_OCC, launched by gt_launch below.
+template <class C, bool QUAD>
+struct GtShape {
+  typedef Fp2L28<C> E2;
+  typedef typename std::conditional<QUAD, GtOpsQ<C, E2>, GtOpsLp<C, E2>>::type G;
+  typedef typename G::T T;
+  static constexpr int LANES = QUAD ? 4 : 2;
+  static __device__ __forceinline__ void load(T& f, const Fp12<C>* in, size_t i) {
+    if constexpr (QUAD)
+      q28_load_gt<C>(f, in, i);
+    else
+      lp28_load_gt<C>(f, in, i);
+  }
+  static __device__ __forceinline__ void store(Fp12<C>* out, size_t i, const T& f) {
+    if constexpr (QUAD)
+      q28_store_gt<C>(out, i, f);
+    else
+      lp28_store_gt<C>(out, i, f);
+  }
+  static __device__ __forceinline__ void zero(T& f) {
+    if constexpr (QUAD) {
+      fp6_zero<C>(f.v);
+    } else {
+      fp6_zero<C>(f.c0);
+      fp6_zero<C>(f.c1);
+    }
+  }
+};
+
 // ---- one pairing per QUAD of lanes (pairing_quad.h; BLS12-381, carry-free element): pair A of a quad carries the c0 half
 // and pair B the c1 half of every Fp12 value.  WHAT: 0 = Miller loop of ppp <= MAXP pairs per product, 1 = final
 // exponentiation, 2 = Miller loop of one pair + final exponentiation.
@@ -387,6 +418,47 @@ __global__ void __launch_bounds__(256) k_fp_mul(const Fp<C>* __restrict__ a, con
   out[i] = r;
 }
 
+// ---- quads or lane pairs: the one place that decides ----------------------------------------------------------------------
+// MLHIP_PAIRING_QUAD=1 / 0 forces / forbids one element per quad of lanes.  Read on every batch, never cached: the tests flip
+// it.  (A value other than 0 or 1 keeps what it meant before there was one reader: "not 1" to the pairing kernels, "not 0" to
+// the Gt operations.)
+enum QuadSwitch { QUAD_UNSET, QUAD_OFF, QUAD_ON, QUAD_OTHER };
+inline QuadSwitch pairing_quad_switch() {
+  const char* qe = getenv("MLHIP_PAIRING_QUAD");
+  return !qe ? QUAD_UNSET : qe[0] == '1' ? QUAD_ON : qe[0] == '0' ? QUAD_OFF : QUAD_OTHER;
+}
+
+// Pairing kernels (what: 0 = Miller loop, 1 = final exponentiation, 2 = both), general and prepared: one pairing per QUAD of
+// lanes (pairing_quad.h) while the batch leaves the chip under-filled.  Up to 2^14 elements (65 536 lanes = one wave per SIMD)
+// a batch takes the time of ONE pairing's dependent chain, which is 1.5 x shorter on a quad (1 024 pairings: 5.7 ms instead
+// of 8.5; single Pairing 2.6 / FExp 3.1 ms instead of 3.9 / 4.6); a full chip is bound by instruction issue, where the
+// pairs' fewer instructions win (65 536: 18.6 vs 23.4 ms).
+// (round 2 also ran the Miller loop of single pairs on quads at every size -- 65 536 loops 9.0 ms against the pairs'
+// 9.2; since round 3 the pairs' loop keeps T and P in LDS and squares and multiplies by the line in one call: 8.6 ms)
+// BLS12-377 (profiles/r04_pairing_quad_bls377.txt): quads win up to 2^15 elements (16 384 pairings 7.4 ms against 13.5,
+// 32 768: 12.9 / 14.9, 65 536: 25.2 / 23.9), its Miller loop alone at every size.
+// The callers add what is theirs: the general kernels have quads for products of up to 4 pairs only, and BN254's Miller loop
+// leaves the quads for the SATURATED lane pairs (pairing_device).
+template <class C>
+bool pairing_wants_quads(int what, size_t n) {
+  const QuadSwitch q = pairing_quad_switch();
+  if (q != QUAD_UNSET) return q == QUAD_ON;
+  return n <= ((size_t)1 << (C::ID == 2 ? 15 : 14)) || (C::ID == 2 && what == 0);
+}
+
+// The Gt operations over GtShape (Gt.Exp both ways, the membership test, Gt.Inverse): quads at EVERY size unless the switch
+// is 0 -- their chains are generic squarings and products, where a quad does the lane pair's work in half the rounds without
+// the 84-word operands crossing scratch (Gt.Exp, 65 536: 15.7 ms against 19.2; 1 024: 4.0 / 7.9).  BLS12-377 (round 4):
+// profiles/r04_pairing_quad_bls377.txt.  `quad` and `pairs` are the two instances of one kernel template.
+template <class C, class... P, class... A>
+int gt_launch(void (*quad)(P...), void (*pairs)(P...), size_t n, hipStream_t st, A... args) {
+  const bool q = pairing_quad_switch() != QUAD_OFF;
+  const size_t lanes = q ? GtShape<C, true>::LANES : GtShape<C, false>::LANES;
+  (q ? quad : pairs)<<<dim3((unsigned)((lanes * n + 63) / 64)), dim3(64), 0, st>>>(args...);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // carry-free lane pairs on every curve (BLS12-377's u^2 = -5: fp2_lanes28.h carry-propagates every product operand first;
 // BN254: 10 limbs, xi = 9 + u) unless MLHIP_PAIRING_SAT=1 (read per batch so a test can switch paths)
 template <class C>
@@ -406,11 +478,8 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
   const bool one_lane = mlhip_alt_switch("MLHIP_PAIRING_ONE_LANE");  // read per batch so a test can switch paths (test build only)
   // BN254's Miller loop ALONE is a product-bound kernel and stays on the saturated lane pairs (7.3 against 7.45 ms per 65 536)
   // -- except where a quad's shorter chain decides: batches that leave the chip under-filled (round 4)
-  bool bn_miller_saturated = C::IS_BN && what == 0;
-  if (bn_miller_saturated && ppp <= 4) {
-    const char* qe = getenv("MLHIP_PAIRING_QUAD");
-    if (qe ? qe[0] == '1' : n <= ((size_t)1 << 14)) bn_miller_saturated = false;
-  }
+  const bool quads = (what != 0 || ppp <= 4) && pairing_wants_quads<C>(what, n);  // (longer products stay on lane pairs)
+  const bool bn_miller_saturated = C::IS_BN && what == 0 && !quads;
   if (one_lane) {
     if constexpr (kBuildAlt) {
       unsigned blocks = (unsigned)((n + 63) / 64);
@@ -432,19 +501,7 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
     // additions and squarings do: 8.6 -> 7.3 ms, the fused pairing 15.9 -> 14.1 ms)
     unsigned blocks = (unsigned)((2 * n + 63) / 64);
     {  // BLS12-381 and, since round 4, BLS12-377 (D-twist line product, u^2 = -5) and BN254 (Frobenius lines, BN hard part)
-      // One pairing per QUAD of lanes (pairing_quad.h) while the batch leaves the chip under-filled: up to 2^14 elements
-      // (65 536 lanes = one wave per SIMD) a batch takes the time of ONE pairing's dependent chain, which is 1.5 x
-      // shorter on a quad (1 024 pairings: 5.7 ms instead of 8.5; single Pairing 2.6 / FExp 3.1 ms instead of 3.9 / 4.6);
-      // a full chip is bound by instruction issue, where the pairs' fewer instructions win (65 536: 18.6 vs 23.4 ms).
-      // MLHIP_PAIRING_QUAD=1 / 0 forces / forbids the quads (products of up to 4 pairs; longer ones stay on lane pairs).
-      const char* qe = getenv("MLHIP_PAIRING_QUAD");
-      // (round 2 also ran the Miller loop of single pairs on quads at every size -- 65 536 loops 9.0 ms against the pairs'
-      // 9.2; since round 3 the pairs' loop keeps T and P in LDS and squares and multiplies by the line in one call: 8.6 ms)
-      // BLS12-377 (profiles/r04_pairing_quad_bls377.txt): quads win up to 2^15 elements (16 384 pairings 7.4 ms against 13.5,
-      // 32 768: 12.9 / 14.9, 65 536: 25.2 / 23.9), its Miller loop alone at every size
-      const size_t quad_max = (size_t)1 << (C::ID == 2 ? 15 : 14);
-      const bool quads = qe ? qe[0] == '1' : (n <= quad_max || (C::ID == 2 && what == 0));
-      if (quads && (what != 0 || ppp <= 4)) {
+      if (quads) {
         const unsigned qblocks = (unsigned)((4 * n + 63) / 64);
         if (what == 0 && ppp == 1)
           k_pairing_q28<C, 0, 1><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr, (Fp12<C>*)d_out);
@@ -546,8 +603,28 @@ __global__ void __launch_bounds__(64) k_gt_exp(const Fp12<C>* __restrict__ in, c
   out[i] = acc;
 }
 
-// the same over lane pairs (two lanes per exponentiation; the running power lives in the LDS slot like the Miller
-// accumulator): the batched entry point runs this one, MLHIP_PAIRING_ONE_LANE=1 the kernel above
+// the same by 4-bit windows (gt_exp_window_chain, gt_exp_cyclo.h), one exponentiation per quad of lanes or per lane pair in
+// the carry-free form: what the batched entry point runs (MLHIP_PAIRING_ONE_LANE=1: the kernel above).  The table of powers
+// and the accumulator live in scratch as 28-bit-limb values (an 84-word LDS slot per lane would cost the eighth wave of a CU
+// its LDS).  On a quad the chain has one Fp6 product per squaring instead of two and two per multiplication instead of three.
+template <class C, bool QUAD>
+__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_window(const Fp12<C>* __restrict__ in,
+                                                                   const uint32_t* __restrict__ scalars, int mont, size_t n,
+                                                                   Fp12<C>* __restrict__ out) {
+  typedef GtShape<C, QUAD> S;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t / S::LANES;  // uniform over the lanes of one value, and so is the scalar: every branch of the chain too
+  if (i >= n) return;
+  uint32_t s[8];
+  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+  typename S::T tab[15], acc;
+  S::load(tab[0], in, i);
+  gt_exp_window_chain<C, typename S::G>(acc, tab, s);
+  S::store(out, i, acc);
+}
+
+// the same chain over lane pairs on SATURATED limbs (test build only, MLHIP_PAIRING_SAT=1); the running power lives in an
+// LDS slot like the Miller accumulator of k_pairing_lp
 template <class C>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_lp(const Fp12<C>* __restrict__ in,
                                                                const uint32_t* __restrict__ scalars, int mont, size_t n,
@@ -561,106 +638,10 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_lp(const Fp12<C>* __
   Fp12<C, E2>& acc = *reinterpret_cast<Fp12<C, E2>*>(&f_slots[threadIdx.x * SLOT]);
   uint32_t s[8];
   fr_canonical<C>(s, scalars + 8 * i, mont != 0);
-  // 4-bit fixed windows: base^1 .. base^15 in scratch (4.3 KB per lane, one 288-byte read per window), then 4 squarings
-  // and at most one product per window -- 255 squarings + <= 78 products instead of ~128
   Fp12<C, E2> tab[15];
   lp_load_gt<C>(tab[0], in, i);
-#pragma unroll 1
-  for (int k = 1; k < 15; k++) fp12_mul<C>(tab[k], tab[k - 1], tab[0]);
-  fp12_one<C>(acc);
-  bool started = false;
-#pragma unroll 1
-  for (int w = 63; w >= 0; w--) {  // the scalar is the same on both lanes of a pair: every branch is pair-uniform
-    if (started) {
-#pragma unroll 1
-      for (int d = 0; d < 4; d++) fp12_sqr<C>(acc, acc);
-    }
-    const uint32_t nib = (s[w >> 3] >> ((w & 7) * 4)) & 15u;
-    if (nib) {
-      if (started)
-        fp12_mul<C>(acc, acc, tab[nib - 1]);
-      else {
-        acc = tab[nib - 1];
-        started = true;
-      }
-    }
-  }
+  gt_exp_window_chain<C, GtOpsLp<C, E2>>(acc, tab, s);
   lp_store_gt<C>(out, i, acc);
-}
-
-// the same in the carry-free form (BLS12-381): 4-bit windows, the table of powers in scratch as 28-bit-limb values, the
-// accumulator too (an 84-word slot per lane would cost the eighth wave of a CU its LDS)
-// Gt.Exp with one exponentiation per quad of lanes (pairing_quad.h): the 4-bit windowed chain of k_gt_exp_lp28 with one
-// Fp6 product per squaring instead of two and two per multiplication instead of three -- for batches that leave the chip
-// under-filled (the chain's depth is what they wait for)
-template <class C>
-__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_q28(const Fp12<C>* __restrict__ in,
-                                                                const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                                Fp12<C>* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = t >> 2;  // quad-uniform exit
-  if (i >= n) return;
-  typedef Fp2L28<C> E2;
-  uint32_t s[8];
-  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
-  Fp12Q<C, E2> tab[15], acc;
-  q28_load_gt<C>(tab[0], in, i);
-#pragma unroll 1
-  for (int k = 1; k < 15; k++) fp12q_mul<C>(tab[k], tab[k - 1], tab[0]);
-  fp12q_one<C>(acc);
-  bool started = false;
-#pragma unroll 1
-  for (int w = 63; w >= 0; w--) {  // the scalar is the same on the four lanes of a quad: every branch is quad-uniform
-    if (started) {
-#pragma unroll 1
-      for (int d = 0; d < 4; d++) fp12q_sqr<C>(acc, acc);
-    }
-    const uint32_t nib = (s[w >> 3] >> ((w & 7) * 4)) & 15u;
-    if (nib) {
-      if (started)
-        fp12q_mul<C>(acc, acc, tab[nib - 1]);
-      else {
-        acc = tab[nib - 1];
-        started = true;
-      }
-    }
-  }
-  q28_store_gt<C>(out, i, acc);
-}
-
-template <class C>
-__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_lp28(const Fp12<C>* __restrict__ in,
-                                                                 const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                                 Fp12<C>* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = t >> 1;  // pair-uniform exit
-  if (i >= n) return;
-  typedef Fp2L28<C> E2;
-  uint32_t s[8];
-  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
-  Fp12<C, E2> tab[15], acc;
-  lp28_load_gt<C>(tab[0], in, i);
-#pragma unroll 1
-  for (int k = 1; k < 15; k++) fp12_mul<C>(tab[k], tab[k - 1], tab[0]);
-  fp12_one<C>(acc);
-  bool started = false;
-#pragma unroll 1
-  for (int w = 63; w >= 0; w--) {  // the scalar is the same on both lanes of a pair: every branch is pair-uniform
-    if (started) {
-#pragma unroll 1
-      for (int d = 0; d < 4; d++) fp12_sqr<C>(acc, acc);
-    }
-    const uint32_t nib = (s[w >> 3] >> ((w & 7) * 4)) & 15u;
-    if (nib) {
-      if (started)
-        fp12_mul<C>(acc, acc, tab[nib - 1]);
-      else {
-        acc = tab[nib - 1];
-        started = true;
-      }
-    }
-  }
-  lp28_store_gt<C>(out, i, acc);
 }
 
 template <class C>
@@ -670,18 +651,8 @@ int gt_exp_device(const void* d_in, const void* d_scalars, int mont, size_t n, v
       k_gt_exp<C><<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars, mont, n,
                                                                      (Fp12<C>*)d_out);
   } else if (lp28_enabled<C>()) {
-    {
-      // quads at every size: the windowed chain is generic squarings and products, where a quad does the lane pair's work
-      // in half the rounds without the 84-word operands crossing scratch (65 536: 15.7 ms against 19.2; 1 024: 4.0 / 7.9);
-      // MLHIP_PAIRING_QUAD=0 keeps the lane-pair kernel.  BLS12-377 (round 4): profiles/r04_pairing_quad_bls377.txt
-      const char* qe = getenv("MLHIP_PAIRING_QUAD");
-      if (!(qe && qe[0] == '0'))
-        k_gt_exp_q28<C><<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
-                                                                               mont, n, (Fp12<C>*)d_out);
-      else
-        k_gt_exp_lp28<C><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in,
-                                                                                (const uint32_t*)d_scalars, mont, n, (Fp12<C>*)d_out);
-    }
+    return gt_launch<C>(k_gt_exp_window<C, true>, k_gt_exp_window<C, false>, n, st, (const Fp12<C>*)d_in,
+                        (const uint32_t*)d_scalars, mont, n, (Fp12<C>*)d_out);
   } else if constexpr (kBuildAlt) {
     k_gt_exp_lp<C><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
                                                                           mont, n, (Fp12<C>*)d_out);
@@ -692,53 +663,28 @@ int gt_exp_device(const void* d_in, const void* d_scalars, int mont, size_t n, v
 
 // ---- Gt.Exp for members of Gt (gt_exp_cyclo.h): the scalar split into digits of |x| (BN254: 6 x^2),
 // a 15-entry table of products of Frobenius images in scratch (the footprint of the kernels above) and 64 steps of one
-// cyclotomic squaring (BN254: two) and at most one product.  One exponentiation per quad of lanes ...
-template <class C>
-__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_cyclo_q28(const Fp12<C>* __restrict__ in,
-                                                                      const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                                      Fp12<C>* __restrict__ out) {
+// cyclotomic squaring (BN254: two) and at most one product.  No one-lane or saturated form of this chain exists.
+template <class C, bool QUAD>
+__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_cyclo(const Fp12<C>* __restrict__ in,
+                                                                  const uint32_t* __restrict__ scalars, int mont, size_t n,
+                                                                  Fp12<C>* __restrict__ out) {
+  typedef GtShape<C, QUAD> S;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = t >> 2;  // quad-uniform exit
+  const size_t i = t / S::LANES;  // uniform over the lanes of one value
   if (i >= n) return;
-  typedef Fp2L28<C> E2;
   uint32_t s[8], dig[8];
   fr_canonical<C>(s, scalars + 8 * i, mont != 0);
   gt_exp_split<C>(dig, s);
-  Fp12Q<C, E2> tab[15], acc;
-  q28_load_gt<C>(tab[0], in, i);
-  gt_exp_cyclo_chain<C, GtOpsQ<C, E2>>(acc, tab, dig);
-  q28_store_gt<C>(out, i, acc);
-}
-// ... and per lane pair (MLHIP_PAIRING_QUAD=0, as for mlhip_gt_exp): the second implementation of the parity tests
-template <class C>
-__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_exp_cyclo_lp28(const Fp12<C>* __restrict__ in,
-                                                                       const uint32_t* __restrict__ scalars, int mont, size_t n,
-                                                                       Fp12<C>* __restrict__ out) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t i = t >> 1;  // pair-uniform exit
-  if (i >= n) return;
-  typedef Fp2L28<C> E2;
-  uint32_t s[8], dig[8];
-  fr_canonical<C>(s, scalars + 8 * i, mont != 0);
-  gt_exp_split<C>(dig, s);
-  Fp12<C, E2> tab[15], acc;
-  lp28_load_gt<C>(tab[0], in, i);
-  gt_exp_cyclo_chain<C, GtOpsLp<C, E2>>(acc, tab, dig);
-  lp28_store_gt<C>(out, i, acc);
+  typename S::T tab[15], acc;
+  S::load(tab[0], in, i);
+  gt_exp_cyclo_chain<C, typename S::G>(acc, tab, dig);
+  S::store(out, i, acc);
 }
 
 template <class C>
 int gt_exp_cyclo_device(const void* d_in, const void* d_scalars, int mont, size_t n, void* d_out, hipStream_t st) {
-  // quads unless MLHIP_PAIRING_QUAD=0, at every size, as gt_exp_device (no one-lane or saturated form of this chain exists)
-  const char* qe = getenv("MLHIP_PAIRING_QUAD");
-  if (!(qe && qe[0] == '0'))
-    k_gt_exp_cyclo_q28<C><<<dim3((unsigned)((4 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
-                                                                                 mont, n, (Fp12<C>*)d_out);
-  else
-    k_gt_exp_cyclo_lp28<C><<<dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st>>>((const Fp12<C>*)d_in,
-                                                                                  (const uint32_t*)d_scalars, mont, n, (Fp12<C>*)d_out);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return gt_launch<C>(k_gt_exp_cyclo<C, true>, k_gt_exp_cyclo<C, false>, n, st, (const Fp12<C>*)d_in, (const uint32_t*)d_scalars,
+                      mont, n, (Fp12<C>*)d_out);
 }
 
 template <class C>

@@ -179,8 +179,8 @@ int g2_prepared_build(mlhip_g2_prepared_tables* t, hipStream_t st) {
 
 // Which kernels run a batch (what: 0 = Miller loop, 2 = Miller loop + final exponentiation):
 //   * MLHIP_PAIRING_ONE_LANE=1 (test build): one lane per product over the boundary-form table;
-//   * quads while the batch leaves the chip under-filled, lane pairs above -- the sizes pairing_device switches at
-//     (MLHIP_PAIRING_QUAD=1 / 0 forces / forbids the quads);
+//   * quads while the batch leaves the chip under-filled, lane pairs above: pairing_wants_quads (pairing_kernels.h), the
+//     switch of the general kernels (MLHIP_PAIRING_QUAD=1 / 0 forces / forbids the quads);
 //   * MLHIP_G2_PREPARED_GENERAL=1, or a size inside prepared_general_range(): the GENERAL kernels on the Qs expanded from
 //     the handle's affine copy -- where the measured A/B (tools/perf_g2_prepared.py) says they win
 //     (MLHIP_G2_PREPARED_GENERAL=0 keeps the prepared kernels at every size).
@@ -248,10 +248,7 @@ int g2_prepared_run(const mlhip_g2_prepared_tables* t, int what, const void* d_g
     HIPCHK(hipGetLastError());
     return 0;
   }
-  const char* qe = getenv("MLHIP_PAIRING_QUAD");
-  const size_t quad_max = (size_t)1 << (C::ID == 2 ? 15 : 14);  // pairing_device's switch
-  const bool quads = qe ? qe[0] == '1' : (n <= quad_max || (C::ID == 2 && what == 0));
-  if (quads) {
+  if (pairing_wants_quads<C>(what, n)) {
     const unsigned blocks = (unsigned)((4 * n + 63) / 64);
     if (what == 0 && ppp == 1)
       k_pairing_prep_q28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, 1, n, out);

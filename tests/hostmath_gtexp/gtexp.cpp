@@ -1,7 +1,8 @@
 // TEST ARTIFACT -- host (g++) build of gt_exp_cyclo.h and of pairing_quad.h's fp12q_cyclo_sqr, loaded by
 // tests/test_gt_exp_cyclo_host.py through ctypes and compared with Python integers and oracle/pyref.py: the scalar split, the
 // quad Granger-Scott squaring against the generic quad squaring, and the whole chain through the host models of the
-// carry-free lane pair and quad (every operation checks its weight and value budget and aborts when one is exceeded).
+// carry-free lane pair and quad (every operation checks its weight and value budget and aborts when one is exceeded); the
+// 4-bit windowed chain of mlhip_gt_exp through the same two models and over the plain tower (tower.h on Fp2<C>).
 // It is NOT part of libmlhip.so.
 #include <stdint.h>
 #include <string.h>
@@ -118,6 +119,36 @@ struct Gx {
     memcpy(out, &o, sizeof(o));
     return w;
   }
+
+  // the same for the windowed chain, valid for any Fp12 value; form 0: the plain tower (the shape of the saturated kernel)
+  static int exp_window(int form, const void* in, const uint32_t* scalar, int mont, void* out) {
+    Fp12<C> a, o;
+    memcpy(&a, in, sizeof(a));
+    uint32_t s[8];
+    fr_canonical<C>(s, scalar, mont != 0);
+    int w = 1;
+    if (form == 0) {
+      static Fp12<C> tab[15];
+      tab[0] = a;
+      gt_exp_window_chain<C, GtOpsLp<C, Fp2<C>>>(o, tab, s);
+    } else if (form == 1) {
+      static Fp12<C, EH> tab[15];
+      Fp12<C, EH> acc;
+      load_lp(tab[0], a);
+      gt_exp_window_chain<C, GtOpsLp<C, EH>>(acc, tab, s);
+      w = store_lp(o, acc);
+    } else if (form == 2) {
+      static Fp12Q<C, EQ> tab[15];
+      Fp12Q<C, EQ> acc;
+      load_q(tab[0], a);
+      gt_exp_window_chain<C, GtOpsQ<C, EQ>>(acc, tab, s);
+      w = store_q(o, acc);
+    } else {
+      return -5;
+    }
+    memcpy(out, &o, sizeof(o));
+    return w;
+  }
 };
 
 #define GX_DISPATCH(call)                  \
@@ -141,4 +172,5 @@ int gx_modulus(int curve, uint64_t* lo, uint64_t* hi) {
 int gx_split(int curve, const uint32_t* scalar, int mont, uint32_t* dig, uint32_t* canon) { GX_DISPATCH(split(scalar, mont, dig, canon)) }
 int gx_cyclo_sqr(int curve, const void* in, void* out_cyclo, void* out_generic) { GX_DISPATCH(cyclo_sqr(in, out_cyclo, out_generic)) }
 int gx_exp(int curve, int form, const void* in, const uint32_t* scalar, int mont, void* out) { GX_DISPATCH(exp(form, in, scalar, mont, out)) }
+int gx_exp_window(int curve, int form, const void* in, const uint32_t* scalar, int mont, void* out) { GX_DISPATCH(exp_window(form, in, scalar, mont, out)) }
 }

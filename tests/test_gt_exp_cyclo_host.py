@@ -1,9 +1,11 @@
 """Gt.Exp for members of Gt without a GPU.  The device math of mathlib_amd/csrc/gt_exp_cyclo.h and pairing_quad.h's
 fp12q_cyclo_sqr, compiled for the CPU (tests/hostmath_gtexp): the scalar split against Python integers, the quad Granger-Scott
 squaring against the generic quad squaring, and the whole chain through the host models of the carry-free lane pair and quad
-(which abort on any weight or value-bound violation) against oracle/pyref.py's f12_pow -- every curve.  Plus the argument
-errors of the two C entry points."""
+(which abort on any weight or value-bound violation) against oracle/pyref.py's f12_pow -- every curve.  The 4-bit windowed
+chain of mlhip_gt_exp (gt_exp_window_chain) the same way, over the plain tower too and on a value outside Gt.  Plus the
+argument errors of the two C entry points."""
 import ctypes
+import functools
 import os
 import re
 
@@ -34,6 +36,7 @@ def gx():
     lib.gx_split.argtypes = [ci, vp, ci, vp, vp]
     lib.gx_cyclo_sqr.argtypes = [ci, vp, vp, vp]
     lib.gx_exp.argtypes = [ci, ci, vp, vp, ci, vp]
+    lib.gx_exp_window.argtypes = [ci, ci, vp, vp, ci, vp]
     return lib
 
 
@@ -119,6 +122,37 @@ def test_chain_matches_f12_pow(gx, name, form):
         if k < 6:
             assert gx.gx_exp(cp.curve_id, FORMS[form], one, raw, mont, out) == 1
             assert out.raw == one
+
+
+@functools.lru_cache(maxsize=None)
+def window_cases(name):
+    """(base bytes, [(scalar, expected bytes)]) for a member of Gt and for an arbitrary Fp12 value: the scalars 0, 1, 15, 16
+    (one window, and the first carry into the second), r - 1, two random ones, and one whose top nibble is zero while the
+    next is not (the chain starts at the second window)"""
+    cp = R.CURVES[name]
+    T = R.tower(cp)
+    d = R.Drbg("gt_exp_window/" + name)
+    top_nibble_zero = (d.below(1 << 252) | 1 << 251) % (1 << 252)
+    assert top_nibble_zero >> 252 == 0 and top_nibble_zero >> 248 != 0 and top_nibble_zero < cp.r
+    scalars = [0, 1, 15, 16, cp.r - 1, d.below(cp.r), d.below(cp.r), top_nibble_zero]
+    arbitrary = T.f12_mul(member(name), T.f12_add(member(name), T.f12_one))  # f (f + 1): a unit of Fp12 outside Gt
+    assert T.f12_pow(arbitrary, cp.r) != T.f12_one
+    return [(R.gt_to_mont_bytes(cp, f), [(s, R.gt_to_mont_bytes(cp, T.f12_pow(f, s))) for s in scalars]) for f in (member(name), arbitrary)]
+
+
+@pytest.mark.parametrize("form", ["plain"] + list(FORMS))
+@pytest.mark.parametrize("name", CURVES)
+def test_window_chain_matches_f12_pow(gx, name, form):
+    """the chain of mlhip_gt_exp's kernels on the host: right for a member of Gt and for any other Fp12 value, and the
+    carry-free models stay within their budgets (they abort otherwise) and hand back weight 1"""
+    cp = R.CURVES[name]
+    out = ctypes.create_string_buffer(12 * cp.fp_bytes)
+    for base, rows in window_cases(name):
+        for k, (s, want) in enumerate(rows):
+            mont = k & 1
+            raw = R.scalar_to_bytes(s, cp, mont=True) if mont else s.to_bytes(32, "little")
+            assert gx.gx_exp_window(cp.curve_id, FORMS.get(form, 0), base, raw, mont, out) == 1
+            assert out.raw == want, (name, form, hex(s))
 
 
 def test_header_declares_the_entry_points(mlhip):
