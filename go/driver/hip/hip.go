@@ -287,6 +287,42 @@ func (c *Curve) MultiScalarMulG2(a []driver.G2, b []driver.Zr) driver.G2 {
 	return out
 }
 
+// SumG1 = a[0] + a[1] + ...: G1.Add in a loop (bls12-381.go, Add) as one call.  Short lists are added on the host by
+// the library; long ones (aggregating signatures, folding proofs) are summed on the device (mlhip_g1_sum,
+// MLHIP_SUM_DEVICE_MIN).  An empty list gives the identity.
+func (c *Curve) SumG1(a []driver.G1) driver.G1 {
+	out := &gurvy381.G1{}
+	n := len(a)
+	if n == 0 {
+		return out
+	}
+	points := make([]bls12381.G1Affine, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G1).G1Affine
+	}
+	check(func() C.int {
+		return C.mlhip_g1_sum(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&points[0]), C.size_t(n), unsafe.Pointer(&out.G1Affine))
+	})
+	return out
+}
+
+// SumG2 is SumG1 in G2 (mlhip_g2_sum): aggregating public keys.
+func (c *Curve) SumG2(a []driver.G2) driver.G2 {
+	out := &gurvy381.G2{}
+	n := len(a)
+	if n == 0 {
+		return out
+	}
+	points := make([]bls12381.G2Affine, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G2).G2Affine
+	}
+	check(func() C.int {
+		return C.mlhip_g2_sum(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&points[0]), C.size_t(n), unsafe.Pointer(&out.G2Affine))
+	})
+	return out
+}
+
 // MultiScalarMulG1G2 = (MultiScalarMul(a1, b), MultiScalarMulG2(a2, b)) for ONE scalar vector (BASELINE configs[3]: a
 // prover's G1 and G2 MSM over the same witness): the scalars travel and are sorted once, both groups accumulate from
 // the same bucket lists.  Mismatched lengths give the identities, as MultiScalarMul does (bls12-381.go:777).

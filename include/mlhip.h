@@ -393,7 +393,20 @@ MLHIP_API int mlhip_gt_to_bytes_device(int curve_id, const void* d_gt, size_t n,
 MLHIP_API int mlhip_gt_is_member(int curve_id, const void* gt, size_t n, unsigned char* status);
 MLHIP_API int mlhip_gt_is_member_device(int curve_id, const void* d_gt, size_t n, unsigned char* d_status, void* stream);
 
-/* ---- group helpers (host, O(n) tiny): combine per-GPU partial results after the RCCL all-gather */
+/* ---- group helpers: out = sum of n affine points (n = 0: the point at infinity).  Two routes, one result:
+ *   host loop     below the threshold -- the handful of per-GPU partial results combined after the RCCL all-gather.  No HIP
+ *                 call is made: a rank that must not initialise a device may call it.
+ *   device route  from the threshold on (aggregating 10^4 .. 10^6 signatures or keys, folding proofs), when the thread has a
+ *                 usable device: upload, strided slices per lane (pair), segmented sums, download of one point, on a leased
+ *                 stream.  Without a usable device the host loop serves every n: these two functions
+ *                 never return MLHIP_ENODEVICE.
+ *   threshold     MLHIP_SUM_DEVICE_MIN=n (0 = never the device, 1 = always when there is one); default 2^14 points for G1
+ *                 and 2^12 for G2: from there on the device route, PCIe upload included, is ahead of the host loop at every
+ *                 measured size on all three curves (profiles/point_sum_ab.txt).
+ *   inputs        any points of the curve, inside or outside the prime-order subgroup, and (0,0) = infinity, in any order
+ *                 and multiplicity (one point n times, P next to -P): both routes give the same bytes, the canonical affine
+ *                 form of the sum.  A point off the curve gives an undefined result on the device route, never a fault
+ *                 (no address depends on the data). */
 MLHIP_API int mlhip_g1_sum(int curve, const void* affine_points, size_t n, void* out_affine);
 MLHIP_API int mlhip_g2_sum(int curve, const void* affine_points, size_t n, void* out_affine);
 
@@ -422,6 +435,8 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
  *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
+ *     MLHIP_SUM_DEVICE_MIN=n           mlhip_g1_sum / mlhip_g2_sum: smallest list summed on the device (0 = never, 1 = always;
+ *                                      default 2^14 G1 / 2^12 G2)
  *     MLHIP_BASES_BATCH_WINDOW=w, MLHIP_BASES_BATCH_CHUNK=P   mlhip_bases_msm_batch*: table width 4 .. 12 (default 12), pairs
  *                                      per chunk on the table path, 1, 2, 4, 8 or 16 (default: the largest that fills 2^16 lanes)
  *     MLHIP_BASES_BATCH_MAX_MB=m       ... tables per handle at most m MB (default 1024; 0 = never: the table-free path)

@@ -18,7 +18,7 @@
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
 //   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
-//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, SumG1, SumG2
 #pragma once
 #include <array>
 #include <cstdint>
@@ -498,6 +498,24 @@ class Curve {
     Bytes pts, sc;
     pack(a, b, pts, sc);
     check(mlhip_msm_g2(id, pts.data(), sc.data(), scalars_mont ? 1 : 0, a.size(), window_c, out.raw.data()));
+    return out;
+  }
+  // points[0] + points[1] + ...: G1::Add / G2::Add in a loop as one call; long lists are summed on the device
+  // (mlhip_g1_sum / mlhip_g2_sum, MLHIP_SUM_DEVICE_MIN).  An empty list gives the identity.
+  G1 SumG1(const std::vector<G1>& points) const {
+    G1 out = NewG1();
+    Bytes pts;
+    pts.reserve(points.size() * g1_bytes);
+    for (const G1& p : points) pts.insert(pts.end(), p.raw.begin(), p.raw.end());
+    check(mlhip_g1_sum(id, pts.data(), points.size(), out.raw.data()));
+    return out;
+  }
+  G2 SumG2(const std::vector<G2>& points) const {
+    G2 out = NewG2();
+    Bytes pts;
+    pts.reserve(points.size() * g2_bytes);
+    for (const G2& p : points) pts.insert(pts.end(), p.raw.begin(), p.raw.end());
+    check(mlhip_g2_sum(id, pts.data(), points.size(), out.raw.data()));
     return out;
   }
   // out[i] = MultiScalarMul(a[i], b[i]) for many small MSMs in one device call (mlhip_msm_batch); every segment keeps

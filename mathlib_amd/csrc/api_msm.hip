@@ -168,6 +168,39 @@ int plan_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d1, void* d2, void
   return rc;
 }
 
+// ---- mlhip_g1_sum / mlhip_g2_sum: host loop or device route (point_sum.h) ------------------------------------------------
+// Smallest n that goes to the device, per group: the smallest measured size (a power of two) from which the device route,
+// upload included, is ahead of the host loop by more than 4 % at every larger size on all three curves: at 2^12 G1 is a
+// tie (0.96 .. 1.08x), G2 2.5x ahead (tools/perf_point_sum.py, profiles/point_sum_ab.txt).  MLHIP_SUM_DEVICE_MIN=n overrides both: 0 = never,
+// 1 = always.  Far above the handful of per-device partials the multi-GPU combine adds, which must not touch a device.
+constexpr size_t SUM_DEVICE_MIN_G1 = (size_t)1 << 14, SUM_DEVICE_MIN_G2 = (size_t)1 << 12;
+
+// does this sum take the device route?  False below the threshold without a single HIP call; at or above it, false when
+// the thread has no usable device (the host loop serves every size: these two entry points never need a GPU).
+bool sum_on_device(int group, size_t n) {
+  size_t min_n = group == MLHIP_GROUP_G1 ? SUM_DEVICE_MIN_G1 : SUM_DEVICE_MIN_G2;
+  if (const char* e = getenv("MLHIP_SUM_DEVICE_MIN")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end != e) min_n = (size_t)v;
+  }
+  if (min_n == 0 || n == 0 || n < min_n) return false;
+  return ensure_device() == 0;
+}
+
+// upload, pass 0, sum passes, download of one point -- on a leased stream; n >= 1, ensure_device() has succeeded
+int device_group_sum(const CurveOps* ops, int group, const void* pts, size_t n, void* out) {
+  const size_t ptsz = ops->point_size(group);
+  HostCall hc;
+  hc.reserve(n * ptsz + ptsz);
+  void* dp = hc.up(pts, n * ptsz);
+  void* dout = hc.dev(ptsz);
+  if (hc.rc) return hc.rc;
+  int rc = ops->point_sum(group, dp, n, dout, hc.l.st);
+  if (rc) return rc;
+  return hc.down(out, dout, ptsz);
+}
+
 }  // namespace
 
 namespace mlhip_rt {
@@ -693,6 +726,7 @@ int mlhip_g1_sum(int curve, const void* pts, size_t n, void* out) {
   if (!out || (n && !pts)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (sum_on_device(MLHIP_GROUP_G1, n)) return device_group_sum(ops, MLHIP_GROUP_G1, pts, n, out);
   return ops->g1_sum(pts, n, out);
 }
 
@@ -700,6 +734,7 @@ int mlhip_g2_sum(int curve, const void* pts, size_t n, void* out) {
   if (!out || (n && !pts)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+  if (sum_on_device(MLHIP_GROUP_G2, n)) return device_group_sum(ops, MLHIP_GROUP_G2, pts, n, out);
   return ops->g2_sum(pts, n, out);
 }
 

@@ -178,6 +178,8 @@ struct mlhip_g2_prepared_tables {
   X(C, int, bases_batch,                                                                                                  \
     (int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars, int mont,          \
      const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out, hipStream_t st))            \
+  /* d_out = the affine sum of the n >= 1 affine points at d_points (point_sum.h: mlhip_g1_sum / mlhip_g2_sum) */        \
+  X(C, int, point_sum, (int group, const void* d_points, size_t n, void* d_out, hipStream_t st))                          \
   /* what = -1: build t's tables from t->d_q ; 0 / 2: Miller loops / fused pairings of n products against them */         \
   X(C, int, g2_prepared,                                                                                                  \
     (mlhip_g2_prepared_tables * t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,             \

@@ -17,6 +17,8 @@
 //                 then segmented sums of <= 32 partials per lane (msm_batch.h)
 //   k_bases_batch_chunk (+ _lp)   the same over a mlhip_bases handle: per-base fixed-window tables, ceil(256 / w) mixed
 //                 additions per pair, no doubling (msm_bases_batch.h)
+//   k_point_sum (+ _lp)   plain sums of many points (mlhip_g1_sum / mlhip_g2_sum above their threshold): strided slices per
+//                 lane, then k_msm_batch_sum over the lanes' partials (point_sum.h)
 //   host tail     Horner over <= W*c bit positions + one inversion (O(1) work, 64-bit limbs)
 // Replaces gnark-crypto's MultiExp behind MultiScalarMul (reference
 // driver/gurvy/bls12381/bls12-381.go:766-783, driver/gurvy/bn254.go:232-245, driver/gurvy/bls12-377.go:229-242).
@@ -57,6 +59,7 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 #include "msm_g2.h"
 #include "msm_scalar_mul.h"
 #include "msm_batch.h"
+#include "point_sum.h"
 #include "msm_bases_batch.h"
 #include "msm_fold.h"
 #include "msm_plan.h"

@@ -45,6 +45,10 @@ int MLHIP_TU_FN(bases_batch)(int group, mlhip_bases_batch_tables* t, const void*
     return bases_batch_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(t, d_pts, n_bases, d_scalars, mont, base_index, offsets, k, need, d_out, st);
   return bases_batch_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(t, d_pts, n_bases, d_scalars, mont, base_index, offsets, k, need, d_out, st);
 }
+int MLHIP_TU_FN(point_sum)(int group, const void* d_points, size_t n, void* d_out, hipStream_t st) {
+  if (group == MLHIP_GROUP_G1) return point_sum_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, n, d_out, st);
+  return point_sum_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, n, d_out, st);
+}
 void MLHIP_TU_FN(release_cache)(void) {
   fixed_base_release();
   msm_batch_release();

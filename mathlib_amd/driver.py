@@ -450,6 +450,19 @@ class Curve:
         check(load().mlhip_msm_g2(self.id, pts, self._scalars(b), 1 if self.scalars_mont else 0, len(a), self.window_c, out))
         return G2(out.raw, self)
 
+    def SumG1(self, points: Sequence[G1]) -> G1:
+        """points[0] + points[1] + ...: G1.Add in a loop (driver/gurvy/bls12381/bls12-381.go, Add) as one call; long lists
+        are summed on the device (mlhip_g1_sum, MLHIP_SUM_DEVICE_MIN).  An empty list gives the identity."""
+        out = ctypes.create_string_buffer(self.g1_bytes)
+        check(load().mlhip_g1_sum(self.id, b"".join(p.raw for p in points), len(points), out))
+        return G1(out.raw, self)
+
+    def SumG2(self, points: Sequence[G2]) -> G2:
+        """the same in G2 (mlhip_g2_sum)"""
+        out = ctypes.create_string_buffer(self.g2_bytes)
+        check(load().mlhip_g2_sum(self.id, b"".join(p.raw for p in points), len(points), out))
+        return G2(out.raw, self)
+
     def MultiScalarMulG1G2(self, a1: Sequence[G1], a2: Sequence[G2], b: Sequence[Zr]):
         """(MultiScalarMul(a1, b), MultiScalarMulG2(a2, b)) for ONE scalar vector: sorted once on the device, both groups
         accumulate from the same lists (additive; BASELINE configs[3]).  Same length rules as MultiScalarMul."""
