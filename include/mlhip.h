@@ -191,6 +191,11 @@ MLHIP_API int mlhip_msm_plan_set_profiling(mlhip_msm_plan* plan, int on);
 MLHIP_API int mlhip_msm_plan_assume_srs(mlhip_msm_plan* plan, int on);
 MLHIP_API int mlhip_msm_plan_timings(mlhip_msm_plan* plan, float* ms, int cap);
 
+/* The device forms of the entry points above (and the _device forms further down, unless their comment says otherwise): device
+ * pointers in and out; they enqueue their kernels on `stream` and return, so the work runs in order on `stream` (NULL = the
+ * default stream) -- after whatever the caller queued there before, which may still be producing the inputs, and before
+ * whatever it queues afterwards, which may overwrite them.  Arrays documented as HOST memory (offsets, base_index, q_index) are
+ * read before the call returns (tests/test_stream_order_gpu.py calls every one of them on a busy stream). */
 MLHIP_API int mlhip_miller_loop_device(int curve, const void* d_g1, const void* d_g2, size_t pairs_per_product,
                              size_t n_products, void* d_out_gt, void* stream);
 MLHIP_API int mlhip_final_exp_device(int curve, const void* d_in_gt, size_t n, void* d_out_gt, void* stream);
