@@ -267,12 +267,11 @@ int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold
     p->M = 1u << (window_c - 1);
   }
   // buckets per level-1 reduction chunk: 16 for G1 (the quad-lane kernels are bound by work, and a longer chunk
-  // halves the second level), 8 for G2 on the boundary-form curves and for tiny windows
+  // halves the second level), 8 for tiny windows
   // (and for small bucket sets, where the chunk pass is a dependent chain rather than work: 2^12 points, c = 13:
   // reduction 0.25 -> 0.22 ms)
   // G2 (carry-free lane-pair reduction): 16 as well -- BLS12-381: reduction 1.43 -> 1.31 ms at c = 16
-  const bool chunks16 = true;
-  p->lgL = (chunks16 && p->M >= 256 && (size_t)p->W * p->M >= ((size_t)1 << 17)) ? 4 : 3;
+  p->lgL = (p->M >= 256 && (size_t)p->W * p->M >= ((size_t)1 << 17)) ? 4 : 3;
   if (const char* e = getenv("MLHIP_CHUNK_LOG2")) {
     int v = atoi(e);
     if (v >= 1 && v <= 6 && (1u << v) <= p->M) p->lgL = v;
@@ -312,25 +311,9 @@ void plan_reserve_edwards(mlhip_msm_plan* p) {
   p->conv_src = nullptr;
 }
 
-// Number of segments a host-buffer MSM is streamed in (1 = one upload, one pass).  Measured on MI355X / PCIe gen5
-// (tools/perf_hostapi.py): from 2^19 points the transfer is worth hiding; MLHIP_STREAM_SEGMENTS overrides (0/1 = off).
+// Number of segments a host-buffer MSM is streamed in (msm_segments.h; 1 = one upload, one pass)
 int stream_segments(int group, size_t n, const mlhip_msm_plan* plan) {
-  // G1 and G2 stream through the carry-free kernels and their bucket state (always there unless MLHIP_ACC32=1, which runs
-  // one pass) -- the condition stream_begin checks
-  (void)group;
-  if (!plan->aux || !plan->d_points28) return 1;
-  if (getenv("MLHIP_STREAM_SCHEDULE")) return n >= 2 ? 2 : 1;  // explicit segment weights (msm_plan.h: stream_schedule), any n
-  if (const char* e = getenv("MLHIP_STREAM_SEGMENTS")) {
-    int v = atoi(e);
-    if (v < 2) return 1;
-    if (v > MLHIP_MAX_SEGMENTS) v = MLHIP_MAX_SEGMENTS;
-    return n >= (size_t)v ? v : 1;
-  }
-  // segments of 2^18 pairs: at 2^20 the call drops from 5.9 to 4.5 ms, at 2^22 from 21.9 to 12.8 ms (the device-only time)
-  // G2 (BLS12-381): segments of 2^17 pairs, 14.9 -> 11.4 ms at 2^20.  For G1 from 2^20 pairs on the count returned here only
-  // says "stream": plan_stream replaces the equal segments by a growing schedule (stream_schedule, round 4)
-  const size_t k = n >> (group == MLHIP_GROUP_G1 ? 18 : 17);
-  return k < 2 ? 1 : (k > MLHIP_MAX_SEGMENTS ? MLHIP_MAX_SEGMENTS : (int)k);
+  return mlhip::stream_segments(plan->aux && plan->d_points28, group == MLHIP_GROUP_G1, n);
 }
 
 int plan_stream(mlhip_msm_plan* p, void* d_pts, void* d_sc, const void* points, const void* scalars, int mont, size_t n,

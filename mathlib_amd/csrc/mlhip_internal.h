@@ -25,7 +25,7 @@ void host_parallel(int njobs, void (*fn)(const void*, int, void*), const void* i
     if (e_ != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-#define MLHIP_MAX_SEGMENTS 24
+#include "msm_segments.h"  // MLHIP_MAX_SEGMENTS, and how an MSM is cut into segments / tiles
 
 // MLHIP_BUILD_ALT=1 (python -m mathlib_amd.build --alt -> libmlhip_alt.so): the test build.  It also contains the second
 // implementations the parity tests compare the default kernels with -- boundary-form (32-bit limb) bucket accumulation and

@@ -20,6 +20,15 @@
 //   k_point_sum (+ _lp)   plain sums of many points (mlhip_g1_sum / mlhip_g2_sum above their threshold): strided slices per
 //                 lane, then k_msm_batch_sum over the lanes' partials (point_sum.h)
 //   host tail     Horner over <= W*c bit positions + one inversion (O(1) work, 64-bit limbs)
+// Launch sequence (msm_plan.h): plan_launch runs an MSM in one pass, stream_begin / stream_tile / stream_end as a train of
+// segments or tiles cut by msm_segments.h (stream_segments, resident_tiles, shared_segments, stream_schedule,
+// segment_cuts).  Both are orchestration of streams and events around the same steps: launch_sort, launch_convert (points
+// into the carry-free form), launch_accumulate (THE choice of bucket kernel, with the long-bucket step: launch_big_slices
+// and the kernel that adds the slice sums), launch_reduce, finish_train (reduce, copy to h_out, `done`).  What one pass does
+// differently from a tile hangs on launch_accumulate's `one_pass` and is listed there and at plan_launch: it skips the
+// long-bucket step below big_bucket_threshold, may take the quad kernel, reaches the test build's boundary-form kernels,
+// uploads a host-buffer call's points itself, sets the conv_* cache after every conversion, and places ev[0..3] / the wait
+// for ev_join where the tiles place ev_tile / the waits for ev_seg.
 // Replaces gnark-crypto's MultiExp behind MultiScalarMul (reference
 // driver/gurvy/bls12381/bls12-381.go:766-783, driver/gurvy/bn254.go:232-245, driver/gurvy/bls12-377.go:229-242).
 #pragma once

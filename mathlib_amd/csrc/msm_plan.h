@@ -1,15 +1,14 @@
-// msm_plan.h -- host side of the MSM: plan allocation, the launch sequences (one pass and streamed in segments), the
-// host tail.  Part of msm_kernels.h.
+// msm_plan.h -- host side of the MSM: plan allocation, the launch steps both sequences share (launch_sort, launch_convert,
+// launch_accumulate, launch_reduce, finish_train), the sequences themselves (plan_launch: one pass; stream_begin /
+// stream_tile / stream_end: a train of segments or tiles, cut by msm_segments.h) and the host tail.  Part of msm_kernels.h.
 #pragma once
-// (included by msm_kernels.h after its common headers and constants)
+// (included by msm_kernels.h after its common headers and constants; msm_segments.h comes with mlhip_internal.h)
 
 namespace mlhip {
 
 // G2 runs in the carry-free lane-pair form (ec28_lp.h: bucket loop, segment / tile state, lane-pair reduction) on every curve
 // since round 3 -- BLS12-381 first (-14 % accumulation), then BLS12-377 (u^2 = -5: 2^20 points 12.35 -> 9.45 ms) and BN254
 // (10 limbs: 5.25 -> 4.95 ms); MLHIP_ACC32=1 keeps the boundary-form kernels as the second implementation
-template <class C>
-constexpr bool g2_carry_free_v = true;
 
 // G2 bucket accumulation (carry-free form): lane pairs split by component with dual products (k_accumulate28_lp_seg, default)
 // or by coordinate with one-lane Karatsuba Fp2 products (k_accumulate28_kc_seg, MLHIP_G2_KC=1: 16 % fewer multiplier
@@ -132,8 +131,8 @@ int plan_alloc(mlhip_msm_plan* p) {
     p->reduce28 = want28 && !p->reduce_one_lane && !mlhip_alt_switch("MLHIP_REDUCE32");
     if (p->reduce28) HIPCHK(hipMalloc(&p->d_state28, nbuckets * sizeof(XYZZ28<typename F::Curve>)));
   }
-  if constexpr (std::is_same<F, Fp2Field<typename F::Curve>>::value && g2_carry_free_v<typename F::Curve>) {
-    // G2 in the carry-free form (g2_carry_free_v above)
+  if constexpr (std::is_same<F, Fp2Field<typename F::Curve>>::value) {
+    // G2 in the carry-free form (above)
     if (!mlhip_alt_switch("MLHIP_ACC32")) {
       if (!p->fold) HIPCHK(hipMalloc(&p->d_points28, p->max_n * sizeof(AffineG2_28<typename F::Curve>)));
       // ... and the lane-pair reduction reads the accumulators as the kernel leaves them (MLHIP_REDUCE32=1: boundary form)
@@ -249,12 +248,11 @@ void host_tail(const mlhip_msm_plan* p, XYZZ<F>& total) {
 
 // slice sums of the long buckets listed by the accumulation kernel (nothing to do, two near-empty launches, when
 // there are none)
-// (`row0`: a folded plan keeps carry-free rows only -- the slices gather from d_points28 + row0, in the form the table holds)
+// (`row0`: a folded plan keeps carry-free rows only -- the slices gather from d_points28 + row0, in the form the table holds;
+// `sv`: the plan whose entry lists (sorted / offsets / counts) describe this tile)
 template <class F, int BB>
-void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t st, const mlhip_msm_plan* sv = nullptr,
-                       size_t row0 = 0) {
+void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t st, const mlhip_msm_plan* sv, size_t row0) {
   typedef typename F::Curve C;
-  if (!sv) sv = p;  // the plan whose entry lists (sorted / offsets / counts) describe this tile
   k_big_prefix<<<dim3(1), dim3(1024), 0, st>>>(sv->d_counts, p->d_biglist, p->d_bigcount, p->d_bigprefix);
   if (p->fold) {
     if constexpr (std::is_same<F, Fp2Field<C>>::value) {
@@ -384,30 +382,23 @@ int launch_reduce(mlhip_msm_plan* p, hipStream_t st) {
   {
     size_t n_chunks = (size_t)p->W * p->T;
     if constexpr (kLanePairs) {
-      bool done28 = false;
-      if constexpr (g2_carry_free_v<C>) {
-        if (p->reduce28) {
-          typedef XYZZ28L<Fp28<C>> X28;
-          k_chunks_lp28<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>(
-              (const X28*)p->d_state28, n_chunks, p->L, (X28*)p->d_A, (X28*)p->d_W0);
-          constexpr int RB = 512;  // 256 lane pairs, 128 slots x 448 B = 56 KB of LDS per block
-          k_masked_sums_lp28<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * 2 * sizeof(X28), st>>>(
-              (const X28*)p->d_A, (const X28*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-          if (p->fold_nsel2)  // folded plan: the groups' sums combined into one window's
-            k_group_combine_lp<C, 128><<<dim3((unsigned)p->fold_nsel2), dim3((unsigned)(4 * p->W)), 2 * p->W * sizeof(X), st>>>(
-                (const X*)p->d_out, p->W, p->nsel, p->nb, (X*)p->d_out + (size_t)p->W * p->nsel);
-          done28 = true;
-        }
-      }
-      if constexpr (kBuildAlt) {  // (boundary-form lane pairs: MLHIP_REDUCE32 / MLHIP_ACC32, test build only)
-        if (!done28) {
-          k_chunks_lp<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>((const X*)p->d_buckets, n_chunks,
-                                                                                            p->L, (X*)p->d_A, (X*)p->d_W0);
-          constexpr int RB = 512;  // 256 lane pairs, 128 slots x 384 B = 48 KB of LDS per block
-          k_masked_sums_lp<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X), st>>>(
-              (const X*)p->d_A, (const X*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-        }
-      } else if (!done28) {
+      if (p->reduce28) {
+        typedef XYZZ28L<Fp28<C>> X28;
+        k_chunks_lp28<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>(
+            (const X28*)p->d_state28, n_chunks, p->L, (X28*)p->d_A, (X28*)p->d_W0);
+        constexpr int RB = 512;  // 256 lane pairs, 128 slots x 448 B = 56 KB of LDS per block
+        k_masked_sums_lp28<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * 2 * sizeof(X28), st>>>(
+            (const X28*)p->d_A, (const X28*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
+        if (p->fold_nsel2)  // folded plan: the groups' sums combined into one window's
+          k_group_combine_lp<C, 128><<<dim3((unsigned)p->fold_nsel2), dim3((unsigned)(4 * p->W)), 2 * p->W * sizeof(X), st>>>(
+              (const X*)p->d_out, p->W, p->nsel, p->nb, (X*)p->d_out + (size_t)p->W * p->nsel);
+      } else if constexpr (kBuildAlt) {  // (boundary-form lane pairs: MLHIP_REDUCE32 / MLHIP_ACC32, test build only)
+        k_chunks_lp<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>((const X*)p->d_buckets, n_chunks,
+                                                                                          p->L, (X*)p->d_A, (X*)p->d_W0);
+        constexpr int RB = 512;  // 256 lane pairs, 128 slots x 384 B = 48 KB of LDS per block
+        k_masked_sums_lp<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X), st>>>(
+            (const X*)p->d_A, (const X*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
+      } else {
         return mlhip_rt::fail(MLHIP_EINVAL, "G2 reduction: the carry-free bucket state is missing");
       }
     } else {
@@ -460,48 +451,178 @@ template <class C, class F>
 int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,
                 size_t n, int K, hipStream_t st);
 
-// Number of tiles a device-resident MSM is cut into (1 = one pass over all points); see plan_stream.  Measured
-// (profiles/r02_tiles.txt): G1 from 2^22 points on in tiles of 2^21 (235 MB of points), G2 from 2^23 on in tiles of 2^20
-// (also 235 MB); at most MLHIP_MAX_SEGMENTS tiles.
-// MLHIP_TILE_LOG2 = t forces tiles of 2^t points for every n above that (0 = never tile).
-template <class C, class F>
-int resident_tiles(const mlhip_msm_plan* p, size_t n) {
-  constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;
-  if (!p->aux || !p->d_points28) return 1;
-  if (p->fold) {  // one pass per tile of the table (an entry index addresses the rows of one tile)
-    const size_t k = (n + p->fold_tile - 1) / p->fold_tile;
-    return k < 2 ? 1 : (int)std::min<size_t>(k, MLHIP_MAX_SEGMENTS);
-  }
-  int lg = kG2 ? 20 : 21;
-  size_t from = (size_t)1 << (kG2 ? 23 : 22);
-  if (plan_use_edwards<C, F>(p)) {  // 168-byte Niels triples: 2^20 of them are what 2^21 Weierstrass points weigh
-    lg = 20;
-    from = (size_t)1 << 21;
-  }
-  if (const char* e = getenv("MLHIP_TILE_LOG2")) {
-    const int v = atoi(e);
-    if (v <= 0) return 1;
-    lg = v > 30 ? 30 : v;
-    from = ((size_t)1 << lg) + 1;
-  }
-  if (n < from) return 1;
-  size_t k = (n + ((size_t)1 << lg) - 1) >> lg;
-  if (k > MLHIP_MAX_SEGMENTS) k = MLHIP_MAX_SEGMENTS;
-  return k < 2 ? 1 : (int)k;
+// ---- the steps plan_launch (one pass) and stream_tile / stream_end (a train of segments or tiles) share -------------------
+
+// A folded plan's points are its own table (plan_fold_build): a call brings none of its own, and at most fold_n scalars.
+inline int fold_check_args(const mlhip_msm_plan* p, size_t n, bool points_travel) {
+  if (points_travel || n > p->fold_n || !p->d_points28)
+    return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: the points are the plan's table; more scalars than tabulated bases, or no table");
+  return 0;
 }
 
+// Buckets far longer than the mean (degenerate inputs: equal scalars, tiny scalars) are handed to a whole
+// workgroup each; the threshold scales with the mean length len / 2^(c-1) so that large inputs, and the sparser top
+// window (2-4x the mean for these group orders), stay on the one-thread-per-bucket path.
+// (a folded plan's buckets collect the entries of all Wd digits: the mean is Wd len / 2^(c-1))
+inline uint32_t big_bucket_threshold(const mlhip_msm_plan* p, size_t len) {
+  const uint32_t t = (uint32_t)std::min<size_t>((((size_t)(p->fold ? p->Wd : 1) * len) >> (p->c - 1)) * 8, 1u << 30);
+  return t < BIG_BUCKET_MIN ? BIG_BUCKET_MIN : t;
+}
+
+// `len` points at `src` into the carry-free form the plan accumulates from, at row `dst_row` of d_points28: G2 lane-pair
+// rows, G1 Niels triples (`ed`) or Weierstrass rows.  The caller owns the upload before it, the events around it and the
+// conv_* bookkeeping.
+template <class C, class F>
+void launch_convert(const mlhip_msm_plan* p, const Affine<F>* src, size_t len, size_t dst_row, bool ed, hipStream_t st) {
+  if constexpr (std::is_same<F, Fp2Field<C>>::value) {
+    k_points_to28_g2<C><<<dim3((unsigned)((4 * len + 255) / 256)), dim3(256), 0, st>>>(src, len, (AffineG2_28<C>*)p->d_points28 + dst_row);
+  } else {
+    if constexpr (C::HAS_EDWARDS) {
+      if (ed) {
+        k_points_to_ed28<C><<<dim3((unsigned)(((len + 3) / 4 + 255) / 256)), dim3(256), 0, st>>>(src, len, (EdNiels28<C>*)p->d_points28 + dst_row);
+        return;
+      }
+    }
+    k_points_to28<C><<<dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st>>>(src, len, (Affine28<C>*)p->d_points28 + dst_row);
+  }
+}
+
+// The bucket accumulation of one segment of `len` scalars, and the long-bucket step that belongs to it (k_big_prefix, the
+// slices, the kernel that adds the slice sums): the one place that picks these kernels.
+//   sv        the plan whose entry lists (sorted / offsets / counts / order) describe the segment: p itself, a sort-ahead
+//             helper record, or the G1 plan of a shared-scalar MSM
+//   row0      first carry-free row of the segment in d_points28 (a folded plan: fold_row of its tile)
+//   d_points  the segment's points in the boundary form, read by the boundary-form kernels and the slices of a plain plan
+//             (a folded plan gathers from d_points28 + row0 only: a token)
+//   flags     MLHIP_SEG_FIRST / _LAST / _KEEP28 for the segment kernels
+//   ev_mid    recorded between the accumulation and the long-bucket step (null: no event)
+//   one_pass  the segment is the whole MSM, launched by plan_launch.  What a single pass does differently from a tile:
+template <class C, class F>
+int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, const Affine<F>* d_points, int flags, bool ed,
+                      size_t len, bool one_pass, hipEvent_t ev_mid, hipStream_t st) {
+  typedef XYZZ<F> X;
+  constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;  // two lanes per bucket
+  constexpr int BB = kG2 ? 128 : 256;                        // workgroup of the long-bucket kernels: 48 KB of LDS per block
+  static_assert((sizeof(X) <= 192) == !kG2, "BB * sizeof(X) is 48 KB for both groups");
+  const size_t nbuckets = (size_t)p->W * p->M;
+  const uint32_t big_threshold = big_bucket_threshold(p, len);
+  // (1) a bucket holds at most all len entries (Wd len when folded): a small MSM skips the three near-empty launches of
+  //     the long-bucket step.  A tile always runs them: whether an MSM has long buckets does not show in one tile's length.
+  const bool long_buckets = !one_pass || (size_t)(p->fold ? p->Wd : 1) * len > big_threshold;
+  // (2) too few buckets to fill the chip with one lane each: one bucket per quad of lanes (shorter dependent chains), ahead
+  //     of the Edwards test.  The quad kernel keeps no state between segments, so tiles never use it.
+  const bool quad = !kG2 && one_pass && p->d_points28 && p->reduce28 && nbuckets <= QUAD_ACC_MAX_BUCKETS && !getenv("MLHIP_NO_QUAD_ACC");
+  // (3, 4) the test build's boundary-form buckets (MLHIP_REDUCE32 / MLHIP_REDUCE_ONE_LANE / MLHIP_ACC32): one pass writes
+  //     d_buckets through the kernels without segment state; a tile of such a plan goes through the segment kernels
+  //     without MLHIP_SEG_KEEP28, which leave the boundary form on the last tile.  The product build instantiates none of
+  //     the boundary-form kernels: nothing is launched, and launch_reduce reports the missing bucket state.
+  const bool boundary = one_pass && !(p->reduce28 && p->d_points28);
+  const dim3 grid((unsigned)(((kG2 ? 2 : 1) * nbuckets + p->acc_block - 1) / p->acc_block)), block(p->acc_block);
+  if constexpr (kG2) {
+    typedef XYZZ28L<Fp28<C>> S;
+    const AffineG2_28<C>* rows = (const AffineG2_28<C>*)p->d_points28 + row0;
+    if (boundary) {
+      if constexpr (kBuildAlt) {
+        if (p->d_points28)  // (MLHIP_REDUCE32=1: the buckets leave in the boundary form)
+          k_accumulate28_lp<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                                     big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+        else  // (MLHIP_ACC32=1)
+          k_accumulate_lp<C><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                                   big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+      }
+    } else {
+      bool kc = false;
+      if constexpr (C::BETA == -1 && kBuildAlt) {
+        if (g2_split_by_coordinate()) {
+          k_accumulate28_kc_seg<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                                         big_threshold, p->d_biglist, p->d_bigcount, (S*)p->d_state28, flags,
+                                                         (X*)p->d_buckets);
+          kc = true;
+        }
+      }
+      if (!kc)
+        k_accumulate28_lp_seg<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                                       big_threshold, p->d_biglist, p->d_bigcount, (S*)p->d_state28, flags,
+                                                       (X*)p->d_buckets);
+    }
+  } else if (quad) {
+    k_accumulate_q28<C><<<dim3((unsigned)((4 * nbuckets + 255) / 256)), dim3(256), 0, st>>>(
+        (const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, big_threshold, p->d_biglist,
+        p->d_bigcount, (XYZZ28<C>*)p->d_state28);
+  } else if (ed) {  // (implies reduce28: the last segment leaves XYZZ28 for the reduction)
+    if constexpr (C::HAS_EDWARDS)
+      k_accumulate_ed28_seg<C><<<grid, block, 0, st>>>((const EdNiels28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets,
+                                                     sv->d_counts, nbuckets, sv->d_order, big_threshold, p->d_biglist,
+                                                     p->d_bigcount, (XYZZ28<C>*)p->d_state28, flags);
+  } else if (!boundary) {
+    k_accumulate28_seg<C><<<grid, block, 0, st>>>((const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets,
+                                                sv->d_counts, nbuckets, sv->d_order, big_threshold, p->d_biglist, p->d_bigcount,
+                                                (XYZZ28<C>*)p->d_state28, flags, (X*)p->d_buckets);
+  } else if constexpr (kBuildAlt) {
+    if (p->d_points28)  // (MLHIP_REDUCE32=1 / MLHIP_REDUCE_ONE_LANE=1: the buckets leave in the boundary form)
+      k_accumulate28<C><<<grid, block, 0, st>>>((const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts,
+                                              nbuckets, sv->d_order, big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+    else  // (MLHIP_ACC32=1)
+      k_accumulate<F><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                            big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+  }
+  if (ev_mid) HIPCHK(hipEventRecord(ev_mid, st));
+  if (!long_buckets) return 0;
+  // (5) the slices of a plain plan gather from d_points, those of a folded plan from d_points28 + row0
+  launch_big_slices<F, BB>(p, d_points, st, sv, row0);
+  const dim3 bgrid(256), bblock(BB);
+  const size_t blds = BB * sizeof(X);
+  if (boundary) {
+    if constexpr (kBuildAlt)
+      k_accumulate_big<F, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
+                                                          (X*)p->d_buckets);
+  } else if constexpr (kG2) {
+    k_accumulate_big_seg_g2<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
+                                                               (XYZZ28L<Fp28<C>>*)p->d_state28, flags, (X*)p->d_buckets);
+  } else {
+    if constexpr (C::HAS_EDWARDS) {
+      if (ed) {
+        k_accumulate_big_seg_ed<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix,
+                                                                   (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28, flags);
+        return 0;
+      }
+    }
+    k_accumulate_big_seg<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
+                                                            (XYZZ28<C>*)p->d_state28, flags, (X*)p->d_buckets);
+  }
+  return 0;
+}
+
+// the tail of both sequences: bucket sums -> partial sums -> h_out, then `done` (plan_finish waits for it)
+template <class C, class F>
+int finish_train(mlhip_msm_plan* p, bool prof, hipStream_t st) {
+  if (int rc_red = launch_reduce<C, F>(p, st)) return rc_red;
+  if (prof) HIPCHK(hipEventRecord(p->ev[4], st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(p->h_out, p->d_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(p->done, st));
+  return 0;
+}
+
+// One pass over all n points: "one segment that is first and last" of the train below, with the differences listed at
+// launch_accumulate, and
+//   (6) a host-buffer call's points (upload_src) ride the auxiliary stream ahead of the conversion -- or, without the
+//       carry-free copy and its stream, a blocking copy first;
+//   (7) conv_src / conv_n / conv_ed are set after every conversion (the train clears conv_src at its start unless the copy
+//       is cached, and restores it at its end only for resident, static points);
+//   (8) events: memset of d_zero, then ev[0]; ev[2] once the conversion is queued; ev[3] between the accumulation and the
+//       long buckets (tiles: ev[0] on the first tile ahead of the memset, ev_tile[s][0..2], ev[3] in stream_end);
+//   (9) the wait for ev_join sits immediately before the first kernel that reads the points (tiles: ev_seg / ev_seg_sc).
 template <class C, class F>
 int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, int mont, size_t n, hipStream_t st) {
   typedef Affine<F> A;
-  typedef XYZZ<F> X;
   if (p->fold) {
-    // the points are the plan's own table (plan_fold_build): the caller's point argument only names the bases it was built from
-    if (n > p->fold_n || !p->d_points28 || p->upload_src)
-      return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: more scalars than tabulated bases, or no table");
+    if (int rc_fold = fold_check_args(p, n, p->upload_src != nullptr)) return rc_fold;
     d_points = p->d_points28;  // (never read as Affine<F>: every kernel of a folded plan gathers from the carry-free rows)
   }
   if (n != 0 && !p->upload_src) {
-    const int K = resident_tiles<C, F>(p, n);
+    const int K = resident_tiles(p->aux && p->d_points28, std::is_same<F, Fp2Field<C>>::value, p->fold, p->fold_tile,
+                                 plan_use_edwards<C, F>(p), n);
     if (K > 1)
       return plan_stream<C, F>(p, const_cast<void*>(d_points), const_cast<void*>(d_scalars), nullptr, nullptr, mont, n, K, st);
   }
@@ -510,14 +631,7 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
   p->pending = true;
   p->last_ed = false;
   if (n != 0) {
-    const size_t nbuckets = (size_t)p->W * p->M;
     const bool prof = p->profiling;
-    // Buckets far longer than the mean (degenerate inputs: equal scalars, tiny scalars) are handed to a whole
-    // workgroup each; the threshold scales with the mean length n / 2^(c-1) so that large n, and the sparser top
-    // window (2-4x the mean for these group orders), stay on the one-thread-per-bucket path.
-    // (a folded plan's buckets collect the entries of all Wd digits: the mean is Wd n / 2^(c-1))
-    uint32_t big_threshold = (uint32_t)std::min<size_t>((((size_t)(p->fold ? p->Wd : 1) * n) >> (p->c - 1)) * 8, 1u << 30);
-    if (big_threshold < BIG_BUCKET_MIN) big_threshold = BIG_BUCKET_MIN;
     if (p->upload_src && !p->d_points28) {  // no auxiliary stream on this path: plain upload first
       HIPCHK(hipMemcpy(const_cast<void*>(d_points), p->upload_src, p->upload_bytes, hipMemcpyHostToDevice));
       p->upload_src = nullptr;
@@ -528,10 +642,7 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
     if (p->d_points28) HIPCHK(hipEventRecord(p->ev_fork, st));
     HIPCHK(hipMemsetAsync(p->d_zero, 0, p->zero_bytes, st));
     if (prof) HIPCHK(hipEventRecord(p->ev[0], st));
-    {
-      int rc_sort = launch_sort<C>(p, d_scalars, mont, n, st, prof);
-      if (rc_sort) return rc_sort;
-    }
+    if (int rc_sort = launch_sort<C>(p, d_scalars, mont, n, st, prof)) return rc_sort;
     // resident bases: the carry-free copy of the first conv_n points of this very buffer is already there
     const bool use_ed = p->fold ? p->conv_ed : plan_use_edwards<C, F>(p);  // (a table is read in the form it was built in)
     p->last_ed = use_ed;
@@ -544,139 +655,18 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
         HIPCHK(hipMemcpyAsync(const_cast<void*>(d_points), p->upload_src, p->upload_bytes, hipMemcpyHostToDevice, p->aux));
         p->upload_src = nullptr;
       }
-      if constexpr (std::is_same<F, Fp2Field<C>>::value) {
-        if constexpr (g2_carry_free_v<C>)
-          k_points_to28_g2<C><<<dim3((unsigned)((4 * n + 255) / 256)), dim3(256), 0, p->aux>>>(
-              (const A*)d_points, n, (AffineG2_28<C>*)p->d_points28);
-      } else {
-        bool converted = false;
-        if constexpr (C::HAS_EDWARDS) {
-          if (use_ed) {
-            k_points_to_ed28<C><<<dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, p->aux>>>(
-                (const A*)d_points, n, (EdNiels28<C>*)p->d_points28);
-            converted = true;
-          }
-        }
-        if (!converted)
-          k_points_to28<C><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->aux>>>((const A*)d_points, n,
-                                                                                       (Affine28<C>*)p->d_points28);
-      }
+      launch_convert<C, F>(p, (const A*)d_points, n, 0, use_ed, p->aux);
       HIPCHK(hipEventRecord(p->ev_join, p->aux));
       p->conv_src = d_points;
       p->conv_n = n;
       p->conv_ed = use_ed;
     }
     if (prof) HIPCHK(hipEventRecord(p->ev[2], st));
-    constexpr bool kLanePairs = std::is_same<F, Fp2Field<C>>::value;  // G2: two lanes per bucket
-    if constexpr (kLanePairs) {
-      bool done28 = false;
-      if constexpr (g2_carry_free_v<C>) {
-        if (p->d_points28) {
-          HIPCHK(hipStreamWaitEvent(st, p->ev_join, 0));
-          if constexpr (g2_carry_free_v<C>) {
-            if (p->reduce28) {  // one segment that is first and last, leaving the raw accumulators for k_chunks_lp28
-              const dim3 grid((unsigned)((2 * nbuckets + p->acc_block - 1) / p->acc_block)), block(p->acc_block);
-              bool kc = false;
-              if constexpr (C::BETA == -1 && kBuildAlt) {
-                if (g2_split_by_coordinate()) {
-                  k_accumulate28_kc_seg<C><<<grid, block, 0, st>>>(
-                      (const AffineG2_28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order,
-                      big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28L<Fp28<C>>*)p->d_state28,
-                      MLHIP_SEG_FIRST | MLHIP_SEG_LAST | MLHIP_SEG_KEEP28, (X*)p->d_buckets);
-                  kc = true;
-                }
-              }
-              if (!kc)
-                k_accumulate28_lp_seg<C><<<grid, block, 0, st>>>(
-                    (const AffineG2_28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order,
-                    big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28L<Fp28<C>>*)p->d_state28,
-                    MLHIP_SEG_FIRST | MLHIP_SEG_LAST | MLHIP_SEG_KEEP28, (X*)p->d_buckets);
-              done28 = true;
-            }
-          }
-          if constexpr (kBuildAlt) {  // (MLHIP_REDUCE32=1: the buckets leave in the boundary form)
-            if (!done28)
-              k_accumulate28_lp<C><<<dim3((unsigned)((2 * nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-                  (const AffineG2_28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order,
-                  big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
-          }
-          done28 = true;
-        }
-      }
-      if constexpr (kBuildAlt) {  // (MLHIP_ACC32=1)
-        if (!done28)
-          k_accumulate_lp<C><<<dim3((unsigned)((2 * nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-              (const A*)d_points, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order, big_threshold, p->d_biglist,
-              p->d_bigcount, (X*)p->d_buckets);
-      }
-    } else if (p->d_points28) {
-      HIPCHK(hipStreamWaitEvent(st, p->ev_join, 0));
-      if (p->reduce28 && nbuckets <= QUAD_ACC_MAX_BUCKETS && !getenv("MLHIP_NO_QUAD_ACC"))
-        // too few buckets to fill the chip with one lane each: one bucket per quad of lanes (shorter dependent chains)
-        k_accumulate_q28<C><<<dim3((unsigned)((4 * nbuckets + 255) / 256)), dim3(256), 0, st>>>(
-            (const Affine28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, big_threshold, p->d_biglist,
-            p->d_bigcount, (XYZZ28<C>*)p->d_state28);
-      else if (use_ed) {  // (implies reduce28) the same single segment in twisted Edwards coordinates
-        if constexpr (C::HAS_EDWARDS)
-          k_accumulate_ed28_seg<C><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-              (const EdNiels28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order, big_threshold,
-              p->d_biglist, p->d_bigcount, (XYZZ28<C>*)p->d_state28, MLHIP_SEG_FIRST | MLHIP_SEG_LAST);
-      } else if (p->reduce28)  // one segment that is first and last, leaving the raw accumulators for k_chunks_q28
-        k_accumulate28_seg<C><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-            (const Affine28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order, big_threshold,
-            p->d_biglist, p->d_bigcount, (XYZZ28<C>*)p->d_state28, MLHIP_SEG_FIRST | MLHIP_SEG_LAST | MLHIP_SEG_KEEP28,
-            (X*)p->d_buckets);
-      else if constexpr (kBuildAlt)  // (MLHIP_REDUCE32=1 / MLHIP_REDUCE_ONE_LANE=1: the buckets leave in the boundary form)
-        k_accumulate28<C><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-            (const Affine28<C>*)p->d_points28, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order, big_threshold,
-            p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
-    } else if constexpr (kBuildAlt) {  // (MLHIP_ACC32=1)
-      k_accumulate<F><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-          (const A*)d_points, p->d_sorted, p->d_offsets, p->d_counts, nbuckets, p->d_order, big_threshold, p->d_biglist,
-          p->d_bigcount, (X*)p->d_buckets);
-    }
-    if (prof) HIPCHK(hipEventRecord(p->ev[3], st));
-    if ((size_t)(p->fold ? p->Wd : 1) * n > big_threshold) {  // a bucket holds at most all n entries (Wd n when folded): small MSMs skip three near-empty launches
-      constexpr int BB = sizeof(X) <= 192 ? 256 : 128;  // 48 KB of LDS per block
-      launch_big_slices<F, BB>(p, (const A*)d_points, st);
-      bool folded = false;
-      if constexpr (!kLanePairs) {
-        if constexpr (C::HAS_EDWARDS) {
-          if (use_ed) {
-            k_accumulate_big_seg_ed<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-                p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28,
-                MLHIP_SEG_FIRST | MLHIP_SEG_LAST);
-            folded = true;
-          }
-        }
-        if (!folded && p->reduce28) {
-          k_accumulate_big_seg<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-              p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28,
-              MLHIP_SEG_FIRST | MLHIP_SEG_LAST | MLHIP_SEG_KEEP28, (X*)p->d_buckets);
-          folded = true;
-        }
-      } else if constexpr (g2_carry_free_v<C>) {
-        if (p->reduce28 && p->d_points28) {
-          k_accumulate_big_seg_g2<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-              p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28L<Fp28<C>>*)p->d_state28,
-              MLHIP_SEG_FIRST | MLHIP_SEG_LAST | MLHIP_SEG_KEEP28, (X*)p->d_buckets);
-          folded = true;
-        }
-      }
-      if constexpr (kBuildAlt) {  // (boundary-form buckets)
-        if (!folded)
-          k_accumulate_big<F, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix,
-                                                                                (const X*)p->d_bigpart, (X*)p->d_buckets);
-      }
-    }
-    {
-      int rc_red = launch_reduce<C, F>(p, st);
-      if (rc_red) return rc_red;
-    }
-    if (prof) HIPCHK(hipEventRecord(p->ev[4], st));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(p->h_out, p->d_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * sizeof(X), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(p->done, st));
+    if (p->d_points28) HIPCHK(hipStreamWaitEvent(st, p->ev_join, 0));
+    // (the Edwards kernels always leave XYZZ28 and read no MLHIP_SEG_KEEP28)
+    const int flags = MLHIP_SEG_FIRST | MLHIP_SEG_LAST | (use_ed ? 0 : MLHIP_SEG_KEEP28);
+    if (int rc = launch_accumulate<C, F>(p, p, 0, (const A*)d_points, flags, use_ed, n, true, prof ? p->ev[3] : nullptr, st)) return rc;
+    return finish_train<C, F>(p, prof, st);
   }
   return 0;
 }
@@ -693,17 +683,13 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
 // reach) each gather goes to HBM and the additions wait: 0.139 ns per G1 addition at 2^20-2^21 points, 0.165 at 2^24
 // (profiles/r02_tiles.txt).  A tile of 2^21-2^22 points keeps all W passes over its points near; the bucket
 // accumulators travel through d_state28 between tiles (0.2-0.5 GB per tile, streamed once).
-// one streamed / tiled MSM in flight on a plan: what stream_begin fixes for its tiles
-struct StreamCtx {
+// one streamed / tiled MSM in flight on a plan: what stream_begin fixes for its tiles (the cuts: msm_segments.h)
+struct StreamCtx : SegmentCuts {
   void* d_points = nullptr;
   void* d_scalars = nullptr;
   const void* h_points = nullptr;
   const void* h_scalars = nullptr;
   int mont = 0;
-  size_t n = 0, seg = 0;  // seg: the longest segment (what a sort-ahead helper record must hold)
-  int K = 0;
-  size_t bound[MLHIP_MAX_SEGMENTS + 1] = {};  // segment s = pairs [bound[s], bound[s + 1])
-  bool scheduled = false;                     // bound[] was filled by the caller (stream_schedule); else K equal segments
   bool resident = false, conv_cached = false, prof = false;
   bool ed = false;  // the buckets are summed in twisted Edwards coordinates (plan_use_edwards)
 };
@@ -717,10 +703,6 @@ int stream_begin(mlhip_msm_plan* p, StreamCtx& cx, hipStream_t st, int min_K) {
   if (cx.n == 0 || cx.K < min_K || cx.K > MLHIP_MAX_SEGMENTS) return mlhip_rt::fail(MLHIP_EINVAL, "bad segment count");
   const size_t nbuckets = (size_t)p->W * p->M;
   if (!p->d_state28) HIPCHK(hipMalloc(&p->d_state28, nbuckets * kStateBytes));
-  for (int s = 0; s < cx.K; s++) {
-    if (!p->ev_seg[s]) HIPCHK(hipEventCreateWithFlags(&p->ev_seg[s], hipEventDisableTiming));
-    if (cx.h_scalars && cx.h_points && !p->ev_seg_sc[s]) HIPCHK(hipEventCreateWithFlags(&p->ev_seg_sc[s], hipEventDisableTiming));
-  }
   // resident points (h_points == nullptr): only the scalars travel (or nothing: h_scalars == nullptr); their carry-free
   // copy is either the plan's (resident bases) or made tile by tile
   cx.resident = cx.h_points == nullptr;
@@ -728,57 +710,23 @@ int stream_begin(mlhip_msm_plan* p, StreamCtx& cx, hipStream_t st, int min_K) {
   p->last_ed = cx.ed;
   cx.conv_cached = cx.resident && p->points_static && p->conv_src == cx.d_points && cx.n <= p->conv_n && p->conv_ed == cx.ed;
   if (p->fold) {
-    if (!cx.resident || cx.n > p->fold_n || !p->d_points28)
-      return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: the points are the plan's table; more scalars than tabulated bases");
+    if (int rc_fold = fold_check_args(p, cx.n, !cx.resident)) return rc_fold;
     cx.conv_cached = true;
     cx.d_points = p->d_points28;  // (a token: never read as Affine<F>)
   }
   cx.prof = p->profiling && cx.h_scalars == nullptr;  // tiles of device-resident inputs: per-tile phase events
-  if (cx.prof)
-    for (int s = 0; s < cx.K; s++)
-      for (int j = 0; j < 3; j++)
-        if (!p->ev_tile[s][j]) HIPCHK(hipEventCreate(&p->ev_tile[s][j]));
-  p->tiles_timed = cx.prof ? cx.K : -1;  // -1: a streamed host-buffer MSM records no phase events
   p->pending_n = cx.n;
   p->pending = true;
   if (!cx.conv_cached) p->conv_src = nullptr;  // the carry-free copy is being rewritten
-  if (!cx.scheduled) {
-    const size_t seg = (cx.n + cx.K - 1) / cx.K;
-    int k = 0;
-    for (size_t off = 0; off < cx.n; off += seg) cx.bound[k++] = off;
-    cx.bound[k] = cx.n;
-    cx.K = k;
+  if (!segment_cuts(cx, p->fold, p->fold_tile)) return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: too many tiles");
+  for (int s = 0; s < cx.K; s++) {  // the events of the segments as cut
+    if (!p->ev_seg[s]) HIPCHK(hipEventCreateWithFlags(&p->ev_seg[s], hipEventDisableTiming));
+    if (cx.h_scalars && cx.h_points && !p->ev_seg_sc[s]) HIPCHK(hipEventCreateWithFlags(&p->ev_seg_sc[s], hipEventDisableTiming));
+    if (cx.prof)
+      for (int j = 0; j < 3; j++)
+        if (!p->ev_tile[s][j]) HIPCHK(hipEventCreate(&p->ev_tile[s][j]));
   }
-  if (p->fold) {
-    // no segment may cross a tile of the table: cut at the tile boundaries; if that makes too many segments, fall back to
-    // the tiles themselves
-    if ((cx.n + p->fold_tile - 1) / p->fold_tile > MLHIP_MAX_SEGMENTS) return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: too many tiles");
-    size_t b[2 * MLHIP_MAX_SEGMENTS + 2];
-    int m = 0;
-    b[0] = 0;
-    for (int s2 = 0; s2 < cx.K; s2++) {
-      const size_t hi = cx.bound[s2 + 1];
-      for (size_t t = (b[m] / p->fold_tile + 1) * p->fold_tile; t < hi; t += p->fold_tile) b[++m] = t;
-      b[++m] = hi;
-    }
-    if (m > MLHIP_MAX_SEGMENTS) {
-      m = 0;
-      for (size_t t = p->fold_tile; t < cx.n; t += p->fold_tile) b[++m] = t;
-      b[++m] = cx.n;
-      if (m > MLHIP_MAX_SEGMENTS) return mlhip_rt::fail(MLHIP_EINVAL, "folded plan: too many tiles");
-    }
-    for (int s2 = 0; s2 <= m; s2++) cx.bound[s2] = b[s2];
-    cx.K = m;
-    for (int s2 = 0; s2 < cx.K; s2++) {  // (events of the segments the cut added)
-      if (!p->ev_seg[s2]) HIPCHK(hipEventCreateWithFlags(&p->ev_seg[s2], hipEventDisableTiming));
-      if (cx.prof)
-        for (int j = 0; j < 3; j++)
-          if (!p->ev_tile[s2][j]) HIPCHK(hipEventCreate(&p->ev_tile[s2][j]));
-    }
-    if (cx.prof) p->tiles_timed = cx.K;
-  }
-  cx.seg = 0;
-  for (int s2 = 0; s2 < cx.K; s2++) cx.seg = std::max(cx.seg, cx.bound[s2 + 1] - cx.bound[s2]);
+  p->tiles_timed = cx.prof ? cx.K : -1;  // -1: a streamed host-buffer MSM records no phase events
   HIPCHK(hipEventRecord(p->ev_fork, st));  // the staging buffers are free once the work queued before us is done
   HIPCHK(hipStreamWaitEvent(p->aux, p->ev_fork, 0));
   return 0;
@@ -790,9 +738,6 @@ int stream_begin(mlhip_msm_plan* p, StreamCtx& cx, hipStream_t st, int min_K) {
 template <class C, class F>
 int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, const mlhip_msm_plan* sorter) {
   typedef Affine<F> A;
-  typedef XYZZ<F> X;
-  constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;
-  const size_t nbuckets = (size_t)p->W * p->M;
   const size_t off = cx.bound[s];
   const size_t len = cx.bound[s + 1] - off;
   const bool first = off == 0, last = off + len >= cx.n;
@@ -810,22 +755,7 @@ int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, c
   if (split) HIPCHK(hipEventRecord(p->ev_seg_sc[s], p->aux));
   if (!cx.conv_cached) {
     if (!cx.resident) HIPCHK(hipMemcpyAsync(dpt, hp + off * sizeof(A), len * sizeof(A), hipMemcpyHostToDevice, p->aux));
-    if constexpr (kG2)
-      k_points_to28_g2<C><<<dim3((unsigned)((4 * len + 255) / 256)), dim3(256), 0, p->aux>>>(
-          dpt, len, (AffineG2_28<C>*)p->d_points28 + off);
-    else {
-      bool converted = false;
-      if constexpr (C::HAS_EDWARDS) {
-        if (cx.ed) {
-          k_points_to_ed28<C><<<dim3((unsigned)(((len + 3) / 4 + 255) / 256)), dim3(256), 0, p->aux>>>(
-              dpt, len, (EdNiels28<C>*)p->d_points28 + off);
-          converted = true;
-        }
-      }
-      if (!converted)
-        k_points_to28<C><<<dim3((unsigned)((len + 255) / 256)), dim3(256), 0, p->aux>>>(dpt, len,
-                                                                                       (Affine28<C>*)p->d_points28 + off);
-    }
+    launch_convert<C, F>(p, dpt, len, off, cx.ed, p->aux);
   }
   HIPCHK(hipEventRecord(p->ev_seg[s], p->aux));
   if (prof && first) HIPCHK(hipEventRecord(p->ev[0], st));
@@ -839,75 +769,20 @@ int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, c
   }
   if (!uploads || split) HIPCHK(hipStreamWaitEvent(st, p->ev_seg[s], 0));  // only the accumulation waits for points / conversion
   if (prof) HIPCHK(hipEventRecord(p->ev_tile[s][1], st));
-  const mlhip_msm_plan* sv = sorter ? sorter : p;  // whose entry lists the kernels read
-  uint32_t big_threshold = (uint32_t)std::min<size_t>((((size_t)(p->fold ? p->Wd : 1) * len) >> (p->c - 1)) * 8, 1u << 30);
-  if (big_threshold < BIG_BUCKET_MIN) big_threshold = BIG_BUCKET_MIN;
-  if constexpr (kG2) {
-    const dim3 grid((unsigned)((2 * nbuckets + p->acc_block - 1) / p->acc_block)), block(p->acc_block);
-    bool kc = false;
-    if constexpr (C::BETA == -1 && kBuildAlt) {
-      if (g2_split_by_coordinate()) {
-        k_accumulate28_kc_seg<C><<<grid, block, 0, st>>>(
-            (const AffineG2_28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-            big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28L<Fp28<C>>*)p->d_state28, flags, (X*)p->d_buckets);
-        kc = true;
-      }
-    }
-    if (!kc)
-      k_accumulate28_lp_seg<C><<<grid, block, 0, st>>>(
-          (const AffineG2_28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-          big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28L<Fp28<C>>*)p->d_state28, flags, (X*)p->d_buckets);
-    constexpr int BB = 128;
-    launch_big_slices<F, BB>(p, dpt, st, sv, row0);
-    k_accumulate_big_seg_g2<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-        p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28L<Fp28<C>>*)p->d_state28, flags,
-        (X*)p->d_buckets);
-  } else {
-    constexpr int BB = 256;
-    bool done_ed = false;
-    if constexpr (C::HAS_EDWARDS) {
-      if (cx.ed) {  // (implies MLHIP_SEG_KEEP28: the last tile leaves XYZZ28 for the reduction)
-        k_accumulate_ed28_seg<C><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-            (const EdNiels28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-            big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28<C>*)p->d_state28, flags);
-        launch_big_slices<F, BB>(p, dpt, st, sv, row0);
-        k_accumulate_big_seg_ed<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-            p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28, flags);
-        done_ed = true;
-      }
-    }
-    if (!done_ed) {
-      k_accumulate28_seg<C><<<dim3((unsigned)((nbuckets + p->acc_block - 1) / p->acc_block)), dim3(p->acc_block), 0, st>>>(
-          (const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-          big_threshold, p->d_biglist, p->d_bigcount, (XYZZ28<C>*)p->d_state28, flags, (X*)p->d_buckets);
-      launch_big_slices<F, BB>(p, dpt, st, sv, row0);
-      k_accumulate_big_seg<C, BB><<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(
-          p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28, flags,
-          (X*)p->d_buckets);
-    }
-  }
+  if (int rc = launch_accumulate<C, F>(p, sorter ? sorter : p, row0, dpt, flags, cx.ed, len, false, nullptr, st)) return rc;
   if (prof) HIPCHK(hipEventRecord(p->ev_tile[s][2], st));
   return 0;
 }
 
 template <class C, class F>
 int stream_end(mlhip_msm_plan* p, const StreamCtx& cx, hipStream_t st) {
-  typedef XYZZ<F> X;
   if (cx.resident && !cx.conv_cached && p->points_static) {  // every tile was converted: the copy is whole again
     p->conv_src = cx.d_points;
     p->conv_n = cx.n;
     p->conv_ed = cx.ed;
   }
   if (cx.prof) HIPCHK(hipEventRecord(p->ev[3], st));
-  {
-    int rc_red = launch_reduce<C, F>(p, st);
-    if (rc_red) return rc_red;
-  }
-  if (cx.prof) HIPCHK(hipEventRecord(p->ev[4], st));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(p->h_out, p->d_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * sizeof(X), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(p->done, st));
-  return 0;
+  return finish_train<C, F>(p, cx.prof, st);
 }
 
 // ---- sorting ahead (round 3) ----------------------------------------------------------------------------------------------
@@ -993,81 +868,6 @@ int sort_ahead_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s) {
   return 0;
 }
 
-// Segment schedule of a host-buffer MSM (round 4; profiles/r04_hostapi.txt, same-box A/Bs at 2^20 pairs).  K equal
-// segments expose the whole first upload and pay the per-segment costs (a sort train, one round trip of the bucket state,
-// two pageable copies, shorter bucket lists) K times.  What bounds the call differs between the two host protocols:
-//   (b) resident bases, only the 32-byte scalars travel -- a fifth of the kernels' time: TWO segments, 3 and 13 sixteenths of
-//       the call; the second upload hides under the first segment's kernels and only one extra sort train is paid:
-//       3.37 -> 3.23 ms against four equal segments, 0.02 ms above the resident MSM of the same box;
-//   (c) points and scalars travel, 128 B a pair -- the copies (2.35 ms) run at about the kernels' rate (2.6 ms), so a later
-//       segment may be at most ~1.1x the one before or the kernels wait for it, and every extra segment costs ~0.1 ms:
-//       growing schedules LOSE (1,1,2,3,4,5: 4.28 ms; 2,3,5,6: 4.24; 1,2,2,3,4,4: 4.09) against four equal segments (3.99) --
-//       equal segments of 2^18 pairs stay.  (What round 4 did gain for (c) is the split event: a segment's sort starts on
-//       its scalars, under the upload of its points -- stream_tile.)
-// MLHIP_STREAM_SCHEDULE="w0,w1,..." (weights, at most MLHIP_MAX_SEGMENTS) overrides; MLHIP_STREAM_SEGMENTS = K keeps K equal
-// segments (what the tests use to force many segments on small inputs).
-inline void stream_schedule(StreamCtx& cx, bool points_travel, size_t tile, bool fold_tiles = false) {
-  int w[MLHIP_MAX_SEGMENTS];
-  int k = 0;
-  if (const char* e = getenv("MLHIP_STREAM_SCHEDULE")) {
-    for (const char* q = e; *q && k < MLHIP_MAX_SEGMENTS;) {
-      const int v = atoi(q);
-      if (v > 0) w[k++] = v;
-      while (*q && *q != ',') q++;
-      if (*q == ',') q++;
-    }
-  } else if (getenv("MLHIP_STREAM_SEGMENTS")) {
-    return;  // K equal segments
-  } else if (fold_tiles && cx.n > tile && !points_travel) {
-    // a folded plan with several tiles: 3 x 2^16 pairs, the rest of the first tile, then the tiles (a segment cannot cross one)
-    const size_t first = (size_t)3 << 16;
-    int m = 0;
-    cx.bound[0] = 0;
-    if (tile > 2 * first) cx.bound[++m] = first;
-    for (size_t t = tile; t < cx.n && m + 1 < MLHIP_MAX_SEGMENTS; t += tile) cx.bound[++m] = t;
-    cx.bound[++m] = cx.n;
-    cx.K = m;
-    cx.scheduled = true;
-    return;
-  } else if (cx.n >= ((size_t)1 << 20) && !points_travel) {
-    // resident bases: 3 x 2^16 pairs first, then segments that grow fourfold (the scalars of the next segment -- 0.6 ns a
-    // pair on the wire -- must arrive within the kernels of this one -- 2.5 ns a pair) up to one tile (2^21 pairs: what keeps
-    // a segment's W passes over its points near the chip, resident_tiles); a remainder shorter than the first segment joins
-    // the segment before it.  2^20: 3 | 13 sixteenths; 2^21: 0.19 | 0.75 | 1.06 M; 2^22: 0.19 | 0.75 | 2.0 | 1.06 M.
-    const size_t first = (size_t)3 << 16;
-    size_t off = 0, len = first;
-    int m = 0;
-    cx.bound[0] = 0;
-    while (off < cx.n && m < MLHIP_MAX_SEGMENTS) {
-      size_t take = std::min(len, cx.n - off);
-      if (cx.n - off - take < first || m + 1 == MLHIP_MAX_SEGMENTS) take = cx.n - off;  // no crumb at the end
-      off += take;
-      cx.bound[++m] = off;
-      len = std::min(len * 4, tile);
-    }
-    if (m >= 2) {
-      cx.K = m;
-      cx.scheduled = true;
-    }
-    return;
-  }
-  if (k < 2) return;
-  long long total = 0;
-  for (int i = 0; i < k; i++) total += w[i];
-  size_t cum = 0;
-  int m = 0;
-  cx.bound[0] = 0;
-  for (int i = 0; i < k; i++) {
-    cum += (size_t)w[i];
-    size_t b = i + 1 == k ? cx.n : ((size_t)((unsigned __int128)cx.n * cum / (size_t)total) + 1023) / 1024 * 1024;
-    if (b > cx.n) b = cx.n;
-    if (b > cx.bound[m]) cx.bound[++m] = b;
-  }
-  if (m < 2) return;
-  cx.K = m;
-  cx.scheduled = true;
-}
-
 template <class C, class F>
 int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,
                 size_t n, int K, hipStream_t st) {
@@ -1080,8 +880,7 @@ int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* 
   cx.n = n;
   cx.K = K;
   if (h_scalars && std::is_same<F, FpField<C>>::value)
-    stream_schedule(cx, h_points != nullptr,
-                    p->fold ? p->fold_tile : (size_t)1 << (plan_use_edwards<C, F>(p) ? 20 : 21), p->fold != 0);  // the tile of resident_tiles
+    stream_schedule(cx, h_points != nullptr, schedule_tile(p->fold, p->fold_tile, plan_use_edwards<C, F>(p)), p->fold != 0);
   int rc = stream_begin<C, F>(p, cx, st, 2);
   if (rc) return rc;
   bool ahead = false;
@@ -1117,23 +916,7 @@ int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1
   if (p1->c != p2->c || p1->W != p2->W || p1->M != p2->M)
     return mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width");
   if (p1->fold || p2->fold) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
-  int K = 1;
-  if (h_scalars) {
-    // uploads to hide: segments of 2^17 pairs, as a host-buffer G2 MSM (api_msm.hip: stream_segments)
-    K = (int)std::min<size_t>(std::max<size_t>(n >> 17, 1), MLHIP_MAX_SEGMENTS);
-    if (const char* e = getenv("MLHIP_STREAM_SEGMENTS")) {
-      const int v = atoi(e);
-      K = v < 2 ? 1 : (int)std::min<size_t>(std::min<size_t>((size_t)v, n), MLHIP_MAX_SEGMENTS);
-    }
-  } else {
-    // tiles of 2^20 pairs from 2^22 on (see resident_tiles: G1 gains from 2^22, G2 from 2^23, neither loses)
-    if (n >= ((size_t)1 << 22)) K = (int)std::min<size_t>((n + ((size_t)1 << 20) - 1) >> 20, MLHIP_MAX_SEGMENTS);
-    if (const char* e = getenv("MLHIP_TILE_LOG2")) {
-      const int v = atoi(e);
-      K = 1;
-      if (v > 0 && v < 31 && n > ((size_t)1 << v)) K = (int)std::min<size_t>((n + ((size_t)1 << v) - 1) >> v, MLHIP_MAX_SEGMENTS);
-    }
-  }
+  const int K = shared_segments(h_scalars != nullptr, n);
   StreamCtx c1, c2;
   c1.d_points = d_points_g1;
   c2.d_points = d_points_g2;

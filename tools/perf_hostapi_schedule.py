@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the segment schedules of a host-buffer G1 MSM (msm_plan.h: stream_schedule): protocol (c) mlhip_msm_g1
+"""Same-box A/B of the segment schedules of a host-buffer G1 MSM (msm_segments.h: stream_schedule): protocol (c) mlhip_msm_g1
 (points and scalars from host memory) and protocol (b) mlhip_bases_msm (resident bases, scalars from host memory), beside
 the resident MSM (a) of the same inputs.  MLHIP_STREAM_SEGMENTS=K = K equal segments (rounds 1-3), MLHIP_STREAM_SCHEDULE =
 explicit weights, neither = the library's schedule.  Usage: perf_hostapi_schedule.py [log2 n = 20] [curve]"""

@@ -84,7 +84,7 @@ while time.time() - t0 < budget:
         # half of the calls stream the pairs in a random number of segments (the library reads the switch per call)
         segs = rnd.choice([0, 0, 0, 2, 3, 5, 16])
         os.environ["MLHIP_STREAM_SEGMENTS"] = str(segs)
-        # round 4: segments of unequal length (msm_plan.h: stream_schedule; it takes precedence over the count above)
+        # round 4: segments of unequal length (msm_segments.h: stream_schedule; it takes precedence over the count above)
         os.environ.pop("MLHIP_STREAM_SCHEDULE", None)
         if rnd.random() < 0.3:
             os.environ["MLHIP_STREAM_SCHEDULE"] = ",".join(str(rnd.randrange(1, 9)) for _ in range(rnd.randrange(2, 8)))
