@@ -61,14 +61,16 @@ var WindowC = 0
 var MinDeviceMSM = 32
 
 // MinDeviceMSMBatch: MultiScalarMulBatch / Mul2Batch with fewer pairs in all stay on the embedded gurvy driver;
-// MaxBatchSegment: a segment of this many pairs or more is sent to MultiScalarMul on its own.  Measured with
-// tools/perf_msm_batch.py (profiles/msm_batch_grid.jsonl, DESIGN.md section 8): a batch call costs the device 3-7 ms
-// while it is not filled, and the C restatement on the GPU box's 16 cores needs 12-47 ms for 2 048 pairs; as for
-// MinDeviceMSM, gnark itself cannot be timed here, and its ADX code being several times faster than that port puts the
-// break-even near 2^11 pairs.  A single mlhip_msm_g1 call of 2^14 pairs (0.72 ms) costs about what those pairs cost
-// inside a full batch (1.8-2.5e7 pairs/s).
+// MaxBatchSegment: a segment of this many pairs or more is sent to MultiScalarMul on its own.  MinDeviceMSMBatch was
+// measured with tools/perf_msm_batch.py (profiles/msm_batch_grid.jsonl, DESIGN.md section 8): a batch call costs the
+// device 3-7 ms while it is not filled, and the C restatement on the GPU box's 16 cores needs 12-47 ms for 2 048 pairs; as
+// for MinDeviceMSM, gnark itself cannot be timed here, and its ADX code being several times faster than that port puts the
+// break-even near 2^11 pairs.  MaxBatchSegment follows tools/perf_msm_batch_bucket.py (profiles/msm_batch_bucket_ab.txt):
+// the library sends segments of 512 pairs or more through its bucket route, and with it one batch call of 2^14-pair
+// segments is level with or ahead of as many single mlhip_msm_g1 calls (BLS12-381: 11.8 against 12.1 ms for 16 of them,
+// 25 against 47 ms for 64); from 2^16 pairs per segment on the single calls are ahead in every measured cell.
 var MinDeviceMSMBatch = 2048
-var MaxBatchSegment = 16384
+var MaxBatchSegment = 65536
 
 // MinDevicePairingBatch: PairingBatch with fewer pairs stays on the embedded gurvy driver.  Any batch up to 16 384
 // pairs costs one wave time on the device (5.2 ms on an MI355X, one pairing per quad of lanes:
@@ -153,7 +155,7 @@ func (c *Curve) MultiScalarMul(a []driver.G1, b []driver.Zr) driver.G1 {
 }
 
 // MultiScalarMulBatch returns MultiScalarMul(a[i], b[i]) for every i -- an idemix / BBS verifier's many small MSMs --
-// with one device call (mlhip_msm_batch: chunks of a few pairs per lane, DESIGN.md section 8).  Every segment keeps
+// with one device call (mlhip_msm_batch: chunks of a few pairs per lane, buckets for long segments, DESIGN.md section 8).  Every segment keeps
 // MultiScalarMul's rules: fewer scalars than points panics (index out of range, math.go:960-969), more gives the
 // identity.  A batch of fewer than MinDeviceMSMBatch pairs in all stays on the embedded gurvy driver, and a segment of
 // MaxBatchSegment pairs or more goes to MultiScalarMul on its own (mlhip_msm_g1 is faster there).

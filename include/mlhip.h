@@ -230,8 +230,17 @@ MLHIP_API int mlhip_scalar_mul(int curve, int group, const void* points, size_t 
  * Every segment is cut into chunks of at most P pairs, one lane (G1) or lane pair (G2) per chunk runs an interleaved
  * signed 4-bit-window double-and-add (256 / P + 71 group operations per pair), and the chunk sums of each segment are
  * added in passes of at most 32 per lane.  P = 4 (MLHIP_MSM_BATCH_CHUNK = 1, 2, 4 or 8 overrides; below ~2^17 pairs in all
- * the device is not filled and P = 1 is faster).  Meant for segments of
- * 2 to a few hundred pairs: a long segment is exact but slower than mlhip_msm_g1 on it.
+ * the device is not filled and P = 1 is faster).
+ * G1 segments of MLHIP_MSM_BATCH_BUCKET_MIN pairs or more (default 512; 0 = never, 1 .. 8 mean 9) take a bucket route
+ * instead: slices of at most S pairs, 7-bit signed windows, one wave per (slice, window) with one bucket per lane, an
+ * in-wave reduction and one Horner lane per slice; the slice sums join the chunk sums of the passes above.  S is the
+ * largest power of two from 256 to 4096 that still gives 4096 waves (MLHIP_MSM_BATCH_BUCKET_SLICE=s fixes it).  Same bytes
+ * as the chunks for every input (infinities, repeated points, P beside -P, points outside the subgroup).  Scratch: 37
+ * bytes per pair of a slice + 37 XYZZ per slice; a call that would need more than 1 GiB of it runs chunks only.  Measured
+ * (profiles/msm_batch_bucket_ab.txt): from 2^18 pairs per call on, 1.2-1.5x the chunks at 512 pairs per
+ * segment and 1.4-2.1x from 1024 on; a batch of 16 384-pair segments is level with or ahead of single mlhip_msm_g1 calls,
+ * from 65 536 pairs per segment on single calls are ahead.  G2, and the table-free path of mlhip_bases_msm_batch*, keep
+ * the chunks: a long segment there is exact but slower than mlhip_msm_g2 on it.
  * Runs on the first listed device.  Device pointers; the offsets are read on the host. */
 MLHIP_API int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
                                      const uint64_t* offsets, size_t k, void* d_out_affine, void* stream);
@@ -440,6 +449,9 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
  *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
+ *     MLHIP_MSM_BATCH_BUCKET_MIN=n     mlhip_msm_batch* G1: segments of n pairs or more take the bucket route (default 512;
+ *                                      0 = never, 1 .. 8 mean 9)
+ *     MLHIP_MSM_BATCH_BUCKET_SLICE=s   ... pairs per slice of such a segment (default: 256 .. 4096 by the size of the batch)
  *     MLHIP_SUM_DEVICE_MIN=n           mlhip_g1_sum / mlhip_g2_sum: smallest list summed on the device (0 = never, 1 = always;
  *                                      default 2^14 G1 / 2^12 G2)
  *     MLHIP_BASES_BATCH_WINDOW=w, MLHIP_BASES_BATCH_CHUNK=P   mlhip_bases_msm_batch*: table width 4 .. 12 (default 12), pairs

@@ -298,7 +298,7 @@ int bases_batch_device(mlhip_bases_batch_tables* t, const void* d_pts, size_t n_
   if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: more than 2^32 - 1 chunks");
   const size_t index_bytes = base_index ? (size_t)offsets[k] * 4 : 0;
   return msm_batch_run<C, F>(L, base_index, index_bytes, d_out, st,
-                             [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void* d_extra, void* part) {
+                             [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void* d_extra, void* part, void*) {
     const uint32_t* d_index = base_index ? (const uint32_t*)d_extra : nullptr;
     if (tabled) {
       if constexpr (kG1)

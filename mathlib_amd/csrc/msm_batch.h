@@ -46,7 +46,10 @@ struct MsmBatchLayout {
 };
 
 // false: the chunk or group indices do not fit 32 bits.  offsets must have been checked (0 first, nondecreasing).
-inline bool msm_batch_layout(MsmBatchLayout& L, const uint64_t* offsets, size_t k, int P, int G = MSM_BATCH_GROUP) {
+// chunk_len(m) = the chunk length of a segment of m pairs (msm_batch_layout: P for every segment; msm_batch_bucket.h: the
+// slice length for the long ones)
+template <class ChunkLen>
+inline bool msm_batch_layout_by(MsmBatchLayout& L, const uint64_t* offsets, size_t k, int G, ChunkLen chunk_len) {
   L.chunks.clear();
   L.groups.clear();
   L.pass_begin.assign(1, 0);
@@ -54,9 +57,9 @@ inline bool msm_batch_layout(MsmBatchLayout& L, const uint64_t* offsets, size_t 
   std::vector<uint64_t> n(k);  // partials per segment in the current pass's input
   for (size_t s = 0; s < k; s++) {
     const uint64_t a = offsets[s], b = offsets[s + 1];
-    n[s] = (b - a + (uint64_t)P - 1) / (uint64_t)P;
-    for (uint64_t f = a; f < b; f += (uint64_t)P)
-      L.chunks.push_back({f, (uint32_t)(b - f < (uint64_t)P ? b - f : (uint64_t)P), (uint32_t)(f - a)});
+    const uint64_t P = chunk_len(b - a);
+    n[s] = (b - a + P - 1) / P;
+    for (uint64_t f = a; f < b; f += P) L.chunks.push_back({f, (uint32_t)(b - f < P ? b - f : P), (uint32_t)(f - a)});
   }
   if (L.chunks.size() >= ((uint64_t)1 << 32)) return false;
   for (;;) {
@@ -80,6 +83,9 @@ inline bool msm_batch_layout(MsmBatchLayout& L, const uint64_t* offsets, size_t 
     L.max_mid = mid > L.max_mid ? mid : L.max_mid;
   }
   return true;
+}
+inline bool msm_batch_layout(MsmBatchLayout& L, const uint64_t* offsets, size_t k, int P, int G = MSM_BATCH_GROUP) {
+  return msm_batch_layout_by(L, offsets, k, G, [P](uint64_t) { return (uint64_t)P; });
 }
 
 // group operations of the per-lane bodies below: the plain formulas (host replay); the kernels pass their own
@@ -181,6 +187,7 @@ __global__ void __launch_bounds__(64) k_msm_batch_chunk(const Affine<FpField<C>>
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_chunks) return;
   const MsmBatchChunk ch = chunks[c];
+  if (ch.count > (uint32_t)P) return;  // a slice of a long segment: the bucket kernels write this row (msm_batch_bucket.h)
   const Affine<F>* pts = points + ch.first;
   XYZZ<F> acc;
   msm_batch_chunk<F, P, MsmBatchOpsG1<F>>(acc, scalars + 8 * ch.first, ch.count, mont != 0,
@@ -301,16 +308,19 @@ void msm_batch_launch_chunks(const void* d_points, const void* d_scalars, int mo
 }
 
 // the passes of one batch call over a built layout: one upload of [chunk table | groups | extra] on the call's stream,
-// launch(d_chunks, n_chunks, d_extra, d_partials) queues the chunk kernel (n_chunks >= 1), then the sum passes write the k
-// affine results.  extra: extra_bytes of host data the chunk kernel reads (the base indices of mlhip_bases_msm_batch)
+// launch(d_chunks, n_chunks, d_extra, d_partials, d_scratch) queues the chunk kernel (n_chunks >= 1), then the sum passes
+// write the k affine results.  extra: extra_bytes of host data the chunk kernel reads (the base indices of
+// mlhip_bases_msm_batch, the slice rows of msm_batch_bucket.h); d_scratch: scratch_bytes more of the buffer, 256-byte aligned
 template <class C, class F, class Launch>
-int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes, void* d_out, hipStream_t st, Launch launch) {
+int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes, void* d_out, hipStream_t st, Launch launch,
+                  size_t scratch_bytes = 0) {
   constexpr bool kG1 = std::is_same<F, FpField<C>>::value;
   const size_t n_chunks = L.chunks.size(), n_groups = L.groups.size();
   const size_t chunk_bytes = n_chunks * sizeof(MsmBatchChunk), group_bytes = n_groups * sizeof(MsmBatchGroup);
   const size_t meta = (chunk_bytes + group_bytes + extra_bytes + 255) & ~(size_t)255;
   const size_t a_bytes = ((n_chunks * sizeof(XYZZ<F>)) + 255) & ~(size_t)255;
-  const size_t need = meta + a_bytes + L.max_mid * sizeof(XYZZ<F>);
+  const size_t b_bytes = ((L.max_mid * sizeof(XYZZ<F>)) + 255) & ~(size_t)255;
+  const size_t need = meta + a_bytes + b_bytes + scratch_bytes;
   std::vector<char> host(chunk_bytes + group_bytes + extra_bytes);
   if (chunk_bytes) memcpy(host.data(), L.chunks.data(), chunk_bytes);
   memcpy(host.data() + chunk_bytes, L.groups.data(), group_bytes);
@@ -335,7 +345,9 @@ int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes
   const MsmBatchChunk* d_chunks = (const MsmBatchChunk*)mb.buf;
   const MsmBatchGroup* d_groups = (const MsmBatchGroup*)(mb.buf + chunk_bytes);
   void* bufs[2] = {mb.buf + meta, mb.buf + meta + a_bytes};
-  if (n_chunks) launch(d_chunks, (uint32_t)n_chunks, (const void*)(mb.buf + chunk_bytes + group_bytes), bufs[0]);
+  if (n_chunks)
+    launch(d_chunks, (uint32_t)n_chunks, (const void*)(mb.buf + chunk_bytes + group_bytes), bufs[0],
+           (void*)(mb.buf + meta + a_bytes + b_bytes));
   const size_t passes = L.pass_begin.size() - 1;
   for (size_t q = 0; q < passes; q++) {
     const bool last = q + 1 == passes;
@@ -355,20 +367,27 @@ int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes
   return 0;
 }
 
-// offsets: k + 1 checked host entries (api_msm.hip: mlhip_msm_batch_device), k >= 1
+// the chunk kernel of the compiled chunk length P
+template <class C, class F>
+void msm_batch_launch_chunks_p(int P, const void* d_points, const void* d_scalars, int mont, const MsmBatchChunk* d_chunks,
+                               uint32_t n_chunks, void* d_partials, hipStream_t st) {
+  switch (P) {
+    case 1: msm_batch_launch_chunks<C, F, 1>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
+    case 2: msm_batch_launch_chunks<C, F, 2>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
+    case 4: msm_batch_launch_chunks<C, F, 4>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
+    default: msm_batch_launch_chunks<C, F, 8>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
+  }
+}
+
+// Straus chunks for every segment.  offsets: k + 1 checked host entries (api_msm.hip: mlhip_msm_batch_device), k >= 1
 template <class C, class F>
 int msm_batch_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
                      hipStream_t st) {
   const int P = msm_batch_chunk_len<C, F>();
   MsmBatchLayout L;
   if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: more than 2^32 - 1 chunks");
-  return msm_batch_run<C, F>(L, nullptr, 0, d_out, st, [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void*, void* part) {
-    switch (P) {
-      case 1: msm_batch_launch_chunks<C, F, 1>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
-      case 2: msm_batch_launch_chunks<C, F, 2>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
-      case 4: msm_batch_launch_chunks<C, F, 4>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
-      default: msm_batch_launch_chunks<C, F, 8>(d_points, d_scalars, mont, d_chunks, n_chunks, part, st); break;
-    }
+  return msm_batch_run<C, F>(L, nullptr, 0, d_out, st, [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void*, void* part, void*) {
+    msm_batch_launch_chunks_p<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, part, st);
   });
 }
 #endif  // __HIPCC__

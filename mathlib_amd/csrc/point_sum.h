@@ -105,7 +105,7 @@ int point_sum_device(const void* d_points, size_t n, void* d_out, hipStream_t st
   const uint64_t offsets[2] = {0, plan.L};  // one segment of L one-partial "chunks": the sum passes over the L partials
   MsmBatchLayout lay;
   if (!msm_batch_layout(lay, offsets, 1, 1)) return mlhip_rt::fail(MLHIP_EINVAL, "point sum: layout");
-  return msm_batch_run<C, F>(lay, nullptr, 0, d_out, st, [&](const MsmBatchChunk*, uint32_t n_partials, const void*, void* part) {
+  return msm_batch_run<C, F>(lay, nullptr, 0, d_out, st, [&](const MsmBatchChunk*, uint32_t n_partials, const void*, void* part, void*) {
     if constexpr (kG1)
       k_point_sum<C><<<dim3((n_partials + 63) / 64), dim3(64), 0, st>>>((const Affine<FpField<C>>*)d_points, n, n_partials,
                                                                         (XYZZ<FpField<C>>*)part);
