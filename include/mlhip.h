@@ -231,16 +231,18 @@ MLHIP_API int mlhip_scalar_mul(int curve, int group, const void* points, size_t 
  * signed 4-bit-window double-and-add (256 / P + 71 group operations per pair), and the chunk sums of each segment are
  * added in passes of at most 32 per lane.  P = 4 (MLHIP_MSM_BATCH_CHUNK = 1, 2, 4 or 8 overrides; below ~2^17 pairs in all
  * the device is not filled and P = 1 is faster).
- * G1 segments of MLHIP_MSM_BATCH_BUCKET_MIN pairs or more (default 512; 0 = never, 1 .. 8 mean 9) take a bucket route
- * instead: slices of at most S pairs, 7-bit signed windows, one wave per (slice, window) with one bucket per lane, an
- * in-wave reduction and one Horner lane per slice; the slice sums join the chunk sums of the passes above.  S is the
- * largest power of two from 256 to 4096 that still gives 4096 waves (MLHIP_MSM_BATCH_BUCKET_SLICE=s fixes it).  Same bytes
- * as the chunks for every input (infinities, repeated points, P beside -P, points outside the subgroup).  Scratch: 37
- * bytes per pair of a slice + 37 XYZZ per slice; a call that would need more than 1 GiB of it runs chunks only.  Measured
- * (profiles/msm_batch_bucket_ab.txt): from 2^18 pairs per call on, 1.2-1.5x the chunks at 512 pairs per
- * segment and 1.4-2.1x from 1024 on; a batch of 16 384-pair segments is level with or ahead of single mlhip_msm_g1 calls,
- * from 65 536 pairs per segment on single calls are ahead.  G2, and the table-free path of mlhip_bases_msm_batch*, keep
- * the chunks: a long segment there is exact but slower than mlhip_msm_g2 on it.
+ * Segments of MLHIP_MSM_BATCH_BUCKET_MIN pairs or more (default 512 for G1, 256 for G2; 0 = never, 1 .. 8 mean 9) take a
+ * bucket route instead: slices of at most S pairs, signed windows of 7 bits (G1: one bucket per lane of a wave) or 6 bits (G2:
+ * one bucket per lane pair, 43 windows), one wave per (slice, window), an in-wave reduction and one Horner lane (pair) per
+ * slice; the slice sums join the chunk sums of the passes above.  S is the largest power of two from 256 to 4096 (G2: to
+ * 1024) that still gives 4096 waves (MLHIP_MSM_BATCH_BUCKET_SLICE=s fixes it).  Same bytes as the chunks for every input
+ * (infinities, repeated points, P beside -P, points outside the subgroup).  Scratch: 37 (G2: 43) bytes per pair of a slice +
+ * as many XYZZ per slice; a call that would need more than 1 GiB of it runs chunks only.  Measured:
+ * G1 (profiles/msm_batch_bucket_ab.txt), from 2^18 pairs per call on, 1.2-1.5x the chunks at 512 pairs per segment and
+ * 1.4-2.1x from 1024 on; a batch of 16 384-pair segments is level with or ahead of single mlhip_msm_g1 calls, from 65 536
+ * pairs per segment on single calls are ahead.  G2 (profiles/msm_batch_bucket_g2_ab.txt), at 2^16 and 2^18 pairs per call,
+ * 1.07-1.4x at 256 pairs per segment, 1.35-1.5x at 512 and 1.4-1.6x from 1024 on.  The table-free path of
+ * mlhip_bases_msm_batch* takes the same route (same switches, its group's defaults).
  * Runs on the first listed device.  Device pointers; the offsets are read on the host. */
 MLHIP_API int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
                                      const uint64_t* offsets, size_t k, void* d_out_affine, void* stream);
@@ -300,7 +302,10 @@ MLHIP_API int mlhip_bases_destroy(mlhip_bases* bases);
  * 1, 2, 4, 8, 16 that still fills 2^16 lanes (MLHIP_BASES_BATCH_CHUNK overrides).  The tables are owned by the handle (freed
  * by mlhip_bases_destroy, untouched by mlhip_release_cache) and capped at MLHIP_BASES_BATCH_MAX_MB (1024) per handle -- 212
  * BLS12-381 G1 or 106 G2 bases at w = 12: a call whose tables would pass the cap (or MLHIP_BASES_BATCH_MAX_MB=0) runs
- * mlhip_msm_batch's variable-base kernel on the handle's points instead.
+ * mlhip_msm_batch's variable-base kernels on the handle's points instead (the table-free path): Straus chunks, and for
+ * segments of MLHIP_MSM_BATCH_BUCKET_MIN pairs or more its bucket route, reading each pair's base through base_index
+ * (G1 with 4096 bases: 1.3-1.5x the chunks at 512 pairs per segment, 1.7-2.1x from 1024 on).  The tabled path never takes
+ * the bucket route: 22 mixed additions per pair beat it.
  * Growing the tables briefly holds the old and the new ones.  A handle that never sees a batch call allocates nothing.
  * Calls on one handle are serialized, as for mlhip_bases_msm. */
 MLHIP_API int mlhip_bases_msm_batch(mlhip_bases* bases, const void* scalars, int scalars_mont, const uint32_t* base_index,
@@ -449,9 +454,10 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
  *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
- *     MLHIP_MSM_BATCH_BUCKET_MIN=n     mlhip_msm_batch* G1: segments of n pairs or more take the bucket route (default 512;
- *                                      0 = never, 1 .. 8 mean 9)
- *     MLHIP_MSM_BATCH_BUCKET_SLICE=s   ... pairs per slice of such a segment (default: 256 .. 4096 by the size of the batch)
+ *     MLHIP_MSM_BATCH_BUCKET_MIN=n     mlhip_msm_batch* and the table-free path of mlhip_bases_msm_batch*: segments of n pairs
+ *                                      or more take the bucket route (default 512 for G1, 256 for G2; 0 = never, 1 .. 8 mean 9)
+ *     MLHIP_MSM_BATCH_BUCKET_SLICE=s   ... pairs per slice of such a segment (default: 256 .. 4096, G2 256 .. 1024, by the size
+ *                                      of the batch)
  *     MLHIP_SUM_DEVICE_MIN=n           mlhip_g1_sum / mlhip_g2_sum: smallest list summed on the device (0 = never, 1 = always;
  *                                      default 2^14 G1 / 2^12 G2)
  *     MLHIP_BASES_BATCH_WINDOW=w, MLHIP_BASES_BATCH_CHUNK=P   mlhip_bases_msm_batch*: table width 4 .. 12 (default 12), pairs

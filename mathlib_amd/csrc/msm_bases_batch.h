@@ -13,7 +13,9 @@
 //              adds, for every pair, ceil(256 / w) entries +-T_idx[j][|d_j|] (signed w-bit digits of the reduced scalar,
 //              msm_window_digit) into one XYZZ28 accumulator -- no doubling, no per-lane table -- and writes its partial
 //              in XYZZ; the sum passes of msm_batch.h (k_msm_batch_sum / _lp) add the partials of each segment.
-//   table-free the variable-base body of mlhip_msm_batch (msm_batch_chunk, its P) reading the handle's points by index.
+//   table-free the variable-base body of mlhip_msm_batch (msm_batch_chunk, its P) reading the handle's points by index; its long
+//              segments take the bucket route of msm_batch_bucket.h (the same switches and per-group defaults), the point
+//              of a pair read through the index list (MsmBucketIndexed).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -21,6 +23,7 @@
 #include "ec28.h"
 #include "ec28_lp.h"
 #include "msm_batch.h"
+#include "msm_batch_bucket.h"
 
 namespace mlhip {
 
@@ -143,6 +146,7 @@ __global__ void __launch_bounds__(64) k_msm_batch_chunk_bases(const Affine<FpFie
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= n_chunks) return;
   const MsmBatchChunk ch = chunks[c];
+  if (ch.count > (uint32_t)P) return;  // a slice of a long segment: the bucket kernels write this row (msm_batch_bucket.h)
   XYZZ<F> acc;
   msm_batch_chunk<F, P, MsmBatchOpsG1<F>>(acc, scalars + 8 * ch.first, ch.count, mont != 0, [&](Affine<F>& p, int j) {
     p = points[index ? index[ch.first + j] : ch.base0 + (uint32_t)j];
@@ -161,6 +165,7 @@ __global__ void __launch_bounds__(64) k_msm_batch_chunk_bases_lp(const Affine<Fp
   if (c >= n_chunks) return;
   const int hi = (int)(threadIdx.x & 1u);
   const MsmBatchChunk ch = chunks[c];
+  if (ch.count > (uint32_t)P) return;  // a slice of a long segment (both lanes of the pair leave)
   XYZZ<FL> acc;
   msm_batch_chunk<FL, P, MsmBatchOpsLp<C>>(acc, scalars + 8 * ch.first, ch.count, mont != 0, [&](Affine<FL>& p, int j) {
     lp_load_affine<C>(p, points, index ? index[ch.first + j] : ch.base0 + (uint32_t)j, hi);
@@ -293,28 +298,50 @@ int bases_batch_device(mlhip_bases_batch_tables* t, const void* d_pts, size_t n_
     int rc = bases_batch_grow<C, F>(t, d_pts, need, w, st);
     if (rc) return rc;
   }
-  const int P = tabled ? bases_batch_chunk_len<C, F>(offsets, k) : msm_batch_chunk_len<C, F>();
+  const size_t index_bytes = base_index ? (size_t)offsets[k] * 4 : 0;
+  if (!tabled) {
+    // mlhip_msm_batch's kernels over the handle's points: Straus chunks, and the bucket route for the long segments.  The
+    // extra upload is [the index list | the slice rows].
+    const int P = msm_batch_chunk_len<C, F>();
+    MsmBucketCall<C, F> call;
+    if (!call.plan(offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: more than 2^32 - 1 chunks");
+    std::vector<uint32_t> extra;
+    const void* up = base_index;
+    if (!call.slices.empty()) {
+      if (base_index) extra.assign(base_index, base_index + offsets[k]);
+      extra.insert(extra.end(), call.slices.begin(), call.slices.end());
+      up = extra.data();
+    }
+    return msm_batch_run<C, F>(
+        call.L, up, index_bytes + call.slices.size() * sizeof(uint32_t), d_out, st,
+        [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void* d_extra, void* part, void* d_scratch) {
+          const uint32_t* d_index = base_index ? (const uint32_t*)d_extra : nullptr;
+          if (n_chunks > call.slices.size()) {
+            switch (P) {
+              case 1: bases_batch_launch_free<C, F, 1>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
+              case 2: bases_batch_launch_free<C, F, 2>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
+              case 4: bases_batch_launch_free<C, F, 4>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
+              default: bases_batch_launch_free<C, F, 8>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
+            }
+          }
+          if (!call.slices.empty())
+            call.launch(d_pts, MsmBucketIndexed{d_index}, d_scalars, mont, d_chunks,
+                        (const uint32_t*)((const char*)d_extra + index_bytes), part, d_scratch, st);
+        },
+        call.scratch);
+  }
+  const int P = bases_batch_chunk_len<C, F>(offsets, k);
   MsmBatchLayout L;
   if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "bases msm batch: more than 2^32 - 1 chunks");
-  const size_t index_bytes = base_index ? (size_t)offsets[k] * 4 : 0;
   return msm_batch_run<C, F>(L, base_index, index_bytes, d_out, st,
                              [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void* d_extra, void* part, void*) {
     const uint32_t* d_index = base_index ? (const uint32_t*)d_extra : nullptr;
-    if (tabled) {
-      if constexpr (kG1)
-        k_bases_batch_chunk<C><<<dim3((n_chunks + 63) / 64), dim3(64), 0, st>>>(
-            (const Affine28<C>*)t->buf, per, w, (const uint32_t*)d_scalars, mont, d_index, d_chunks, n_chunks, (XYZZ<F>*)part);
-      else
-        k_bases_batch_chunk_lp<C><<<dim3((unsigned)((2 * (size_t)n_chunks + 63) / 64)), dim3(64), 0, st>>>(
-            (const AffineG2_28<C>*)t->buf, per, w, (const uint32_t*)d_scalars, mont, d_index, d_chunks, n_chunks, (XYZZ<F>*)part);
-      return;
-    }
-    switch (P) {
-      case 1: bases_batch_launch_free<C, F, 1>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
-      case 2: bases_batch_launch_free<C, F, 2>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
-      case 4: bases_batch_launch_free<C, F, 4>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
-      default: bases_batch_launch_free<C, F, 8>(d_pts, d_scalars, mont, d_index, d_chunks, n_chunks, part, st); break;
-    }
+    if constexpr (kG1)
+      k_bases_batch_chunk<C><<<dim3((n_chunks + 63) / 64), dim3(64), 0, st>>>(
+          (const Affine28<C>*)t->buf, per, w, (const uint32_t*)d_scalars, mont, d_index, d_chunks, n_chunks, (XYZZ<F>*)part);
+    else
+      k_bases_batch_chunk_lp<C><<<dim3((unsigned)((2 * (size_t)n_chunks + 63) / 64)), dim3(64), 0, st>>>(
+          (const AffineG2_28<C>*)t->buf, per, w, (const uint32_t*)d_scalars, mont, d_index, d_chunks, n_chunks, (XYZZ<F>*)part);
   });
 }
 #endif  // __HIPCC__

@@ -205,6 +205,7 @@ __global__ void __launch_bounds__(64) k_msm_batch_chunk_lp(const Affine<Fp2Field
   if (c >= n_chunks) return;
   const int hi = (int)(threadIdx.x & 1u);
   const MsmBatchChunk ch = chunks[c];
+  if (ch.count > (uint32_t)P) return;  // a slice of a long segment (both lanes of the pair leave): msm_batch_bucket.h
   XYZZ<FL> acc;
   msm_batch_chunk<FL, P, MsmBatchOpsLp<C>>(acc, scalars + 8 * ch.first, ch.count, mont != 0,
                                            [&](Affine<FL>& p, int j) { lp_load_affine<C>(p, points, ch.first + j, hi); });

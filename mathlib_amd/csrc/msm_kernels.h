@@ -15,9 +15,10 @@
 //                 (k_chunks / k_masked_sums: one lane per point; *_lp: G2 lane pairs)
 //   k_msm_batch_chunk / k_msm_batch_sum (+ _lp for G2)   many small MSMs per call: Straus chunks of <= P pairs per lane,
 //                 then segmented sums of <= 32 partials per lane (msm_batch.h)
-//   k_msm_bucket_digits / k_msm_bucket_accumulate / k_msm_bucket_combine   the G1 segments of such a call that are long enough
+//   k_msm_bucket_digits / k_msm_bucket_accumulate / k_msm_bucket_combine   the segments of such a call that are long enough
 //                 for buckets: 7-bit digit bytes per slice, one wave per (slice, window) with one bucket per lane and an
-//                 in-wave reduction, Horner per slice into the slice's row of the partials (msm_batch_bucket.h)
+//                 in-wave reduction, Horner per slice into the slice's row of the partials (msm_batch_bucket.h); _lp for G2
+//                 (6-bit digits, one bucket per lane pair), _at / MsmBucketIndexed for the bases of a handle
 //   k_bases_batch_chunk (+ _lp)   the same over a mlhip_bases handle: per-base fixed-window tables, ceil(256 / w) mixed
 //                 additions per pair, no doubling (msm_bases_batch.h)
 //   k_point_sum (+ _lp)   plain sums of many points (mlhip_g1_sum / mlhip_g2_sum above their threshold): strided slices per
