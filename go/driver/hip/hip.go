@@ -28,6 +28,7 @@ package hip
 #cgo LDFLAGS: -L${SRCDIR}/../../../mathlib_amd -lmlhip -Wl,-rpath,${SRCDIR}/../../../mathlib_amd
 #include <stdlib.h>
 #include "mlhip.h"
+#include "mlhip_bits.h"
 */
 import "C"
 
@@ -285,6 +286,56 @@ func (c *Curve) MultiScalarMulG2(a []driver.G2, b []driver.Zr) driver.G2 {
 		return C.mlhip_msm_g2(C.MLHIP_CURVE_BLS12_381,
 		unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1, C.size_t(n), C.int(WindowC),
 		unsafe.Pointer(&out.G2Affine))
+	})
+	return out
+}
+
+// MultiScalarMulShort = MultiScalarMul for scalars known to be below 2^bits (a batch verifier's 64- or 128-bit
+// randomisers): sum of [b[i] mod 2^bits] a[i] through mlhip_msm_bits, the same point as MultiScalarMul when the scalars
+// keep the promise, in fewer windows.  bits = 0 means full width.  Same length rules as MultiScalarMul.
+func (c *Curve) MultiScalarMulShort(a []driver.G1, b []driver.Zr, bits int) driver.G1 {
+	n := len(a)
+	if len(b) < n {
+		_ = b[n-1] // the reference's index out of range (math.go:960-969)
+	}
+	out := &gurvy381.G1{}
+	if len(b) != n || n == 0 {
+		return out
+	}
+	points := make([]bls12381.G1Affine, n)
+	scalars := make([]fr.Element, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G1).G1Affine
+		scalars[i] = gurvy381.ZrValue(b[i])
+	}
+	check(func() C.int {
+		return C.mlhip_msm_bits(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1,
+			unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1, C.int(bits), C.size_t(n), C.int(WindowC),
+			unsafe.Pointer(&out.G1Affine))
+	})
+	return out
+}
+
+// MultiScalarMulG2Short is the same in G2.
+func (c *Curve) MultiScalarMulG2Short(a []driver.G2, b []driver.Zr, bits int) driver.G2 {
+	n := len(a)
+	if len(b) < n {
+		_ = b[n-1]
+	}
+	out := &gurvy381.G2{}
+	if len(b) != n || n == 0 {
+		return out
+	}
+	points := make([]bls12381.G2Affine, n)
+	scalars := make([]fr.Element, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G2).G2Affine
+		scalars[i] = gurvy381.ZrValue(b[i])
+	}
+	check(func() C.int {
+		return C.mlhip_msm_bits(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2,
+			unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1, C.int(bits), C.size_t(n), C.int(WindowC),
+			unsafe.Pointer(&out.G2Affine))
 	})
 	return out
 }

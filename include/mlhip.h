@@ -191,6 +191,52 @@ MLHIP_API int mlhip_msm_plan_set_profiling(mlhip_msm_plan* plan, int on);
 MLHIP_API int mlhip_msm_plan_assume_srs(mlhip_msm_plan* plan, int on);
 MLHIP_API int mlhip_msm_plan_timings(mlhip_msm_plan* plan, float* ms, int cap);
 
+/* ---- short scalars: plans and a host-buffer call that know the scalar width --------------------------------------------
+ * For callers whose scalars are short by construction (the 64- or 128-bit randomisers of a batch verifier, small weights,
+ * bit-decomposed witnesses).
+ *
+ * Result.  out = sum_i [s_i'] P_i with s_i' = (s_i mod r) mod 2^scalar_bits: scalars_mont and unreduced 256-bit inputs are
+ * handled as everywhere else, then the canonical value is masked to its low scalar_bits bits.  The result is therefore
+ * defined for every input; a caller who keeps the promise s_i < 2^scalar_bits gets exactly mlhip_msm_g1's / _g2's bytes.
+ *
+ * How it is said.  The library's dynamic symbol table does not grow (the tests pin it): the width travels in the window_c
+ * argument of the existing entry points -- mlhip_msm_plan_create, mlhip_msm_g1, mlhip_msm_g2 -- as
+ * MLHIP_WINDOW_BITS(window_c, scalar_bits) below, and a plan reports it as a twelfth value, [11], of
+ * mlhip_msm_plan_timings when cap >= 12 (the curve's fr_bits for a full-width plan; the call then returns 12, and with
+ * cap <= 11 exactly what it returned before).  include/mlhip_bits.h wraps this in three inline functions for C, C++ and cgo
+ * callers: mlhip_msm_plan_create_bits(curve_id, group, max_n, window_c, scalar_bits, &plan),
+ * mlhip_msm_plan_scalar_bits(plan, &scalar_bits) and mlhip_msm_bits(curve_id, group, points, scalars, scalars_mont,
+ * scalar_bits, n, window_c, out_affine); the names below mean those.  The packed value is taken apart in those three
+ * entry points and nowhere else: every other one that takes a window_c (mlhip_msm_multi, mlhip_msm_g1g2,
+ * mlhip_bases_create*) rejects it as it rejects any window_c above 20, and nothing inside the library calls the three.
+ *
+ * Range.  scalar_bits = 0, or any value from the curve's fr_bits (253 / 254 / 255) up to 256, means full width: the packed
+ * window_c is then the plain one -- same geometry, same bytes, same code path (full width is the short path with the
+ * width at fr_bits).  A negative value or one above 256 is MLHIP_EINVAL (the plan pointer is left NULL).  Otherwise
+ * 1 .. fr_bits - 1.
+ *
+ * Geometry.  B = scalar_bits + 1 bits are covered (the spare bit absorbs the last signed-digit carry) by W = ceil(B / c)
+ * windows; the plan's effective width is c' = ceil(B / W) <= c, with 2^(c'-1) buckets per window (B = 129, c = 16: 9 windows
+ * of 15 / 14 bits and 2^14 buckets each; c' is never taken below 4).  ceil(B / c') = W again, so c' is simply the plan's
+ * width: mlhip_msm_plan_timings [7] and [8] report c' and W.  Digits, sort, bucket arrays, reduction and the host tail all
+ * scale with this W; W * max_n must stay below 2^32.  window_c = 0: the library picks from (n, scalar_bits, group) -- the
+ * width it would pick for full-width scalars, or, from a size that grows with the number of windows, 17 bits: fewer, fuller
+ * windows, whose buckets are many enough to keep the chip busy (api_msm.hip: pick_window_bits).
+ *
+ * A short plan runs through mlhip_msm_run / _launch / _launch_shared / _finish like any other (one pass, tiles, profiling,
+ * mlhip_msm_plan_assume_srs, out_xyzz).  mlhip_msm_launch_shared shares one sort only between plans of the same curve,
+ * width, window count AND scalar width; others run one after the other with the same results.  mlhip_msm_bits uses the
+ * plan pool (a pooled full-width plan never serves a short call, nor the reverse), streams large inputs in segments like
+ * mlhip_msm_g1, runs on the calling thread's first device (a short call is never spread over a device list), and gives the
+ * point at infinity for n = 0.  Plans over the shifted-base tables of a mlhip_bases handle, mlhip_msm_batch*,
+ * mlhip_scalar_mul* and the Gt exponentiations keep full width.
+ * curve_id is a MLHIP_CURVE_* value (an unknown one is MLHIP_EINVAL, "unknown curve id").
+ * Measured: profiles/msm_bits_ab.txt, DESIGN.md section 14 -- 2^20 BLS12-381 G1 points, scalars below 2^bits, short plan
+ * against full-width plan: 0.656 / 0.707 / 0.833 of its time at 32 / 64 / 128 bits (the additions count alone would predict
+ * 0.125 / 0.25 / 0.5: the full-width plan already skips zero digits). */
+#define MLHIP_WINDOW_BITS(window_c, scalar_bits) \
+  ((int)((window_c) < 0 || (window_c) > 255 ? 0xFF : (window_c)) | (int)(((scalar_bits) < 0 || (scalar_bits) > 256 ? 0x3FF : (scalar_bits)) << 8))
+
 /* The device forms of the entry points above (and the _device forms further down, unless their comment says otherwise): device
  * pointers in and out; they enqueue their kernels on `stream` and return, so the work runs in order on `stream` (NULL = the
  * default stream) -- after whatever the caller queued there before, which may still be producing the inputs, and before

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "mlhip.h"
+#include "mlhip_bits.h"
 
 namespace mlhip_driver {
 
@@ -498,6 +499,26 @@ class Curve {
     Bytes pts, sc;
     pack(a, b, pts, sc);
     check(mlhip_msm_g2(id, pts.data(), sc.data(), scalars_mont ? 1 : 0, a.size(), window_c, out.raw.data()));
+    return out;
+  }
+  // MultiScalarMul / MultiScalarMulG2 for scalars known to be below 2^bits (additive; mlhip_msm_bits): sum_i [b_i mod 2^bits] a_i,
+  // the same point as the full-width call when the scalars keep the promise, in fewer windows.  bits = 0: full width.
+  G1 MultiScalarMulShort(const std::vector<G1>& a, const std::vector<Zr>& b, int bits) const {
+    if (b.size() < a.size()) throw std::out_of_range("MultiScalarMulShort: fewer scalars than points");
+    G1 out = NewG1();
+    if (b.size() != a.size() || a.empty()) return out;
+    Bytes pts, sc;
+    pack(a, b, pts, sc);
+    check(mlhip_msm_bits(id, MLHIP_GROUP_G1, pts.data(), sc.data(), scalars_mont ? 1 : 0, bits, a.size(), window_c, out.raw.data()));
+    return out;
+  }
+  G2 MultiScalarMulG2Short(const std::vector<G2>& a, const std::vector<Zr>& b, int bits) const {
+    if (b.size() < a.size()) throw std::out_of_range("MultiScalarMulG2Short: fewer scalars than points");
+    G2 out = NewG2();
+    if (b.size() != a.size() || a.empty()) return out;
+    Bytes pts, sc;
+    pack(a, b, pts, sc);
+    check(mlhip_msm_bits(id, MLHIP_GROUP_G2, pts.data(), sc.data(), scalars_mont ? 1 : 0, bits, a.size(), window_c, out.raw.data()));
     return out;
   }
   // points[0] + points[1] + ...: G1::Add / G2::Add in a loop as one call; long lists are summed on the device

@@ -296,6 +296,39 @@ def msm_batch(curve: int, group: int, points: bytes, scalars: bytes, scalars_mon
     return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
 
 
+def window_bits(window_c: int, scalar_bits: int) -> int:
+    """MLHIP_WINDOW_BITS of include/mlhip.h: a window width and a scalar width in one window_c argument"""
+    return (0xFF if not 0 <= window_c <= 255 else window_c) | ((0x3FF if not 0 <= scalar_bits <= 256 else scalar_bits) << 8)
+
+
+def mlhip_msm_plan_create_bits(lib, curve: int, group: int, max_n: int, window_c: int, scalar_bits: int, plan_ref) -> int:
+    """include/mlhip_bits.h: a plan for scalars below 2^scalar_bits (the return code, as the C function)"""
+    return lib.mlhip_msm_plan_create(curve, group, max_n, window_bits(window_c, scalar_bits), plan_ref)
+
+
+def mlhip_msm_plan_scalar_bits(lib, plan):
+    """include/mlhip_bits.h: (return code, the width the plan was made for)"""
+    buf = (c_float * 12)()
+    k = lib.mlhip_msm_plan_timings(plan, buf, 12)
+    return (k, 0) if k < 0 else (EINVAL, 0) if k < 12 else (0, int(buf[11]))
+
+
+def mlhip_msm_bits(lib, curve: int, group: int, points, scalars, scalars_mont: int, scalar_bits: int, n: int, window_c: int, out) -> int:
+    """include/mlhip_bits.h: mlhip_msm_g1 / mlhip_msm_g2 for short scalars (the return code, as the C function)"""
+    if group not in (GROUP_G1, GROUP_G2):
+        return EINVAL
+    fn = lib.mlhip_msm_g1 if group == GROUP_G1 else lib.mlhip_msm_g2
+    return fn(curve, points, scalars, scalars_mont, n, window_bits(window_c, scalar_bits), out)
+
+
+def msm_bits(curve: int, group: int, points, scalars, scalars_mont: bool, scalar_bits: int, n: int, window_c: int = 0) -> bytes:
+    """mlhip_msm_bits: sum_i [(s_i mod r) mod 2^scalar_bits] P_i over host buffers, as one affine point (bytes)"""
+    _, g1, g2, _ = sizes(curve)
+    out = ctypes.create_string_buffer(g1 if group == GROUP_G1 else g2)
+    check(mlhip_msm_bits(load(), curve, group, points, scalars, 1 if scalars_mont else 0, scalar_bits, n, window_c, out))
+    return out.raw
+
+
 def batch_index(index_lists):
     """the base_index array of mlhip_bases_msm_batch* (one uint32 per pair, segment after segment), or None"""
     if index_lists is None:
@@ -382,10 +415,14 @@ def plan_timings(lib, handle):
 class MsmPlan:
     """Device workspace for repeated MSMs over device-resident points/scalars (include/mlhip.h)."""
 
-    def __init__(self, curve: int, group: int, max_n: int, window_c: int = 0):
+    def __init__(self, curve: int, group: int, max_n: int, window_c: int = 0, scalar_bits: int = 0):
+        """scalar_bits != 0: a plan for scalars below 2^scalar_bits (mlhip_msm_plan_create_bits; 0 = full width)"""
         self._h = c_void_p()
         lib = self._lib = concrete()
-        check(lib.mlhip_msm_plan_create(curve, group, max_n, window_c, byref(self._h)))
+        if scalar_bits:
+            check(mlhip_msm_plan_create_bits(lib, curve, group, max_n, window_c, scalar_bits, byref(self._h)))
+        else:
+            check(lib.mlhip_msm_plan_create(curve, group, max_n, window_c, byref(self._h)))
         _, g1, g2, _ = sizes(curve)
         self.point_bytes = g1 if group == GROUP_G1 else g2
         self.curve, self.group = curve, group
@@ -405,6 +442,12 @@ class MsmPlan:
         buf = (c_float * 9)()
         self._lib.mlhip_msm_plan_timings(self._h, buf, 9)
         return int(buf[7]), int(buf[8])
+
+    def scalar_bits(self) -> int:
+        """the scalar width the plan was made for (the curve's fr_bits for a full-width plan)"""
+        rc, bits = mlhip_msm_plan_scalar_bits(self._lib, self._h)
+        check(rc)
+        return bits
 
     def run(self, d_points: int, d_scalars: int, n: int, scalars_mont: bool, stream: int = 0, want_xyzz: bool = False):
         out = ctypes.create_string_buffer(self.point_bytes)

@@ -90,7 +90,7 @@ int bases_create_single(int curve, int group, const void* points, size_t n, int 
       if (plan_create_ex(curve, group, n, fold_c, fold_tile, &b->plan) != 0) b->plan = nullptr;  // (the plain plan below)
     }
   }
-  rc = b->plan ? 0 : mlhip_msm_plan_create(curve, group, n, window_c, &b->plan);
+  rc = b->plan ? 0 : plan_create_ex(curve, group, n, window_c, 0, &b->plan);
   if (!rc && (hipMalloc(&b->d_pts, n * b->ptsz) != hipSuccess || hipMalloc(&b->d_sc, n * 32) != hipSuccess))
     rc = mlhip_rt::fail(MLHIP_ENOMEM, "hipMalloc of the bases failed");
   if (!rc && hipMemcpy(b->d_pts, points, n * b->ptsz, points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
@@ -131,7 +131,7 @@ int bases_create_single(int curve, int group, const void* points, size_t n, int 
       const bool trusted = b->plan->trust_subgroup;
       mlhip_msm_plan_destroy(b->plan);
       b->plan = nullptr;
-      rc = mlhip_msm_plan_create(curve, group, n, window_c, &b->plan);
+      rc = plan_create_ex(curve, group, n, window_c, 0, &b->plan);
       if (rc) {
         mlhip_bases_destroy(b);
         return rc;

@@ -35,6 +35,7 @@ struct PoolEntry {
   void *d_pts = nullptr, *d_sc = nullptr;
   hipStream_t stream = nullptr;  // the entry's own non-blocking stream: concurrent callers do not meet on the null stream
   int curve = 0, group = 0, c = 0, device = 0;
+  int bits = 0;  // the plan's scalar width (fr_bits: full width) -- a full-width plan never serves a short call, nor the reverse
   size_t cap = 0;
   bool busy = false, pooled = false;
   unsigned long stamp = 0;
@@ -55,14 +56,14 @@ void pool_free_entry(PoolEntry* e) {
   delete e;
 }
 
-PoolEntry* pool_acquire(int curve, int group, int c, size_t n, size_t ptsz, int& rc) {
+PoolEntry* pool_acquire(int curve, int group, int c, int bits, size_t n, size_t ptsz, int& rc) {
   const char* off = getenv("MLHIP_NO_PLAN_CACHE");
   const bool use_pool = !(off && off[0] == '1');
   std::vector<PoolEntry*> victims;
   if (use_pool) {
     std::lock_guard<std::mutex> lk(g_pool_mu);
     for (PoolEntry* e : g_pool)
-      if (!e->busy && e->curve == curve && e->group == group && e->c == c && e->device == call_device() && e->cap >= n &&
+      if (!e->busy && e->curve == curve && e->group == group && e->c == c && e->bits == bits && e->device == call_device() && e->cap >= n &&
           e->cap <= 4 * n) {
         e->busy = true;
         e->stamp = ++g_pool_clock;
@@ -92,11 +93,12 @@ PoolEntry* pool_acquire(int curve, int group, int c, size_t n, size_t ptsz, int&
   e->curve = curve;
   e->group = group;
   e->c = c;
+  e->bits = bits;
   e->device = call_device();
   e->cap = n;
   e->busy = true;
   for (int attempt = 0;; attempt++) {
-    rc = mlhip_msm_plan_create(curve, group, n, c, &e->plan);
+    rc = plan_create_ex(curve, group, n, c, 0, &e->plan, bits);
     if (!rc && (hipMalloc(&e->d_pts, n * ptsz) != hipSuccess || hipMalloc(&e->d_sc, n * 32) != hipSuccess))
       rc = mlhip_rt::fail(MLHIP_ENOMEM, "hipMalloc of MSM inputs failed");
     if (!rc || attempt == 1 || !use_pool) break;
@@ -224,19 +226,72 @@ int pick_window(size_t n, int fr_bits) {
   return 16;
 }
 
+// The width for n scalars of `bits` bits (short-scalar plans: mlhip_msm_plan_create_bits, mlhip_msm_bits).  Full width is
+// pick_window itself.  Below it the starting rule is pick_window's width for the size, which the plan then normalises to
+// c' = ceil((bits + 1) / W) (msm_body.h: msm_effective_c): the same number of windows, fewer buckets each.  That rule is the
+// measured optimum for small inputs only (tools/perf_msm_bits.py --sweep, profiles/msm_bits_ab.txt: G1 on BLS12-381 and
+// BN254 from 2^12 to 2^22 points, G2 on BLS12-381 up to 2^18, at 32 / 64 / 128 bits).  With few windows the buckets are few
+// and their chains of dependent additions long -- 2^20 points, 64 bits, 5 windows of 13 bits: 2.9 ms of accumulation, where
+// 4 windows of 17 bits take 0.76 (and 0.32 instead of 0.13 ms of reduction) -- so from a size that grows with the number of
+// windows the pick is 17 bits: fewer, fuller windows, 2^16 buckets each, still on the two-level sort.  Measured crossovers,
+// by W17 = ceil((bits + 1) / 17):  G1  W17 <= 2: 2^16 points, <= 4: 2^17, <= 8: 2^18;  G2 (its reduction of a 17-bit window
+// costs 1.6 ms against 0.6 at 13 bits)  W17 <= 2: 2^17, <= 8: 2^19 -- the G2 sizes above 2^18 are extrapolated, not measured.
+// The wide pick is taken only where its windows come out 16 or 17 bits wide and there are at most the 8 of the widest
+// measured width (128 bits); other widths keep the starting rule.
+int pick_window_bits(size_t n, int bits, int fr_bits, int group) {
+  const int c = pick_window(n, fr_bits);
+  if (bits >= fr_bits) return c;
+  const int start = std::max(4, msm_effective_c(bits, c));
+  const int w17 = msm_num_windows(bits, 17), wide = msm_effective_c(bits, 17);
+  if (wide < 16 || wide <= start || w17 > 8) return start;
+  int lg_min;
+  if (group == MLHIP_GROUP_G2)
+    lg_min = w17 <= 2 ? 17 : 19;
+  else
+    lg_min = w17 <= 2 ? 16 : w17 <= 4 ? 17 : 18;
+  return n >= ((size_t)1 << lg_min) ? wide : start;
+}
+
+// normalised scalar width: 0 or >= fr_bits (up to 256) = fr_bits; -1 = out of range
+int scalar_width(int scalar_bits, int fr_bits) {
+  if (scalar_bits < 0 || scalar_bits > 256) return -1;
+  return (scalar_bits == 0 || scalar_bits >= fr_bits) ? fr_bits : scalar_bits;
+}
+
+// MLHIP_WINDOW_BITS(window_c, scalar_bits) of include/mlhip.h taken apart: the window width in the low 8 bits, the scalar
+// width above them (0 = full width; the macro's 0x3FF for an out-of-range width, and anything else above 256, comes out as
+// -1, which scalar_width rejects).  A plain window_c is its own packed form.
+void unpack_window(int packed, int& window_c, int& scalar_bits) {
+  if (packed < 0) {  // (never a packed value: the window check reports it)
+    window_c = packed;
+    scalar_bits = 0;
+    return;
+  }
+  window_c = packed & 0xFF;
+  scalar_bits = packed >> 8;
+  if (scalar_bits > 256) scalar_bits = -1;
+}
+
 // fold_tile != 0: a plan over shifted-base tables (msm_fold.h, mlhip_internal.h) -- window_c is the digit width, the
 // 2^(c-1) buckets all digits share are cut into groups of at most 2^15 for the reduction; the table itself is built by
 // mlhip_tu_plan_fold_build_* (mlhip_bases_create).
-int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out) {
+int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits) {
   if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null plan pointer");
   *out = nullptr;
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   if (!ops->point_size(group)) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
   if (max_n == 0 || max_n > ((size_t)1 << 27)) return mlhip_rt::fail(MLHIP_EINVAL, "max_n out of range (1 .. 2^27)");
-  if (window_c == 0) window_c = pick_window(max_n, ops->fr_bits);
+  // (shifted-base tables keep full width: the table rows are the bases shifted by the full-width digit offsets)
+  const int bits = fold_tile ? ops->fr_bits : scalar_width(scalar_bits, ops->fr_bits);
+  if (bits < 0) return mlhip_rt::fail(MLHIP_EINVAL, "scalar_bits out of range (0 .. 256)");
+  if (window_c == 0) window_c = pick_window_bits(max_n, bits, ops->fr_bits, group);
   if (window_c < 4 || window_c > 20) return mlhip_rt::fail(MLHIP_EINVAL, "window_c out of range (4 .. 20)");
-  const int digits = msm_num_windows(ops->fr_bits, window_c);
+  // a short plan's W = ceil((bits + 1) / c) windows need c' = ceil((bits + 1) / W) bits each: the plan's width is c'
+  // (never below 4, the smallest width the reduction's chunks of 8 buckets take: a few bits only; W stays the same, since
+  // ceil(B / 4) lies between ceil(B / c) and ceil(B / c'))
+  if (bits < ops->fr_bits) window_c = std::max(4, msm_effective_c(bits, window_c));
+  const int digits = msm_num_windows(bits, window_c);
   // sorted-entry offsets, cursors and scans are 32-bit: W * max_n entries must be addressable
   if (!fold_tile && (size_t)digits * max_n > 0xFFFFFFFFull)
     return mlhip_rt::fail(MLHIP_EINVAL, "window_c too small for max_n: W * max_n entries exceed 2^32 - 1");
@@ -254,6 +309,7 @@ int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold
   p->group = group;
   p->device = call_device();
   p->c = window_c;
+  p->bits = bits;
   p->Wd = digits;
   p->max_n = max_n;
   if (fold_tile) {
@@ -361,7 +417,7 @@ void release_plan_pool() {
 
 namespace {
 int msm_host_buffers(int curve, int group, const void* points, const void* scalars, int mont, size_t n, int window_c,
-                     void* out);
+                     void* out, int scalar_bits = 0);
 
 // One MSM over several devices (reference semantics math.go:960-969 /
 // driver/gurvy/bls12381/bls12-381.go:766-783): contiguous shards of the pairs, one host thread per device running the
@@ -380,12 +436,16 @@ int msm_multi(const std::vector<int>& devs, int curve, int group, const void* po
   return host_group_sum(curve, group, partial.data(), devs.size(), out);
 }
 
+// scalar_bits: mlhip_msm_bits' width (0 = full: mlhip_msm_g1 / _g2).  A short call runs on the calling thread's first device.
 int msm_host_buffers(int curve, int group, const void* points, const void* scalars, int mont, size_t n, int window_c,
-                     void* out) {
+                     void* out, int scalar_bits) {
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
   const size_t ptsz = ops->point_size(group);
+  if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
+  const int bits = scalar_width(scalar_bits, ops->fr_bits);
+  if (bits < 0) return mlhip_rt::fail(MLHIP_EINVAL, "scalar_bits out of range (0 .. 256)");
   if (n == 0) {
     // the point at infinity, as gnark's MultiExp gives for empty slices (and, via the dropped
     // error, for mismatched lengths: bls12-381.go:777)
@@ -393,14 +453,14 @@ int msm_host_buffers(int curve, int group, const void* points, const void* scala
     return 0;
   }
   if (!points || !scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  {
+  if (bits == ops->fr_bits) {
     const std::vector<int> devs = spread_devices(n, false);
     if (!devs.empty()) return msm_multi(devs, curve, group, points, scalars, mont, n, window_c, out, ptsz);
   }
-  if (window_c == 0) window_c = pick_window(n, ops->fr_bits);
+  if (window_c == 0) window_c = pick_window_bits(n, bits, ops->fr_bits, group);
   int rc = ensure_device();
   if (rc) return rc;
-  PoolEntry* e = pool_acquire(curve, group, window_c, n, ptsz, rc);
+  PoolEntry* e = pool_acquire(curve, group, window_c, bits, n, ptsz, rc);
   if (!e) return rc;
   const int segments = stream_segments(group, n, e->plan);
   do {
@@ -449,7 +509,9 @@ int mlhip_msm_multi(int curve, int group, const int* devices, int n_devices, con
 }
 
 int mlhip_msm_plan_create(int curve, int group, size_t max_n, int window_c, mlhip_msm_plan** out) {
-  return plan_create_ex(curve, group, max_n, window_c, 0, out);
+  int c = 0, bits = 0;  // (window_c may carry a scalar width: MLHIP_WINDOW_BITS)
+  unpack_window(window_c, c, bits);
+  return plan_create_ex(curve, group, max_n, c, 0, out, bits);
 }
 
 int mlhip_msm_plan_destroy(mlhip_msm_plan* p) {
@@ -515,7 +577,7 @@ int mlhip_msm_launch_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, const void* 
     return mlhip_rt::fail(MLHIP_EINVAL, "plan already has a pending launch; call mlhip_msm_finish first");
   if (n > g1->max_n || n > g2->max_n) return mlhip_rt::fail(MLHIP_EINVAL, "n exceeds a plan's max_n");
   if (n && (!d_points_g1 || !d_points_g2 || !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null device pointer");
-  const bool share = n != 0 && g1->c == g2->c && plan_can_stream(g1) && plan_can_stream(g2);
+  const bool share = n != 0 && g1->c == g2->c && g1->W == g2->W && g1->bits == g2->bits && plan_can_stream(g1) && plan_can_stream(g2);
   if (!share) {  // nothing to share (or a plan on a second-implementation path): two ordinary launches, one after the other
     int rc = mlhip_msm_launch(g1, d_points_g1, d_scalars, scalars_mont, n, stream);
     if (rc) return rc;
@@ -553,9 +615,9 @@ int mlhip_msm_g1g2(int curve, const void* points_g1, const void* points_g2, cons
   if (window_c == 0) window_c = pick_window(n, ops->fr_bits);
   int rc = ensure_device();
   if (rc) return rc;
-  PoolEntry* e1 = pool_acquire(curve, MLHIP_GROUP_G1, window_c, n, ops->g1, rc);
+  PoolEntry* e1 = pool_acquire(curve, MLHIP_GROUP_G1, window_c, ops->fr_bits, n, ops->g1, rc);
   if (!e1) return rc;
-  PoolEntry* e2 = pool_acquire(curve, MLHIP_GROUP_G2, window_c, n, ops->g2, rc);
+  PoolEntry* e2 = pool_acquire(curve, MLHIP_GROUP_G2, window_c, ops->fr_bits, n, ops->g2, rc);
   if (!e2) {
     pool_release(e1, false);
     return rc;
@@ -613,24 +675,29 @@ int mlhip_msm_plan_assume_srs(mlhip_msm_plan* p, int on) {
 
 int mlhip_msm_plan_timings(mlhip_msm_plan* p, float* ms, int cap) {
   if (!p || !ms) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int k = cap < 11 ? cap : 11;
+  int k = cap < 12 ? cap : 12;
   for (int i = 0; i < k && i < 6; i++) ms[i] = p->ms[i];
   if (k >= 7) ms[6] = p->tiles_timed > 0 ? (float)p->tiles_timed : 1.0f;
   if (k >= 8) ms[7] = (float)p->c;
   if (k >= 9) ms[8] = (float)p->Wd;
   if (k >= 10) ms[9] = p->last_ed ? 1.0f : 0.0f;
   if (k >= 11) ms[10] = p->fold ? 1.0f : 0.0f;
+  if (k >= 12) ms[11] = (float)p->bits;  // the plan's scalar width (fr_bits: full width)
   return k;
 }
 
 int mlhip_msm_g1(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
                  void* out_affine) {
-  return msm_host_buffers(curve, MLHIP_GROUP_G1, points, scalars, scalars_mont, n, window_c, out_affine);
+  int c = 0, bits = 0;  // (window_c may carry a scalar width: MLHIP_WINDOW_BITS)
+  unpack_window(window_c, c, bits);
+  return msm_host_buffers(curve, MLHIP_GROUP_G1, points, scalars, scalars_mont, n, c, out_affine, bits);
 }
 
 int mlhip_msm_g2(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
                  void* out_affine) {
-  return msm_host_buffers(curve, MLHIP_GROUP_G2, points, scalars, scalars_mont, n, window_c, out_affine);
+  int c = 0, bits = 0;
+  unpack_window(window_c, c, bits);
+  return msm_host_buffers(curve, MLHIP_GROUP_G2, points, scalars, scalars_mont, n, c, out_affine, bits);
 }
 
 int mlhip_scalar_mul_device(int curve, int group, const void* d_points, size_t point_stride, const void* d_scalars,

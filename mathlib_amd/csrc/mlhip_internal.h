@@ -47,6 +47,9 @@ struct mlhip_msm_plan {
   int curve, group, device, c, W, L, lgL, nb, nsel;
   size_t max_n;
   uint32_t M, T;
+  // the scalar width the window layout covers (bits + 1 bits in Wd windows): the curve's fr_bits, or less for a plan made by
+  // mlhip_msm_plan_create_bits, whose kernels mask every canonical scalar to its low `bits` bits (msm_body.h: fr_mask_bits)
+  int bits = 0;
   // Shifted-base tables (msm_fold.h; resident bases only).  Wd = digits per scalar.  A plain plan has one bucket set per
   // digit position: Wd == W windows of M = 2^(c-1) buckets.  A FOLDED plan (fold != 0) has ONE set of 2^(c-1) buckets for
   // all Wd digits -- digit j of scalar i adds row (j, i) = 2^off(j) P_i of the table (off(j) = first bit of digit j) instead of P_i -- cut into W groups of

@@ -50,7 +50,10 @@ struct HostCall {
 // ---- api_msm.hip ----------------------------------------------------------------------------------------------------------
 int pick_window(size_t n, int fr_bits);
 // fold_tile != 0: a plan over shifted-base tables (msm_fold.h, mlhip_internal.h)
-int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out);
+// scalar_bits: 0 or >= the curve's fr_bits = full width; 1 .. fr_bits - 1 = a short-scalar plan (ignored when fold_tile != 0)
+int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits = 0);
+// the window width the library picks for n scalars of `bits` bits in `group` (bits == fr_bits: pick_window(n, fr_bits))
+int pick_window_bits(size_t n, int bits, int fr_bits, int group = MLHIP_GROUP_G1);
 void plan_reserve_edwards(mlhip_msm_plan* p);
 // Number of segments a host-buffer MSM is streamed in (1 = one upload, one pass), and the segment train itself
 int stream_segments(int group, size_t n, const mlhip_msm_plan* plan);

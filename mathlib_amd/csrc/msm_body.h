@@ -80,6 +80,34 @@ MLHIP_HD void fr_canonical(uint32_t (&s)[8], const uint32_t* in, bool mont) {
   for (int i = 0; i < 8; i++) s[i] = t[i];
 }
 
+// Short-scalar plans (mlhip_msm_plan_create_bits): the canonical value masked to its low `bits` bits -- the one place that
+// does it, for the device kernels, the host build and the tests alike.  bits >= FR_BITS leaves the value as it is (a
+// canonical scalar is below r < 2^FR_BITS), so full-width plans pass C::FR_BITS and pay one compare.
+MLHIP_HD void fr_mask_bits(uint32_t (&s)[8], int bits) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int lo = 32 * i;
+    if (bits <= lo)
+      s[i] = 0;
+    else if (bits < lo + 32)
+      s[i] &= (1u << (bits - lo)) - 1u;
+  }
+}
+template <class C>
+MLHIP_HD void fr_canonical_bits(uint32_t (&s)[8], const uint32_t* in, bool mont, int bits) {
+  fr_canonical<C>(s, in, mont);
+  if (bits < C::FR_BITS) fr_mask_bits(s, bits);
+}
+
+// Effective window width of a plan over `bits`-bit scalars asked for width c: W = ceil((bits + 1) / c) windows need only
+// c' = ceil((bits + 1) / W) <= c bits each, and ceil((bits + 1) / c') = W again, so the balanced layout under c' is the
+// same W windows with 2^(c'-1) buckets instead of 2^(c-1).  Only short-scalar plans are normalised this way: a full-width
+// plan keeps the c it was asked for (its geometry is what it always was).
+MLHIP_HD int msm_effective_c(int bits, int c) {
+  const int W = (bits + c) / c;
+  return (bits + W) / W;
+}
+
 MLHIP_HD int msm_num_windows(int fr_bits, int c) { return (fr_bits + 1 + c - 1) / c; }
 
 // Window layout.  The FR_BITS + 1 bits of a scalar (the extra bit absorbs the last carry) are spread over
@@ -100,6 +128,14 @@ MLHIP_HD WinLayout msm_win_layout(int fr_bits, int c) {
 }
 MLHIP_HD int msm_win_off(int wbase, int wrem, int w) { return w * wbase + (w < wrem ? w : wrem); }
 MLHIP_HD int msm_win_bits(int wbase, int wrem, int w) { return wbase + (w < wrem ? 1 : 0); }
+
+// The Horner pass of the host tail (msm_plan.h: host_tail): down[w] = doublings between window w and window w - 1 of the
+// layout over `bits` + 1 bits (down[0] = 0); their sum is off(W - 1), below the plan's scalar width.
+inline void msm_window_shifts(int bits, int c, int* down /* [W] */) {
+  const WinLayout wl = msm_win_layout(bits, c);
+  down[0] = 0;
+  for (int w = 1; w < wl.W; w++) down[w] = msm_win_off(wl.base, wl.rem, w) - msm_win_off(wl.base, wl.rem, w - 1);
+}
 
 // Signed digit of window w: v = bits [off, off + width) + carry; v > 2^(width-1) => v -= 2^width, carry 1.
 // Returns the magnitude (0 = skip; bucket = magnitude - 1), sets neg and the carry into the next window.
@@ -129,11 +165,12 @@ MLHIP_HD int fb_windows(int w) { return (256 + w - 1) / w; }
 
 // Encoded as 0 (skip) or (magnitude << 1) | sign with magnitude in [1, 2^(width-1)] -> bucket magnitude-1.
 template <class C>
+// (`bits`: the plan's scalar width -- the layout covers bits + 1 bits and the value is masked to `bits`)
 MLHIP_HD void msm_digits_body(size_t i, size_t n, const uint32_t* scalars, bool mont, int c, int W,
-                              uint32_t* digits /* [W][n] */) {
+                              uint32_t* digits /* [W][n] */, int bits = C::FR_BITS) {
   uint32_t s[8];
-  fr_canonical<C>(s, scalars + 8 * i, mont);
-  const WinLayout l = msm_win_layout(C::FR_BITS, c);
+  fr_canonical_bits<C>(s, scalars + 8 * i, mont, bits);
+  const WinLayout l = msm_win_layout(bits, c);
   uint32_t carry = 0, neg = 0;
   for (int w = 0; w < W; w++) {
     const uint32_t mag = msm_window_digit(s, msm_win_off(l.base, l.rem, w), msm_win_bits(l.base, l.rem, w), carry, neg);

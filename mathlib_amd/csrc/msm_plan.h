@@ -231,7 +231,6 @@ void host_tail(const mlhip_msm_plan* p, XYZZ<F>& total) {
     host_tail_fold<F>(p, total);
     return;
   }
-  const WinLayout wl = msm_win_layout(F::Curve::FR_BITS, p->c);
   const size_t sums = (size_t)p->W * p->nsel * sizeof(XYZZ<F>);
   std::vector<unsigned char> blob(sizeof(HostTailHeader) + sums);
   const HostTailHeader h{p->nb, p->lgL, p->nsel, 0};
@@ -242,7 +241,7 @@ void host_tail(const mlhip_msm_plan* p, XYZZ<F>& total) {
   // the sequential part: one doubling per scalar bit.  In Jacobian coordinates since round 4 (ec_jac.h: 2M + 5S a doubling
   // instead of 6M + 3S; the 16 additions are dearer and do not matter)
   std::vector<int> down(p->W, 0);
-  for (int w = 1; w < p->W; w++) down[w] = msm_win_off(wl.base, wl.rem, w) - msm_win_off(wl.base, wl.rem, w - 1);
+  msm_window_shifts(p->bits, p->c, down.data());  // (a short-scalar plan: its own, shorter layout)
   horner_jac<F>(total, V.data(), p->W, down.data());
 }
 
@@ -320,7 +319,7 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
     }
     const unsigned blocks = (unsigned)((n + tile - 1) / tile);
     k_coarse_hist<C><<<dim3(blocks), dim3(256), NB * 4, st>>>((const uint32_t*)d_scalars, n, mont, p->c, Wd, p->sort_low, NB,
-                                                            p->d_coarse_count, p->d_blockhist, tile, fold_stride);
+                                                            p->d_coarse_count, p->d_blockhist, tile, fold_stride, p->bits);
     if (prof) HIPCHK(hipEventRecord(p->ev[1], st));
     launch_scan(p->d_coarse_count, p->d_coarse_off, p->d_tilesums, NB, st);
     if (staged) {
@@ -329,11 +328,11 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
       HIPCHK(hipFuncSetAttribute((const void*)k_coarse_scatter_staged<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
       k_coarse_scatter_staged<C><<<dim3(blocks), dim3(1024), staged_lds(tile), st>>>(
           (const uint32_t*)d_scalars, n, mont, p->c, Wd, p->sort_low, p->sort_idx_bits, NB, p->d_coarse_off, p->d_coarse_cursor,
-          p->d_digits, p->d_blockhist, tile, group, fold_stride);
+          p->d_digits, p->d_blockhist, tile, group, fold_stride, p->bits);
     } else {
       k_coarse_scatter<C><<<dim3(blocks), dim3(256), NB * 8, st>>>((const uint32_t*)d_scalars, n, mont, p->c, Wd, p->sort_low,
                                                                  p->sort_idx_bits, NB, p->d_coarse_off, p->d_coarse_cursor,
-                                                                 p->d_digits, p->d_blockhist, tile, fold_stride);
+                                                                 p->d_digits, p->d_blockhist, tile, fold_stride, p->bits);
     }
     // bins more than 8x the mean (and at least 32768 entries) are sorted by many workgroups
     const uint32_t big_bin = (uint32_t)std::min<size_t>(std::max<size_t>(32768, 8 * ((size_t)Wd * n / NB)), 0x7fffffffu);
@@ -353,7 +352,7 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
       size_t blocks = (n + 255) / 256;
       if (blocks > 65536) blocks = 65536;
       k_digits<C><<<dim3((unsigned)blocks), dim3(256), 0, st>>>((const uint32_t*)d_scalars, n, mont, p->c, p->W, p->M,
-                                                                 p->d_digits, p->d_counts);
+                                                                 p->d_digits, p->d_counts, p->bits);
     }
     if (prof) HIPCHK(hipEventRecord(p->ev[1], st));
     launch_scan(p->d_counts, p->d_offsets, p->d_tilesums, nbuckets, st);
@@ -811,6 +810,7 @@ int sort_ahead_prepare(mlhip_msm_plan* p, size_t seg, bool& on) {
       h->group = p->group;
       h->device = p->device;
       h->c = p->c;
+      h->bits = p->bits;
       h->W = p->W;
       h->Wd = p->Wd;
       h->fold = p->fold;
@@ -913,8 +913,8 @@ int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1
                        hipStream_t st) {
   typedef FpField<C> F1;
   typedef Fp2Field<C> F2;
-  if (p1->c != p2->c || p1->W != p2->W || p1->M != p2->M)
-    return mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width");
+  if (p1->c != p2->c || p1->W != p2->W || p1->M != p2->M || p1->bits != p2->bits)
+    return mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width and scalar width");
   if (p1->fold || p2->fold) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
   const int K = shared_segments(h_scalars != nullptr, n);
   StreamCtx c1, c2;

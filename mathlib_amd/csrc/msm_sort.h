@@ -10,10 +10,10 @@ namespace mlhip {
 template <class C>
 __global__ void __launch_bounds__(256) k_digits(const uint32_t* __restrict__ scalars, size_t n, int mont, int c, int W,
                                                 uint32_t M, uint32_t* __restrict__ digits,
-                                                uint32_t* __restrict__ counts) {
+                                                uint32_t* __restrict__ counts, int bits) {
   size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    msm_digits_body<C>(i, n, scalars, mont != 0, c, W, digits);
+    msm_digits_body<C>(i, n, scalars, mont != 0, c, W, digits, bits);
     for (int w = 0; w < W; w++) {
       uint32_t d = digits[(size_t)w * n + i];
       if (d) atomicAdd(&counts[(size_t)w * M + (d >> 1) - 1], 1u);
@@ -124,21 +124,23 @@ static inline int sort_tile_for(size_t n) {
 template <class C>
 __global__ void __launch_bounds__(256) k_coarse_hist(const uint32_t* __restrict__ scalars, size_t n, int mont, int c, int W,
                                                      int low, uint32_t NB, uint32_t* __restrict__ coarse_count,
-                                                     uint16_t* __restrict__ blockhist, int tile, uint32_t fold_stride) {
+                                                     uint16_t* __restrict__ blockhist, int tile, uint32_t fold_stride, int bits) {
   extern __shared__ uint32_t lds_u32[];
   uint32_t* hist = lds_u32;
   for (uint32_t b = threadIdx.x; b < NB; b += 256) hist[b] = 0;
   __syncthreads();
   const uint32_t cb_shift = (uint32_t)(c - 1 - low);  // coarse bins per window = 1 << cb_shift
+  // bits: the plan's scalar width (C::FR_BITS unless it is a short-scalar plan: the layout covers bits + 1 bits, the
+  // canonical value is masked to `bits`)
   // fold_stride != 0: a folded plan (msm_fold.h) -- the W digits of a scalar (same layout) share one bucket set (window 0 of
   // the bin numbering) and digit w's entry carries the table row index i + w fold_stride
-  const WinLayout wl = msm_win_layout(C::FR_BITS, c);
+  const WinLayout wl = msm_win_layout(bits, c);
   for (int k = 0; k < tile / 256; k++) {
     size_t i = (size_t)blockIdx.x * tile + (size_t)k * 256 + threadIdx.x;
     if (i >= n) break;
     // recompute the digit chain window by window (no per-lane array: keeps this in registers)
     uint32_t s[8];
-    fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+    fr_canonical_bits<C>(s, scalars + 8 * i, mont != 0, bits);
     uint32_t carry = 0, neg = 0;
     for (int w = 0; w < W; w++) {
       const uint32_t mag = msm_window_digit(s, msm_win_off(wl.base, wl.rem, w), msm_win_bits(wl.base, wl.rem, w), carry, neg);
@@ -160,12 +162,12 @@ __global__ void __launch_bounds__(256) k_coarse_scatter(const uint32_t* __restri
                                                         int low, int idx_bits, uint32_t NB,
                                                         const uint32_t* __restrict__ coarse_off,
                                                         uint32_t* __restrict__ coarse_cursor, uint32_t* __restrict__ tmp,
-                                                        const uint16_t* __restrict__ blockhist, int tile, uint32_t fold_stride) {
+                                                        const uint16_t* __restrict__ blockhist, int tile, uint32_t fold_stride, int bits) {
   extern __shared__ uint32_t lds_u32[];
   uint32_t* hist = lds_u32;       // per-block count, then running rank
   uint32_t* base = lds_u32 + NB;  // global position of this block's slice of each bin
   const uint32_t cb_shift = (uint32_t)(c - 1 - low);
-  const WinLayout wl = msm_win_layout(C::FR_BITS, c);
+  const WinLayout wl = msm_win_layout(bits, c);
   // pass 1: this block's counts, computed by k_coarse_hist
   for (uint32_t b = threadIdx.x; b < NB; b += 256) hist[b] = blockhist[(size_t)blockIdx.x * NB + b];
   __syncthreads();
@@ -181,7 +183,7 @@ __global__ void __launch_bounds__(256) k_coarse_scatter(const uint32_t* __restri
     size_t i = (size_t)blockIdx.x * tile + (size_t)k * 256 + threadIdx.x;
     if (i >= n) break;
     uint32_t s[8];
-    fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+    fr_canonical_bits<C>(s, scalars + 8 * i, mont != 0, bits);
     uint32_t carry = 0, neg = 0;
     for (int w = 0; w < W; w++) {
       const uint32_t mag = msm_window_digit(s, msm_win_off(wl.base, wl.rem, w), msm_win_bits(wl.base, wl.rem, w), carry, neg);
@@ -208,7 +210,7 @@ __global__ void __launch_bounds__(1024) k_coarse_scatter_staged(const uint32_t* 
                                                                 const uint32_t* __restrict__ coarse_off,
                                                                 uint32_t* __restrict__ coarse_cursor, uint32_t* __restrict__ tmp,
                                                                 const uint16_t* __restrict__ blockhist, int tile, int group,
-                                                                uint32_t fold_stride) {
+                                                                uint32_t fold_stride, int bits) {
   extern __shared__ uint32_t lds_u32[];
   uint32_t* cnt = lds_u32;            // this block's count per bin, then the running rank
   uint32_t* loc = lds_u32 + NB;       // start of the bin's run in the staged image
@@ -217,7 +219,7 @@ __global__ void __launch_bounds__(1024) k_coarse_scatter_staged(const uint32_t* 
   __shared__ uint32_t wave_sum[16];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t cb_shift = (uint32_t)(c - 1 - low);
-  const WinLayout wl = msm_win_layout(C::FR_BITS, c);
+  const WinLayout wl = msm_win_layout(bits, c);
   // exclusive scan of the block's histogram: thread t owns bins [t per, (t + 1) per)
   const uint32_t per = (NB + 1023u) / 1024u;
   uint32_t mine = 0;
@@ -253,7 +255,7 @@ __global__ void __launch_bounds__(1024) k_coarse_scatter_staged(const uint32_t* 
     const size_t i = (size_t)blockIdx.x * tile + (size_t)k * 1024 + tid;
     if (i < n) {
       uint32_t s[8];
-      fr_canonical<C>(s, scalars + 8 * i, mont != 0);
+      fr_canonical_bits<C>(s, scalars + 8 * i, mont != 0, bits);
       uint32_t carry = 0, neg = 0;
       for (int w = 0; w < W; w++) {
         const uint32_t mag = msm_window_digit(s, msm_win_off(wl.base, wl.rem, w), msm_win_bits(wl.base, wl.rem, w), carry, neg);

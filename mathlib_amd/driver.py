@@ -450,6 +450,26 @@ class Curve:
         check(load().mlhip_msm_g2(self.id, pts, self._scalars(b), 1 if self.scalars_mont else 0, len(a), self.window_c, out))
         return G2(out.raw, self)
 
+    def _msm_short(self, group: int, a, b: Sequence[Zr], bits: int, name: str):
+        if len(b) < len(a):
+            raise IndexError("%s: fewer scalars than points" % name)
+        if len(b) != len(a):
+            return None
+        return _lib.msm_bits(self.id, group, b"".join(p.raw for p in a), self._scalars(b), self.scalars_mont, bits, len(a),
+                             self.window_c)
+
+    def MultiScalarMulShort(self, a: Sequence[G1], b: Sequence[Zr], bits: int) -> G1:
+        """MultiScalarMul for scalars known to be below 2^bits (additive; mlhip_msm_bits): sum_i [b_i mod 2^bits] a_i, the
+        same point as MultiScalarMul when the scalars keep the promise, in fewer windows.  bits = 0: full width.  Same length
+        rules as MultiScalarMul."""
+        raw = self._msm_short(GROUP_G1, a, b, bits, "MultiScalarMulShort")
+        return self.NewG1() if raw is None else G1(raw, self)
+
+    def MultiScalarMulG2Short(self, a: Sequence[G2], b: Sequence[Zr], bits: int) -> G2:
+        """the same in G2"""
+        raw = self._msm_short(GROUP_G2, a, b, bits, "MultiScalarMulG2Short")
+        return self.NewG2() if raw is None else G2(raw, self)
+
     def SumG1(self, points: Sequence[G1]) -> G1:
         """points[0] + points[1] + ...: G1.Add in a loop (driver/gurvy/bls12381/bls12-381.go, Add) as one call; long lists
         are summed on the device (mlhip_g1_sum, MLHIP_SUM_DEVICE_MIN).  An empty list gives the identity."""
