@@ -29,6 +29,7 @@ package hip
 #include <stdlib.h>
 #include "mlhip.h"
 #include "mlhip_bits.h"
+#include "mlhip_products.h"
 */
 import "C"
 
@@ -427,6 +428,67 @@ func (c *Curve) PairingBatch(g2s []driver.G2, g1s []driver.G1) []driver.Gt {
 	check(func() C.int {
 		return C.mlhip_pairing_batch(C.MLHIP_CURVE_BLS12_381,
 		unsafe.Pointer(&p[0]), unsafe.Pointer(&q[0]), C.size_t(n), unsafe.Pointer(&gts[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range gts {
+		out[i] = &gurvy381.Gt{GT: gts[i]}
+	}
+	return out
+}
+
+// MillerLoopProducts returns out[k] = prod_j Pairing(g2s[k][j], g1s[k][j]): K products of m pairs each, any m, in one device
+// call (include/mlhip.h: "products of any length", mlhip_miller_loop_products); not final-exponentiated, like Pairing.  Every
+// product has the same length: a shorter one is padded with pairs at infinity.
+func (c *Curve) MillerLoopProducts(g2s [][]driver.G2, g1s [][]driver.G1) []driver.Gt {
+	n := len(g1s)
+	if len(g2s) != n {
+		panic("hip: MillerLoopProducts length mismatch")
+	}
+	if n == 0 {
+		return nil
+	}
+	m := len(g1s[0])
+	if m == 0 {
+		panic("hip: MillerLoopProducts needs at least one pair per product")
+	}
+	p := make([]bls12381.G1Affine, 0, n*m)
+	q := make([]bls12381.G2Affine, 0, n*m)
+	for k := range g1s {
+		if len(g1s[k]) != m || len(g2s[k]) != m {
+			panic("hip: MillerLoopProducts: every product takes the same number of G1 and of G2 points")
+		}
+		for j := 0; j < m; j++ {
+			p = append(p, g1s[k][j].(*gurvy381.G1).G1Affine)
+			q = append(q, g2s[k][j].(*gurvy381.G2).G2Affine)
+		}
+	}
+	gts := make([]bls12381.GT, n)
+	check(func() C.int {
+		return C.mlhip_miller_loop_products(C.MLHIP_CURVE_BLS12_381,
+			unsafe.Pointer(&p[0]), unsafe.Pointer(&q[0]), C.size_t(m), C.size_t(n), unsafe.Pointer(&gts[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range gts {
+		out[i] = &gurvy381.Gt{GT: gts[i]}
+	}
+	return out
+}
+
+// PairingProducts returns out[k] = FExp(prod_j Pairing(g2s[k][j], g1s[k][j])): FExp of MillerLoopProducts, through
+// mlhip_final_exp.
+func (c *Curve) PairingProducts(g2s [][]driver.G2, g1s [][]driver.G1) []driver.Gt {
+	ml := c.MillerLoopProducts(g2s, g1s)
+	n := len(ml)
+	if n == 0 {
+		return nil
+	}
+	in := make([]bls12381.GT, n)
+	for i := range ml {
+		in[i] = ml[i].(*gurvy381.Gt).GT
+	}
+	gts := make([]bls12381.GT, n)
+	check(func() C.int {
+		return C.mlhip_final_exp(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&in[0]), C.size_t(n), unsafe.Pointer(&gts[0]))
 	})
 	out := make([]driver.Gt, n)
 	for i := range gts {
@@ -923,6 +985,58 @@ func (p *G2Prepared) Pairing2Batch(p1a, p1b []driver.G1) []driver.Gt {
 	gts := make([]bls12381.GT, n)
 	check(func() C.int {
 		return C.mlhip_pairing_prepared(p.h, unsafe.Pointer(&g1[0]), nil, 2, C.size_t(n), unsafe.Pointer(&gts[0]))
+	})
+	out := make([]driver.Gt, n)
+	for i := range gts {
+		out[i] = &gurvy381.Gt{GT: gts[i]}
+	}
+	return out
+}
+
+// MillerLoopBatch returns out[k] = prod_j MillerLoop(g1s[k][j], Q[index[j]]) (index nil: Q[j]) for any number of pairs per
+// product (mlhip_miller_loop_prepared_products); compare after FExp, as Pairing.
+func (p *G2Prepared) MillerLoopBatch(g1s [][]driver.G1, index []uint32) []driver.Gt {
+	return p.products(false, g1s, index)
+}
+
+// PairingBatch returns out[k] = FExp of the same product (mlhip_pairing_prepared_products).
+func (p *G2Prepared) PairingBatch(g1s [][]driver.G1, index []uint32) []driver.Gt {
+	return p.products(true, g1s, index)
+}
+
+func (p *G2Prepared) products(fused bool, g1s [][]driver.G1, index []uint32) []driver.Gt {
+	n := len(g1s)
+	if n == 0 {
+		return nil
+	}
+	m := len(g1s[0])
+	if m == 0 || (index != nil && len(index) != m) || (index == nil && m > p.m) {
+		panic("hip: G2Prepared: one prepared point per pair of a product")
+	}
+	for _, x := range index {
+		if int(x) >= p.m {
+			panic("hip: G2Prepared: point index out of range")
+		}
+	}
+	g1 := make([]bls12381.G1Affine, 0, n*m)
+	for k := range g1s {
+		if len(g1s[k]) != m {
+			panic("hip: G2Prepared: every product takes the same number of G1 points")
+		}
+		for j := 0; j < m; j++ {
+			g1 = append(g1, g1s[k][j].(*gurvy381.G1).G1Affine)
+		}
+	}
+	var ix *C.uint32_t
+	if index != nil {
+		ix = (*C.uint32_t)(unsafe.Pointer(&index[0]))
+	}
+	gts := make([]bls12381.GT, n)
+	check(func() C.int {
+		if fused {
+			return C.mlhip_pairing_prepared_products(p.h, unsafe.Pointer(&g1[0]), ix, C.size_t(m), C.size_t(n), unsafe.Pointer(&gts[0]))
+		}
+		return C.mlhip_miller_loop_prepared_products(p.h, unsafe.Pointer(&g1[0]), ix, C.size_t(m), C.size_t(n), unsafe.Pointer(&gts[0]))
 	})
 	out := make([]driver.Gt, n)
 	for i := range gts {

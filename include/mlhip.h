@@ -112,9 +112,10 @@ MLHIP_API int mlhip_msm_g2(int curve, const void* points, const void* scalars, i
 MLHIP_API int mlhip_msm_g1g2(int curve, const void* points_g1, const void* points_g2, const void* scalars, int scalars_mont, size_t n,
                    int window_c, void* out_g1, void* out_g2);
 
-/* out[k] = prod_{j < pairs_per_product} MillerLoop(g1[k*ppp + j], g2[k*ppp + j]); Pairing = 1, Pairing2 = 2
- * (pairs_per_product <= 4).  Pairs holding an infinity contribute 1.  NOT final-exponentiated: like gurvy's
- * Pairing the value is only meaningful after mlhip_final_exp. */
+/* out[k] = prod_{j < pairs_per_product} MillerLoop(g1[k*ppp + j], g2[k*ppp + j]); Pairing = 1, Pairing2 = 2.
+ * pairs_per_product is 1 .. 4 as a plain number, or MLHIP_PRODUCT_PAIRS(m) for any m ("products of any length" below).
+ * Pairs holding an infinity contribute 1.  NOT final-exponentiated: like gurvy's Pairing the value is only meaningful
+ * after mlhip_final_exp. */
 MLHIP_API int mlhip_miller_loop(int curve, const void* g1, const void* g2, size_t pairs_per_product, size_t n_products,
                       void* out_gt);
 /* out[i] = in[i]^(k (p^12-1)/r), k = 3 (BLS12 curves) or 2x(6x^2+3x+1) (BN254): gnark's and kilic's value */
@@ -236,6 +237,44 @@ MLHIP_API int mlhip_msm_plan_timings(mlhip_msm_plan* plan, float* ms, int cap);
  * 0.125 / 0.25 / 0.5: the full-width plan already skips zero digits). */
 #define MLHIP_WINDOW_BITS(window_c, scalar_bits) \
   ((int)((window_c) < 0 || (window_c) > 255 ? 0xFF : (window_c)) | (int)(((scalar_bits) < 0 || (scalar_bits) > 256 ? 0x3FF : (scalar_bits)) << 8))
+
+/* ---- products of any length: K products of m pairs each, for any m ------------------------------------------------------------
+ * For callers with K independent products of MORE than four pairs: K aggregated signatures over m messages each, K
+ * pairing-product equations of five to nine pairs, a batch of multi-openings, a verifier that folds m proofs into each of K
+ * checks.
+ *
+ * Result.  out[k] = prod_{j < m} MillerLoop(g1[k m + j], g2[k m + j]); for the prepared forms the G2 point of slot j is
+ * Q[q_index[j]] (q_index: m HOST entries shared by all products, read before the call returns, repeats allowed), and a NULL
+ * q_index pairs slot j with point j, which needs m <= the handle's count.  A pair with an infinity on either side contributes
+ * 1; a product of such pairs only is 1 (mlhip_pairing_prepared*: FExp(1) = 1).  The Miller value is the exact Fp12 product,
+ * however the library groups the pairs: its bytes are those of the library's own calls with at most four pairs multiplied
+ * together with mlhip_gt_mul.  n_products = 0 returns 0 and launches nothing; n_products * m overflowing size_t, or a null
+ * pointer in a non-empty batch, is MLHIP_EINVAL before anything is launched.  A RAGGED batch (products of different
+ * lengths) is a uniform one padded with infinity pairs (all-zero points): there is no offsets array.
+ *
+ * How it is said.  The library's dynamic symbol table does not grow (the tests pin it): the length travels in the
+ * pairs_per_product / ppp argument of exactly six entry points -- mlhip_miller_loop, mlhip_miller_loop_device,
+ * mlhip_miller_loop_prepared, mlhip_miller_loop_prepared_device, mlhip_pairing_prepared, mlhip_pairing_prepared_device -- as
+ * MLHIP_PRODUCT_PAIRS(m) below: bit 63 set, m in the low 32 bits.  It is taken apart in those six and nowhere else.
+ * include/mlhip_products.h wraps this in six inline functions for C, C++ and cgo callers, with m as a plain size_t:
+ * mlhip_miller_loop_products[_device], mlhip_miller_loop_prepared_products[_device], mlhip_pairing_prepared_products[_device].
+ *   - A PLAIN value keeps its meaning exactly: 1 .. 4 accepted, anything else MLHIP_EINVAL ("pairs_per_product must be 1..4").
+ *   - MLHIP_PRODUCT_PAIRS(m) with m <= 4 is the plain call: same path, same bytes.
+ *   - m = 0 or m >= 2^32 packs to a value that every entry point rejects with MLHIP_EINVAL.
+ *
+ * How it runs.  A product is cut into groups of `per` pairs (and a shorter tail); one launch runs the
+ * Miller loops of all groups of all products -- the kernels of the plain calls, quads or lane pairs by the number of groups
+ * -- into a per-device scratch buffer, log2-many launches fold each product's values into one (Gt products on the device),
+ * and the fused forms then run the final exponentiation on the K folded values.  per = 1 while K m pairs leave the chip
+ * under-filled, 4 from 2^17 pairs on (mlhip_pairing_product's rule; profiles/miller_products_ab.txt);
+ * MLHIP_MILLER_GROUP=1|2|4 forces it.  The scratch is kept between calls (mlhip_release_cache frees it) and never exceeds
+ * 1 GiB: a larger call runs in slabs of products, one after the other on the same stream, and a single product whose partial
+ * values alone exceed 1 GiB is MLHIP_EINVAL.  The _device forms are asynchronous and in order on `stream` like every other
+ * _device form; calls on different streams share the scratch and are ordered on the device by an event.  A long product is
+ * never spread over a device list: it runs on the calling thread's first device (the prepared forms: the handle's).
+ * MLHIP_G2_PREPARED_GENERAL does not apply to m > 4. */
+#define MLHIP_PRODUCT_PAIRS(m) \
+  (((size_t)1 << 63) | ((m) >= 1 && (unsigned long long)(m) <= 0xFFFFFFFFull ? (size_t)(m) : (size_t)0))
 
 /* The device forms of the entry points above (and the _device forms further down, unless their comment says otherwise): device
  * pointers in and out; they enqueue their kernels on `stream` and return, so the work runs in order on `stream` (NULL = the
@@ -387,9 +426,9 @@ MLHIP_API int mlhip_g2_prepared_destroy(mlhip_g2_prepared* h);
  * not final-exponentiated (raw values are defined up to what FExp kills, as for mlhip_miller_loop; after mlhip_final_exp they
  * are byte-identical to mlhip_final_exp(mlhip_miller_loop(..)) on the expanded pairs).  q_index is HOST memory in both forms
  * and has ppp entries that ALL products share: slot j of every product pairs with the same Q, which keeps the line reads
- * uniform across a wave.  ppp = 1 .. 4.  A G1 argument at infinity, or a Q at infinity, contributes 1.  n_products = 0 does
- * nothing.  MLHIP_EINVAL before anything is launched for a null handle, ppp outside 1 .. 4, an index >= m, ppp > m without
- * q_index.
+ * uniform across a wave.  ppp = 1 .. 4, or MLHIP_PRODUCT_PAIRS(m) for any length ("products of any length" above).  A G1
+ * argument at infinity, or a Q at infinity, contributes 1.  n_products = 0 does nothing.  MLHIP_EINVAL before anything is
+ * launched for a null handle, a plain ppp outside 1 .. 4, an index >= m, ppp > m without q_index.
  * Kernels: one product per quad of lanes up to 2^14 products (BLS12-377: 2^15, its Miller loop at every size), per lane pair
  * above -- the sizes the general entry points switch at; MLHIP_PAIRING_QUAD=0|1 forbids / forces the quads.  Switch to the
  * general kernels: at no size, on any curve.  In the A/B against the general entry points on an MI355X
@@ -511,6 +550,8 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_BASES_BATCH_MAX_MB=m       ... tables per handle at most m MB (default 1024; 0 = never: the table-free path)
  *     MLHIP_PAIRING_QUAD=0|1           BLS12-381: never / always one pairing per quad of lanes (default: up to 2^14 elements)
  *     MLHIP_G2_PREPARED_GENERAL=1      mlhip_*_prepared*: the general kernels on the Qs expanded from the handle (same bytes after FExp)
+ *     MLHIP_MILLER_GROUP=1|2|4         products of more than four pairs (MLHIP_PRODUCT_PAIRS): pairs per Miller loop (default: 1 below
+ *                                      2^17 pairs per call, 4 from there on)
  *   2nd impl (parity tests; DESIGN.md section 2 lists which test runs which)
  *     MLHIP_ACC32=1                    boundary-form (32-bit limb) bucket accumulation, G1 and G2
  *     MLHIP_REDUCE32=1, MLHIP_REDUCE_ONE_LANE=1   boundary-form / one-point-per-lane bucket reduction

@@ -16,7 +16,7 @@
 //   Curve::FExp(gt)                      driver/math.go:56-57                         -> mlhip_final_exp
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
-//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
+//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
 //             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, SumG1, SumG2
 #pragma once
@@ -30,6 +30,7 @@
 
 #include "mlhip.h"
 #include "mlhip_bits.h"
+#include "mlhip_products.h"
 
 namespace mlhip_driver {
 
@@ -650,6 +651,40 @@ class Curve {
     }
     return out;
   }
+  // out[k] = prod_j Pairing(g2[k][j], g1[k][j]): K products of m pairs each, any m, in one device call (include/mlhip.h:
+  // "products of any length", mlhip_miller_loop_products); not final-exponentiated, like Pairing.  Every product has the same
+  // length: a shorter one is padded with pairs at infinity.
+  std::vector<Gt> MillerLoopProducts(const std::vector<std::vector<G2>>& g2, const std::vector<std::vector<G1>>& g1) const {
+    if (g2.size() != g1.size()) throw std::invalid_argument("MillerLoopProducts: length mismatch");
+    std::vector<Gt> out;
+    const size_t n = g1.size();
+    if (n == 0) return out;
+    const size_t m = g1[0].size();
+    Bytes p, q, o(gt_bytes * n);
+    for (size_t k = 0; k < n; k++) {
+      if (m == 0 || g1[k].size() != m || g2[k].size() != m)
+        throw std::invalid_argument("MillerLoopProducts: every product takes the same number (at least one) of G1 and of G2 points");
+      for (auto& x : g1[k]) p.insert(p.end(), x.raw.begin(), x.raw.end());
+      for (auto& x : g2[k]) q.insert(q.end(), x.raw.begin(), x.raw.end());
+    }
+    check(mlhip_miller_loop_products(id, p.data(), q.data(), m, n, o.data()));
+    for (size_t i = 0; i < n; i++) {
+      Gt g = new_gt();
+      memcpy(g.raw.data(), o.data() + i * gt_bytes, gt_bytes);
+      out.push_back(g);
+    }
+    return out;
+  }
+  // out[k] = FExp of the same product, through mlhip_final_exp
+  std::vector<Gt> PairingProducts(const std::vector<std::vector<G2>>& g2, const std::vector<std::vector<G1>>& g1) const {
+    std::vector<Gt> out = MillerLoopProducts(g2, g1);
+    if (out.empty()) return out;
+    Bytes in, o(gt_bytes * out.size());
+    for (auto& x : out) in.insert(in.end(), x.raw.begin(), x.raw.end());
+    check(mlhip_final_exp(id, in.data(), out.size(), o.data()));
+    for (size_t i = 0; i < out.size(); i++) memcpy(out[i].raw.data(), o.data() + i * gt_bytes, gt_bytes);
+    return out;
+  }
   Gt PairingProduct(const std::vector<G2>& g2s, const std::vector<G1>& g1s) const {
     if (g2s.size() != g1s.size()) throw std::invalid_argument("PairingProduct: length mismatch");
     Bytes p, q;
@@ -830,7 +865,8 @@ class G2Prepared {
     check(mlhip_g2_prepared_count(h_, &m));
     return m;
   }
-  // out[k] = prod_j MillerLoop(g1[k][j], Q[index[j]]) (no index: Q[j]); compare after FExp, as Curve::Pairing
+  // out[k] = prod_j MillerLoop(g1[k][j], Q[index[j]]) (no index: Q[j]), any number of pairs per product; compare after FExp,
+  // as Curve::Pairing
   std::vector<Gt> MillerLoopBatch(const std::vector<std::vector<G1>>& g1, const std::vector<uint32_t>* index = nullptr) const {
     return run(false, g1, index);
   }
@@ -858,8 +894,9 @@ class G2Prepared {
     const size_t size = curve_->gt_bytes;
     Bytes o(size * n);
     const uint32_t* ix = index ? index->data() : nullptr;
-    check(fused ? mlhip_pairing_prepared(h_, p.data(), ix, ppp, n, o.data())
-                : mlhip_miller_loop_prepared(h_, p.data(), ix, ppp, n, o.data()));
+    // (any number of pairs per product: include/mlhip.h, "products of any length"; up to four it is the plain call)
+    check(fused ? mlhip_pairing_prepared_products(h_, p.data(), ix, ppp, n, o.data())
+                : mlhip_miller_loop_prepared_products(h_, p.data(), ix, ppp, n, o.data()));
     for (size_t i = 0; i < n; i++) {
       Gt g = curve_->new_gt();
       g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);

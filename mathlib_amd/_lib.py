@@ -376,6 +376,59 @@ def g2_prepared_run(lib, handle, gtsz: int, fused: bool, g1: bytes, index, ppp: 
     return out.raw[: n * gtsz]
 
 
+def product_pairs(m: int) -> int:
+    """MLHIP_PRODUCT_PAIRS of include/mlhip.h: a product length in the pairs_per_product / ppp argument of the six Miller-loop
+    entry points (bit 63 set, m in the low 32 bits; m = 0 or m >= 2^32 packs to a value they all reject)"""
+    return (1 << 63) | (m if 1 <= m <= 0xFFFFFFFF else 0)
+
+
+def mlhip_miller_loop_products(lib, curve: int, g1, g2, m: int, n_products: int, out) -> int:
+    """include/mlhip_products.h: n_products Miller-loop products of m pairs each, any m (the return code, as the C function)"""
+    return lib.mlhip_miller_loop(curve, g1, g2, product_pairs(m), n_products, out)
+
+
+def mlhip_miller_loop_products_device(lib, curve: int, d_g1, d_g2, m: int, n_products: int, d_out, stream) -> int:
+    """include/mlhip_products.h: the same on device pointers, in order on `stream`"""
+    return lib.mlhip_miller_loop_device(curve, d_g1, d_g2, product_pairs(m), n_products, d_out, stream)
+
+
+def mlhip_miller_loop_prepared_products(lib, handle, g1, q_index, m: int, n_products: int, out) -> int:
+    """include/mlhip_products.h: products of m pairs against the handle's points (q_index: m host entries, or None)"""
+    return lib.mlhip_miller_loop_prepared(handle, g1, q_index, product_pairs(m), n_products, out)
+
+
+def mlhip_miller_loop_prepared_products_device(lib, handle, d_g1, q_index, m: int, n_products: int, d_out, stream) -> int:
+    """include/mlhip_products.h: the same on device pointers, in order on `stream`"""
+    return lib.mlhip_miller_loop_prepared_device(handle, d_g1, q_index, product_pairs(m), n_products, d_out, stream)
+
+
+def mlhip_pairing_prepared_products(lib, handle, g1, q_index, m: int, n_products: int, out) -> int:
+    """include/mlhip_products.h: FExp of the same products"""
+    return lib.mlhip_pairing_prepared(handle, g1, q_index, product_pairs(m), n_products, out)
+
+
+def mlhip_pairing_prepared_products_device(lib, handle, d_g1, q_index, m: int, n_products: int, d_out, stream) -> int:
+    """include/mlhip_products.h: the same on device pointers, in order on `stream`"""
+    return lib.mlhip_pairing_prepared_device(handle, d_g1, q_index, product_pairs(m), n_products, d_out, stream)
+
+
+def miller_loop_products(curve: int, g1: bytes, g2: bytes, m: int, n_products: int) -> bytes:
+    """mlhip_miller_loop_products over host buffers: n_products raw Miller values (bytes)"""
+    gtsz = sizes(curve)[3]
+    out = ctypes.create_string_buffer(max(1, n_products * gtsz))
+    check(mlhip_miller_loop_products(load(), curve, g1, g2, m, n_products, out))
+    return out.raw[: n_products * gtsz]
+
+
+def g2_prepared_products(lib, handle, gtsz: int, fused: bool, g1: bytes, index, m: int, n: int) -> bytes:
+    """mlhip_miller_loop_prepared_products (fused = False) / mlhip_pairing_prepared_products (True) on the handle `handle`
+    of `lib`: n Gt values (bytes) for n products of m pairs; g1 holds the n * m affine G1 points"""
+    out = ctypes.create_string_buffer(max(1, n * gtsz))
+    fn = mlhip_pairing_prepared_products if fused else mlhip_miller_loop_prepared_products
+    check(fn(lib, handle, g1, q_index_array(index, m), m, n, out))
+    return out.raw[: n * gtsz]
+
+
 def init_devices(devices=None) -> None:
     """the process's device list (mlhip_init): None / [] = every visible device"""
     devices = list(devices or [])

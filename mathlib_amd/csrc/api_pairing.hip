@@ -1,5 +1,6 @@
 // api_pairing.hip -- the pairing, Gt and prepared-G2 entry points of include/mlhip.h (and the field-multiplication probe):
 // argument checking, host-buffer staging and dispatch.  No kernels here.
+#include <cstdint>
 #include <cstring>
 #include <initializer_list>
 #include <string>
@@ -104,13 +105,50 @@ int pairing_device(int curve, int what, const void* d_g1, const void* d_g2, size
   const CurveOps* ops = begin_call(DEVICE_CURVE, curve, n, false, rc);
   return ops ? ops->pairing(what, d_g1, d_g2, ppp, n, d_in, d_out, (hipStream_t)stream) : rc;
 }
+
+// ---- pairs_per_product as the six Miller-loop entry points take it (include/mlhip.h): a plain 1 .. 4, or
+// MLHIP_PRODUCT_PAIRS(m) -- bit 63 set, m in the low 32 bits.  m <= 4 is the plain call whichever way it was said.
+int unpack_pairs(size_t ppp, size_t& m) {
+  m = ppp;
+  if (!(ppp >> 63)) return ppp < 1 || ppp > 4 ? mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4") : 0;
+  m = ppp & 0xFFFFFFFFu;
+  if (((ppp << 1) >> 33) != 0 || m == 0) return mlhip_rt::fail(MLHIP_EINVAL, "MLHIP_PRODUCT_PAIRS(m): m must be 1 .. 2^32 - 1");
+  return 0;
+}
+// n products of m pairs: n m pairs of `each` bytes must be addressable
+int check_products(size_t m, size_t n, size_t each) {
+  if (n > SIZE_MAX / m || n * m > SIZE_MAX / each) return mlhip_rt::fail(MLHIP_EINVAL, "n_products * pairs_per_product overflows");
+  return 0;
+}
+
+// K products of m > 4 pairs against per-product G2 points (pairing_products_run.h): on the calling thread's device, never
+// spread over the device list
+int products_host(int curve, const void* g1, const void* g2, size_t m, size_t n, void* out) {
+  int rc;
+  const CurveOps* ops = begin_call(ARGS_ONLY, curve, n, !out || !g1 || !g2, rc);
+  if (!ops) return rc;
+  if ((rc = check_products(m, n, ops->gt)) != 0 || (rc = ensure_device()) != 0) return rc;
+  return staged_call(n, {{g1, m * ops->g1}, {g2, m * ops->g2}}, {{out, ops->gt}}, [&](void* const* d, void* const* o, hipStream_t st) {
+    return ops->miller_products(nullptr, 0, d[0], d[1], nullptr, m, n, o[0], st);
+  });
+}
+int products_device(int curve, const void* d_g1, const void* d_g2, size_t m, size_t n, void* d_out, void* stream) {
+  int rc;
+  const CurveOps* ops = begin_call(DEVICE_CURVE, curve, n, false, rc);
+  if (!ops || n == 0) return rc;
+  if (!d_g1 || !d_g2 || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if ((rc = check_products(m, n, ops->gt)) != 0) return rc;
+  return ops->miller_products(nullptr, 0, d_g1, d_g2, nullptr, m, n, d_out, (hipStream_t)stream);
+}
 }  // namespace
 
 extern "C" {
 
 int mlhip_miller_loop(int curve, const void* g1, const void* g2, size_t ppp, size_t n_products, void* out_gt) {
-  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
-  return pairing_host(curve, 0, g1, g2, ppp, n_products, nullptr, out_gt);
+  size_t m;
+  if (int rc = unpack_pairs(ppp, m)) return rc;
+  if (m > 4) return products_host(curve, g1, g2, m, n_products, out_gt);
+  return pairing_host(curve, 0, g1, g2, m, n_products, nullptr, out_gt);
 }
 
 int mlhip_final_exp(int curve, const void* in_gt, size_t n, void* out_gt) {
@@ -123,8 +161,10 @@ int mlhip_pairing_batch(int curve, const void* g1, const void* g2, size_t n, voi
 
 int mlhip_miller_loop_device(int curve, const void* d_g1, const void* d_g2, size_t ppp, size_t n_products,
                              void* d_out_gt, void* stream) {
-  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
-  return pairing_device(curve, 0, d_g1, d_g2, ppp, n_products, nullptr, d_out_gt, stream);
+  size_t m;
+  if (int rc = unpack_pairs(ppp, m)) return rc;
+  if (m > 4) return products_device(curve, d_g1, d_g2, m, n_products, d_out_gt, stream);
+  return pairing_device(curve, 0, d_g1, d_g2, m, n_products, nullptr, d_out_gt, stream);
 }
 
 int mlhip_final_exp_device(int curve, const void* d_in_gt, size_t n, void* d_out_gt, void* stream) {
@@ -199,48 +239,59 @@ int mlhip_g2_prepared_count(mlhip_g2_prepared* h, size_t* m) {
   return 0;
 }
 
-// every argument error of the four entry points, before anything is launched; 1 = nothing to do
+// every argument error of the four entry points, before anything is launched; 1 = nothing to do.  ppp: as the caller
+// gave it; m: the pairs per product it means (unpack_pairs)
 static int g2_prepared_check(const mlhip_g2_prepared* h, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
-                             const void* out) {
+                             const void* out, size_t& m) {
   if (!h) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
-  if (ppp < 1 || ppp > 4) return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product must be 1..4");
+  if (int rc = unpack_pairs(ppp, m)) return rc;
   if (q_index) {
-    for (size_t j = 0; j < ppp; j++)
+    for (size_t j = 0; j < m; j++)
       if (q_index[j] >= h->t.m) return mlhip_rt::fail(MLHIP_EINVAL, "q_index entry beyond the handle's points");
-  } else if (ppp > h->t.m) {
+  } else if (m > h->t.m) {
     return mlhip_rt::fail(MLHIP_EINVAL, "pairs_per_product exceeds the handle's points (no q_index)");
   }
   if (n == 0) return 1;
   if (!g1 || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (m > 4) return check_products(m, n, h->ops->gt);
   return 0;
+}
+
+// the launch: products of at most 4 pairs through the prepared kernels' own dispatcher, longer ones through the groups
+static int g2_prepared_launch(mlhip_g2_prepared* h, int what, const void* d_g1, const uint32_t* q_index, size_t m, size_t n,
+                              void* d_out, hipStream_t st) {
+  if (m > 4) return h->ops->miller_products(&h->t, what, d_g1, nullptr, q_index, m, n, d_out, st);
+  return h->ops->g2_prepared(&h->t, what, d_g1, q_index, m, n, d_out, st);
 }
 
 static int g2_prepared_device(mlhip_g2_prepared* h, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,
                               void* d_out, void* stream) {
-  int rc = g2_prepared_check(h, d_g1, q_index, ppp, n, d_out);
+  size_t m;
+  int rc = g2_prepared_check(h, d_g1, q_index, ppp, n, d_out, m);
   if (rc) return rc < 0 ? rc : 0;
   // the launch needs the handle's device current; the caller gets its own current device back (`stream` and the pointers
   // must belong to the handle's device: multi-device handles are out of scope)
   int prev = h->device;
   (void)hipGetDevice(&prev);
   if (prev != h->device && hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
-  rc = h->ops->g2_prepared(&h->t, what, d_g1, q_index, ppp, n, d_out, (hipStream_t)stream);
+  rc = g2_prepared_launch(h, what, d_g1, q_index, m, n, d_out, (hipStream_t)stream);
   if (prev != h->device) (void)hipSetDevice(prev);
   return rc;
 }
 
 static int g2_prepared_host(mlhip_g2_prepared* h, int what, const void* g1, const uint32_t* q_index, size_t ppp, size_t n,
                             void* out) {
-  int rc = g2_prepared_check(h, g1, q_index, ppp, n, out);
+  size_t m;
+  int rc = g2_prepared_check(h, g1, q_index, ppp, n, out, m);
   if (rc) return rc < 0 ? rc : 0;
   if (hipSetDevice(h->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   call_device() = h->device;  // thread_local (the device of this thread's call in progress): the call's scratch is leased on the handle's device
   HostCall hc;
-  hc.reserve(n * ppp * h->ops->g1 + n * h->ops->gt);
-  void* d1 = hc.up(g1, n * ppp * h->ops->g1);
+  hc.reserve(n * m * h->ops->g1 + n * h->ops->gt);
+  void* d1 = hc.up(g1, n * m * h->ops->g1);
   void* dout = hc.dev(n * h->ops->gt);
   if (hc.rc) return hc.rc;
-  rc = h->ops->g2_prepared(&h->t, what, d1, q_index, ppp, n, dout, hc.l.st);
+  rc = g2_prepared_launch(h, what, d1, q_index, m, n, dout, hc.l.st);
   if (rc) return rc;
   return hc.down(out, dout, n * h->ops->gt);
 }

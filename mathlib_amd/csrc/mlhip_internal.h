@@ -187,6 +187,11 @@ struct mlhip_g2_prepared_tables {
   X(C, int, g2_prepared,                                                                                                  \
     (mlhip_g2_prepared_tables * t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,             \
      void* d_out, hipStream_t st))                                                                                        \
+  /* n products of m > 4 pairs (pairing_products_run.h): t null = against the n m points d_g2, else against t's points by   \
+     q_index; what 0 / 2 = Miller values / their final exponentiation, -1 = free the scratch (mlhip_release_cache) */      \
+  X(C, int, miller_products,                                                                                              \
+    (const mlhip_g2_prepared_tables* t, int what, const void* d_g1, const void* d_g2, const uint32_t* q_index, size_t m,  \
+     size_t n, void* d_out, hipStream_t st))                                                                              \
   X(C, void, release_cache, (void))
 
 #define MLHIP_OP_DECLARE(C, ret, name, params) ret mlhip_tu_##name##_##C params;

@@ -11,18 +11,20 @@
 #include "fp2_lanes28.h"
 #include "pairing_quad.h"
 #include "pairing.h"
+#include "pairing_products.h"
 #include "gt_exp_cyclo.h"
 
 namespace mlhip {
 
 template <class C>
 __global__ void __launch_bounds__(64) k_miller(const Affine<FpField<C>>* __restrict__ g1,
-                                               const Affine<Fp2Field<C>>* __restrict__ g2, int ppp, size_t n,
+                                               const Affine<Fp2Field<C>>* __restrict__ g2, MillerGroups mg, size_t n,
                                                Fp12<C>* __restrict__ out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Fp12<C> f;
-  miller_loop<C, 4>(f, g1 + i * ppp, g2 + i * ppp, ppp);
+  const MillerGroupAt at(mg, i);
+  miller_loop<C, 4>(f, g1 + at.first, g2 + at.first, at.count);
   out[i] = f;
 }
 
@@ -86,7 +88,7 @@ __device__ __forceinline__ void lp_load_gt(Fp12<C, Fp2L<C>>& f, const Fp12<C>* i
 // registers instead of dynamically indexed scratch)
 template <class C, int WHAT, int MAXP>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_lp(const Affine<FpField<C>>* __restrict__ g1,
-                                                   const Affine<Fp2Field<C>>* __restrict__ g2, int ppp, size_t n,
+                                                   const Affine<Fp2Field<C>>* __restrict__ g2, MillerGroups mg, size_t n,
                                                    const Fp12<C>* __restrict__ in, Fp12<C>* __restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 1;  // both lanes of a pair share i, so this exit is pair-uniform
@@ -102,13 +104,15 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_lp(const Affine<FpF
   if (WHAT == 1) {
     lp_load_gt<C>(f, in, i);
   } else {
+    const MillerGroupAt at(mg, i);  // this group's first pair and its number of pairs (pairing_products.h)
+    const int ppp = at.count;
     Fp<C> px[MAXP], py[MAXP];
     E2 qx[MAXP], qy[MAXP];
     bool live[MAXP];
     const int hi = lane_is_hi() ? 1 : 0;
     for (int k = 0; k < ppp && k < MAXP; k++) {
-      const Affine<FpField<C>> P = g1[i * ppp + k];
-      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + i * ppp + k);
+      const Affine<FpField<C>> P = g1[at.first + k];
+      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + at.first + k);
       px[k] = P.x;
       py[k] = P.y;
       qx[k].v = q[hi];
@@ -272,8 +276,8 @@ __device__ __forceinline__ void miller_loop_lp28_lds(Fp12<C, Fp2L28<C>>& f, cons
 
 template <class C, int WHAT, int MAXP>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_lp28(const Affine<FpField<C>>* __restrict__ g1,
-                                                                  const Affine<Fp2Field<C>>* __restrict__ g2, int ppp,
-                                                                  size_t n, const Fp12<C>* __restrict__ in,
+                                                                  const Affine<Fp2Field<C>>* __restrict__ g2,
+                                                                  MillerGroups mg, size_t n, const Fp12<C>* __restrict__ in,
                                                                   Fp12<C>* __restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 1;  // both lanes of a pair share i, so this exit is pair-uniform
@@ -283,13 +287,15 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_lp28(const Affine<F
   if (WHAT == 1) {
     lp28_load_gt<C>(f, in, i);
   } else {
+    const MillerGroupAt at(mg, i);  // this group's first pair and its number of pairs (pairing_products.h)
+    const int ppp = at.count;
     Fp28<C> px[MAXP], py[MAXP];
     E2 qx[MAXP], qy[MAXP];
     bool live[MAXP];
     const int hi = lane_is_hi() ? 1 : 0;
     for (int k = 0; k < ppp && k < MAXP; k++) {
-      const Affine<FpField<C>> P = g1[i * ppp + k];
-      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + i * ppp + k);
+      const Affine<FpField<C>> P = g1[at.first + k];
+      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + at.first + k);
       const Fp<C> qxc = q[hi], qyc = q[2 + hi];
       // Q is the point at infinity iff all four of its Fp components are zero (tested on the boundary form)
       uint32_t zq = (fp_is_zero<C>(qxc) & fp_is_zero<C>(qyc)) ? 1u : 0u;
@@ -372,7 +378,7 @@ struct GtShape {
 // exponentiation, 2 = Miller loop of one pair + final exponentiation.
 template <class C, int WHAT, int MAXP>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_q28(const Affine<FpField<C>>* __restrict__ g1,
-                                                                 const Affine<Fp2Field<C>>* __restrict__ g2, int ppp, size_t n,
+                                                                 const Affine<Fp2Field<C>>* __restrict__ g2, MillerGroups mg, size_t n,
                                                                  const Fp12<C>* __restrict__ in, Fp12<C>* __restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 2;  // the four lanes of a quad share i: quad-uniform exit
@@ -383,12 +389,14 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_q28(const Affine<Fp
   if (WHAT == 1) {
     q28_load_gt<C>(f, in, i);
   } else {
+    const MillerGroupAt at(mg, i);  // this group's first pair and its number of pairs (pairing_products.h)
+    const int ppp = at.count;
     Fp28<C> px[MAXP], py[MAXP];
     E2 qx[MAXP], qy[MAXP];
     bool live[MAXP];
     for (int k = 0; k < ppp && k < MAXP; k++) {
-      const Affine<FpField<C>> P = g1[i * ppp + k];
-      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + i * ppp + k);
+      const Affine<FpField<C>> P = g1[at.first + k];
+      const Fp<C>* q = reinterpret_cast<const Fp<C>*>(g2 + at.first + k);
       const Fp<C> qxc = q[hi], qyc = q[2 + hi];
       uint32_t zq = (fp_is_zero<C>(qxc) & fp_is_zero<C>(qyc)) ? 1u : 0u;
       zq &= pair_xchg_u32(zq);  // Q at infinity: all four Fp components zero (both pairs hold the same Q)
@@ -459,6 +467,43 @@ int gt_launch(void (*quad)(P...), void (*pairs)(P...), size_t n, hipStream_t st,
   return 0;
 }
 
+// ---- the fold of long products (pairing_products.h): value v of a pass over n = K half values is
+// part[lo] * part[hi] of product k, written back to part[lo] -- or, by the pass that leaves one value per product, to out[k].
+// A pass writes slots j < half and reads, besides them, slots j + (cur - half) >= half: in place without a hazard.
+template <class C, bool QUAD>
+__global__ void __launch_bounds__(64) MLHIP_LP_OCC k_gt_fold(Fp12<C>* part, uint32_t g, uint32_t cur, uint32_t half, size_t n,
+                                                             Fp12<C>* out) {
+  typedef GtShape<C, QUAD> S;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t v = t / S::LANES;  // uniform over the lanes of one value
+  if (v >= n) return;
+  size_t k, lo, hi;
+  fold_operands(g, cur, half, v, k, lo, hi);
+  typename S::T a, b, r;
+  S::load(a, part, lo);
+  S::load(b, part, hi);
+  S::G::mul(r, a, b);
+  if (out)
+    S::store(out, k, r);
+  else
+    S::store(part, lo, r);
+}
+
+// d_out[k] = the product of the g values part[k g .. k g + g) for k < K (g >= 2); part is overwritten.  ceil(log2 g) launches:
+// ONE launch in which the lanes of product k multiply its g values in sequence was measured beside this and lost wherever g
+// is not small (g = 64: 3.65 against 2.43 ms at 64 pairs, 10.03 against 8.92 at 2^16)
+template <class C>
+int gt_fold_device(void* d_part, uint32_t g, size_t K, void* d_out, hipStream_t st) {
+  Fp12<C>* part = (Fp12<C>*)d_part;
+  FoldPass f;
+  for (int p = 0; fold_pass(g, p, f); p++) {
+    const int rc = gt_launch<C>(k_gt_fold<C, true>, k_gt_fold<C, false>, K * f.half, st, part, g, f.cur, f.half, K * f.half,
+                                f.last ? (Fp12<C>*)d_out : (Fp12<C>*)nullptr);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 // carry-free lane pairs on every curve (BLS12-377's u^2 = -5: fp2_lanes28.h carry-propagates every product operand first;
 // BN254: 10 limbs, xi = 9 + u) unless MLHIP_PAIRING_SAT=1 (read per batch so a test can switch paths)
 template <class C>
@@ -471,8 +516,11 @@ bool lp28_enabled() {
 // kernels above stay as the reference shape (MLHIP_PAIRING_ONE_LANE=1 selects them; the tests run both).
 template <class C>
 int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out,
-                   hipStream_t st) {
+                   hipStream_t st, const MillerGroups* groups = nullptr) {
   if (n == 0) return 0;
+  // groups: the n Miller loops are the groups of longer products (what = 0, ppp = the pairs of a full group, 2 or 4;
+  // pairing_products.h); without it, loop i takes the ppp pairs from i ppp
+  const MillerGroups mg = groups ? *groups : miller_groups_plain(ppp), one = miller_groups_plain(1);
   typedef Affine<FpField<C>> A1;
   typedef Affine<Fp2Field<C>> A2;
   const bool one_lane = mlhip_alt_switch("MLHIP_PAIRING_ONE_LANE");  // read per batch so a test can switch paths (test build only)
@@ -485,7 +533,7 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
       unsigned blocks = (unsigned)((n + 63) / 64);
       switch (what) {
         case 0:
-          k_miller<C><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, (int)ppp, n, (Fp12<C>*)d_out);
+          k_miller<C><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, mg, n, (Fp12<C>*)d_out);
           break;
         case 1:
           k_final_exp<C><<<dim3(blocks), dim3(64), 0, st>>>((const Fp12<C>*)d_in, n, (Fp12<C>*)d_out);
@@ -504,13 +552,13 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
       if (quads) {
         const unsigned qblocks = (unsigned)((4 * n + 63) / 64);
         if (what == 0 && ppp == 1)
-          k_pairing_q28<C, 0, 1><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr, (Fp12<C>*)d_out);
+          k_pairing_q28<C, 0, 1><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr, (Fp12<C>*)d_out);
         else if (what == 0)
-          k_pairing_q28<C, 0, 4><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, (int)ppp, n, nullptr, (Fp12<C>*)d_out);
+          k_pairing_q28<C, 0, 4><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, mg, n, nullptr, (Fp12<C>*)d_out);
         else if (what == 1)
-          k_pairing_q28<C, 1, 1><<<dim3(qblocks), dim3(64), 0, st>>>(nullptr, nullptr, 1, n, (const Fp12<C>*)d_in, (Fp12<C>*)d_out);
+          k_pairing_q28<C, 1, 1><<<dim3(qblocks), dim3(64), 0, st>>>(nullptr, nullptr, one, n, (const Fp12<C>*)d_in, (Fp12<C>*)d_out);
         else
-          k_pairing_q28<C, 2, 1><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr, (Fp12<C>*)d_out);
+          k_pairing_q28<C, 2, 1><<<dim3(qblocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr, (Fp12<C>*)d_out);
         HIPCHK(hipGetLastError());
         return 0;
       }
@@ -519,18 +567,18 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
       switch (what) {
         case 0:
           if (ppp == 1)
-            k_pairing_lp28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr,
+            k_pairing_lp28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr,
                                                                       (Fp12<C>*)d_out);
           else
-            k_pairing_lp28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, (int)ppp, n,
+            k_pairing_lp28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, mg, n,
                                                                       nullptr, (Fp12<C>*)d_out);
           break;
         case 1:
-          k_pairing_lp28<C, 1, 1><<<dim3(blocks), dim3(64), 0, st>>>(nullptr, nullptr, 1, n, (const Fp12<C>*)d_in,
+          k_pairing_lp28<C, 1, 1><<<dim3(blocks), dim3(64), 0, st>>>(nullptr, nullptr, one, n, (const Fp12<C>*)d_in,
                                                                     (Fp12<C>*)d_out);
           break;
         default:
-          k_pairing_lp28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr,
+          k_pairing_lp28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr,
                                                                     (Fp12<C>*)d_out);
           break;
       }
@@ -542,21 +590,21 @@ int pairing_device(int what, const void* d_g1, const void* d_g2, size_t ppp, siz
       case 0:
         if constexpr (C::IS_BN || kBuildAlt) {
           if (ppp == 1)
-            k_pairing_lp<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr,
+            k_pairing_lp<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr,
                                                                     (Fp12<C>*)d_out);
           else
-            k_pairing_lp<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, (int)ppp, n, nullptr,
+            k_pairing_lp<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, mg, n, nullptr,
                                                                     (Fp12<C>*)d_out);
         }
         break;
       case 1:
         if constexpr (kBuildAlt)
-          k_pairing_lp<C, 1, 1><<<dim3(blocks), dim3(64), 0, st>>>(nullptr, nullptr, 1, n, (const Fp12<C>*)d_in,
+          k_pairing_lp<C, 1, 1><<<dim3(blocks), dim3(64), 0, st>>>(nullptr, nullptr, one, n, (const Fp12<C>*)d_in,
                                                                (Fp12<C>*)d_out);
         break;
       default:
         if constexpr (kBuildAlt)
-          k_pairing_lp<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, 1, n, nullptr,
+          k_pairing_lp<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>((const A1*)d_g1, (const A2*)d_g2, one, n, nullptr,
                                                                (Fp12<C>*)d_out);
         break;
     }

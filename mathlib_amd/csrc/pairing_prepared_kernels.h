@@ -14,7 +14,10 @@ struct PreparedView {
   const int32_t* t28;          // [m][NL][r0 r1 r2][c0 c1][N28]
   const Line<C, Fp2<C>>* t32;  // [m][NL]; test build only (nullptr in the product)
   const uint32_t* q_inf;       // [m]: 1 = this Q is the point at infinity
-  uint32_t q[4];
+  uint32_t q[4];               // the Q of each slot of a product of at most 4 pairs ...
+  const uint32_t* d_index;     // ... or, for longer products, the Q of every slot: a device copy of q_index (else nullptr)
+  // the Q of pair k of the group whose first pair sits in slot `slot` of its product (pairing_products.h)
+  __device__ __forceinline__ uint32_t q_of(uint32_t slot, int k) const { return d_index ? d_index[slot + k] : q[k]; }
 };
 
 // ---- build: one Q per lane, boundary-form arithmetic (runs once per handle) -------------------------------------------
@@ -52,20 +55,22 @@ __global__ void __launch_bounds__(256) k_g2_prepared_expand(const Affine<Fp2Fiel
 // WHAT: 0 = Miller loop, 2 = Miller loop + final exponentiation
 template <class C, int WHAT>
 __global__ void __launch_bounds__(64) k_miller_prepared(PreparedView<C> pv, const Affine<FpField<C>>* __restrict__ g1,
-                                                        int ppp, size_t n, Fp12<C>* __restrict__ out) {
+                                                        MillerGroups mg, size_t n, Fp12<C>* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const MillerGroupAt at(mg, i);
+  const int ppp = at.count;
   Fp<C> px[4], py[4];
   bool live[4];
-  for (int k = 0; k < ppp && k < 4; k++) {
-    const Affine<FpField<C>> P = g1[i * ppp + k];
-    px[k] = P.x;
-    py[k] = P.y;
-    live[k] = !(affine_is_inf<FpField<C>>(P) | (pv.q_inf[pv.q[k]] != 0));
-  }
   PreparedLines32<C> ls;
   ls.tab = pv.t32;
-  for (int k = 0; k < 4; k++) ls.q[k] = pv.q[k];
+  for (int k = 0; k < 4; k++) ls.q[k] = k < ppp ? pv.q_of(at.slot, k) : 0u;
+  for (int k = 0; k < ppp && k < 4; k++) {
+    const Affine<FpField<C>> P = g1[at.first + k];
+    px[k] = P.x;
+    py[k] = P.y;
+    live[k] = !(affine_is_inf<FpField<C>>(P) | (pv.q_inf[ls.q[k]] != 0));
+  }
   Fp12<C> f, r;
   miller_loop_prepared_core<C, 4, Fp2<C>, Fp<C>>(f, px, py, live, ppp, ls);
   if (WHAT == 0) {
@@ -101,12 +106,14 @@ struct PreparedLines28 {
   }
 };
 
+// (q: the Q of each pair of this group, PreparedLines28::q)
 template <class C, int MAXP>
 __device__ __forceinline__ void prepared_load_g1(Fp28<C>* px, Fp28<C>* py, bool* live, const PreparedView<C>& pv,
-                                                 const Affine<FpField<C>>* __restrict__ g1, size_t i, int ppp) {
+                                                 const Affine<FpField<C>>* __restrict__ g1, size_t first, int ppp,
+                                                 const uint32_t* q) {
   for (int k = 0; k < ppp && k < MAXP; k++) {
-    const Affine<FpField<C>> P = g1[i * ppp + k];
-    live[k] = !(affine_is_inf<FpField<C>>(P) | (pv.q_inf[pv.q[k]] != 0));
+    const Affine<FpField<C>> P = g1[first + k];
+    live[k] = !(affine_is_inf<FpField<C>>(P) | (pv.q_inf[q[k]] != 0));
     fp28_from_fp<C>(px[k], P.x);
     fp28_from_fp<C>(py[k], P.y);
   }
@@ -116,19 +123,21 @@ __device__ __forceinline__ void prepared_load_g1(Fp28<C>* px, Fp28<C>* py, bool*
 // arrays are then registers), 4 otherwise -- the conventions of k_pairing_lp28
 template <class C, int WHAT, int MAXP>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_prep_lp28(PreparedView<C> pv,
-                                                                       const Affine<FpField<C>>* __restrict__ g1, int ppp,
-                                                                       size_t n, Fp12<C>* __restrict__ out) {
+                                                                       const Affine<FpField<C>>* __restrict__ g1,
+                                                                       MillerGroups mg, size_t n, Fp12<C>* __restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 1;  // both lanes of a pair share i, so this exit is pair-uniform
   if (i >= n) return;
   typedef Fp2L28<C> E2;
+  const MillerGroupAt at(mg, i);
+  const int ppp = at.count;
   Fp28<C> px[MAXP], py[MAXP];
   bool live[MAXP];
-  prepared_load_g1<C, MAXP>(px, py, live, pv, g1, i, ppp);
   PreparedLines28<C> ls;
   ls.tab = pv.t28;
-  for (int k = 0; k < 4; k++) ls.q[k] = pv.q[k];
+  for (int k = 0; k < 4; k++) ls.q[k] = k < ppp ? pv.q_of(at.slot, k) : 0u;
   ls.hi = lane_is_hi() ? 1 : 0;
+  prepared_load_g1<C, MAXP>(px, py, live, pv, g1, at.first, ppp, ls.q);
   Fp12<C, E2> f, r;
   miller_loop_prepared_core<C, MAXP, E2, Fp28<C>>(f, px, py, live, ppp, ls);
   if (WHAT == 0) {
@@ -142,19 +151,21 @@ __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_prep_lp28(PreparedV
 // four lanes per product (pairing_quad.h): the shorter dependent chain for batches that leave the chip under-filled
 template <class C, int WHAT, int MAXP>
 __global__ void __launch_bounds__(64) MLHIP_LP_OCC k_pairing_prep_q28(PreparedView<C> pv,
-                                                                      const Affine<FpField<C>>* __restrict__ g1, int ppp,
-                                                                      size_t n, Fp12<C>* __restrict__ out) {
+                                                                      const Affine<FpField<C>>* __restrict__ g1,
+                                                                      MillerGroups mg, size_t n, Fp12<C>* __restrict__ out) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t i = t >> 2;  // the four lanes of a quad share i: quad-uniform exit
   if (i >= n) return;
   typedef Fp2L28<C> E2;
+  const MillerGroupAt at(mg, i);
+  const int ppp = at.count;
   Fp28<C> px[MAXP], py[MAXP];
   bool live[MAXP];
-  prepared_load_g1<C, MAXP>(px, py, live, pv, g1, i, ppp);
   PreparedLines28<C> ls;
   ls.tab = pv.t28;
-  for (int k = 0; k < 4; k++) ls.q[k] = pv.q[k];
+  for (int k = 0; k < 4; k++) ls.q[k] = k < ppp ? pv.q_of(at.slot, k) : 0u;
   ls.hi = lane_is_hi() ? 1 : 0;
+  prepared_load_g1<C, MAXP>(px, py, live, pv, g1, at.first, ppp, ls.q);
   Fp12Q<C, E2> f, r;
   miller_loop_prepared_q<C, MAXP, E2, Fp28<C>>(f, px, py, live, ppp, ls);
   if (WHAT != 0) {
@@ -200,20 +211,26 @@ PreparedGeneralRange prepared_general_range(int what, size_t ppp) {
 
 template <class C, class General>
 int g2_prepared_run(const mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
-                    size_t n, void* d_out, hipStream_t st, General general) {
+                    size_t n, void* d_out, hipStream_t st, General general, const MillerGroups* groups = nullptr,
+                    const uint32_t* d_index = nullptr) {
   if (n == 0) return 0;
+  // groups: the n Miller loops are the groups of longer products (pairing_products.h; what = 0, ppp = the pairs of a full
+  // group, q_index unused: slot s of every product pairs with Q[d_index[s]], a device array); without it, loop i takes
+  // the ppp pairs from i ppp against Q[q_index[0 .. ppp)]
+  const MillerGroups mg = groups ? *groups : miller_groups_plain(ppp);
   typedef Affine<FpField<C>> A1;
   typedef Affine<Fp2Field<C>> A2;
   PreparedView<C> pv;
   pv.t28 = t->d_t28;
   pv.t32 = (const Line<C, Fp2<C>>*)t->d_t32;
   pv.q_inf = t->d_inf;
-  for (size_t j = 0; j < 4; j++) pv.q[j] = j < ppp ? (q_index ? q_index[j] : (uint32_t)j) : 0u;
+  for (size_t j = 0; j < 4; j++) pv.q[j] = j < ppp && !groups ? (q_index ? q_index[j] : (uint32_t)j) : 0u;
+  pv.d_index = groups ? d_index : nullptr;
   Fp12<C>* out = (Fp12<C>*)d_out;
   const A1* g1 = (const A1*)d_g1;
   const char* ge = getenv("MLHIP_G2_PREPARED_GENERAL");
   const PreparedGeneralRange gr = prepared_general_range<C>(what, ppp);
-  if (ge ? ge[0] == '1' : (n >= gr.lo && n < gr.hi)) {
+  if (!groups && (ge ? ge[0] == '1' : (n >= gr.lo && n < gr.hi))) {
     // scratch of this call alone: the handle stays read-only, so concurrent callers need no lock.  hipMalloc / hipFree make
     // this path synchronous: the call returns when its work is done (include/mlhip.h says so)
     A2* d_q = nullptr;
@@ -241,9 +258,9 @@ int g2_prepared_run(const mlhip_g2_prepared_tables* t, int what, const void* d_g
     if constexpr (kBuildAlt) {
       const unsigned blocks = (unsigned)((n + 63) / 64);
       if (what == 0)
-        k_miller_prepared<C, 0><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+        k_miller_prepared<C, 0><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
       else
-        k_miller_prepared<C, 2><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+        k_miller_prepared<C, 2><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -251,23 +268,23 @@ int g2_prepared_run(const mlhip_g2_prepared_tables* t, int what, const void* d_g
   if (pairing_wants_quads<C>(what, n)) {
     const unsigned blocks = (unsigned)((4 * n + 63) / 64);
     if (what == 0 && ppp == 1)
-      k_pairing_prep_q28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, 1, n, out);
+      k_pairing_prep_q28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else if (what == 0)
-      k_pairing_prep_q28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+      k_pairing_prep_q28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else if (ppp == 1)
-      k_pairing_prep_q28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, 1, n, out);
+      k_pairing_prep_q28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else
-      k_pairing_prep_q28<C, 2, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+      k_pairing_prep_q28<C, 2, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
   } else {
     const unsigned blocks = (unsigned)((2 * n + 63) / 64);
     if (what == 0 && ppp == 1)
-      k_pairing_prep_lp28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, 1, n, out);
+      k_pairing_prep_lp28<C, 0, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else if (what == 0)
-      k_pairing_prep_lp28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+      k_pairing_prep_lp28<C, 0, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else if (ppp == 1)
-      k_pairing_prep_lp28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, 1, n, out);
+      k_pairing_prep_lp28<C, 2, 1><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
     else
-      k_pairing_prep_lp28<C, 2, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, (int)ppp, n, out);
+      k_pairing_prep_lp28<C, 2, 4><<<dim3(blocks), dim3(64), 0, st>>>(pv, g1, mg, n, out);
   }
   HIPCHK(hipGetLastError());
   return 0;

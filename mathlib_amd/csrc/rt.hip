@@ -435,7 +435,10 @@ int mlhip_sizes(int curve, size_t* fp, size_t* g1, size_t* g2, size_t* gt) {
 
 int mlhip_release_cache(void) {
   // the fixed-base tables of the batched scalar multiplication (one per curve and device; msm_scalar_mul.h)
-  for (const CurveOps& c : g_curves) c.release_cache();
+  for (const CurveOps& c : g_curves) {
+    c.release_cache();
+    (void)c.miller_products(nullptr, -1, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr);  // the long products' scratch
+  }
   release_plan_pool();
   // the idle leases (stream + scratch arena) of the other host-buffer entry points go too
   std::vector<Lease> leases;

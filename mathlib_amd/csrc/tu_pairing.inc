@@ -2,6 +2,7 @@
 // includes this.
 #include "pairing_kernels.h"
 #include "pairing_prepared_kernels.h"
+#include "pairing_products_run.h"
 using namespace mlhip;
 int MLHIP_TU_FN(pairing)(int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in,
                         void* d_out, hipStream_t st) {
@@ -34,5 +35,16 @@ int MLHIP_TU_FN(gt_inverse)(const void* d_in, size_t n, void* d_out, hipStream_t
 int MLHIP_TU_FN(g2_prepared)(mlhip_g2_prepared_tables* t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp,
                             size_t n, void* d_out, hipStream_t st) {
   if (what < 0) return g2_prepared_build<MLHIP_TU_CURVE>(t, st);
-  return g2_prepared_run<MLHIP_TU_CURVE>(t, what, d_g1, q_index, ppp, n, d_out, st, pairing_device<MLHIP_TU_CURVE>);
+  return g2_prepared_run<MLHIP_TU_CURVE>(t, what, d_g1, q_index, ppp, n, d_out, st,
+                                         [](int w, const void* a, const void* b, size_t p, size_t k, const void* in, void* o, hipStream_t s) {
+                                           return pairing_device<MLHIP_TU_CURVE>(w, a, b, p, k, in, o, s);
+                                         });
+}
+int MLHIP_TU_FN(miller_products)(const mlhip_g2_prepared_tables* t, int what, const void* d_g1, const void* d_g2,
+                                const uint32_t* q_index, size_t m, size_t n, void* d_out, hipStream_t st) {
+  if (what < 0) {
+    miller_products_release();
+    return 0;
+  }
+  return miller_products_run<MLHIP_TU_CURVE>(t, what, d_g1, d_g2, q_index, m, n, d_out, st);
 }

@@ -617,6 +617,32 @@ class Curve:
         check(load().mlhip_gt_exp_cyclo(self.id, b"".join(g.raw for g in gts), self._scalars(scalars), 1 if self.scalars_mont else 0, n, out))
         return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
 
+    def MillerLoopProducts(self, g2_lists: Sequence[Sequence[G2]], g1_lists: Sequence[Sequence[G1]]) -> List[Gt]:
+        """out[k] = prod_j Pairing(g2_lists[k][j], g1_lists[k][j]): K products of m pairs each, any m, in one device call
+        (include/mlhip.h: "products of any length", mlhip_miller_loop_products); not final-exponentiated, like Pairing.  Every
+        product has the same length: a shorter one is padded with pairs at infinity."""
+        if len(g2_lists) != len(g1_lists):
+            raise ValueError("MillerLoopProducts: %d G2 lists, %d G1 lists" % (len(g2_lists), len(g1_lists)))
+        n = len(g1_lists)
+        if n == 0:
+            return []
+        m = len(g1_lists[0])
+        if m == 0 or any(len(a) != m or len(b) != m for a, b in zip(g1_lists, g2_lists)):
+            raise ValueError("MillerLoopProducts: every product takes the same number (at least one) of G1 and of G2 points")
+        raw = _lib.miller_loop_products(self.id, b"".join(p.raw for l in g1_lists for p in l),
+                                        b"".join(q.raw for l in g2_lists for q in l), m, n)
+        return [Gt(raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
+
+    def PairingProducts(self, g2_lists: Sequence[Sequence[G2]], g1_lists: Sequence[Sequence[G1]]) -> List[Gt]:
+        """out[k] = FExp(prod_j Pairing(g2_lists[k][j], g1_lists[k][j])): FExp of MillerLoopProducts, through mlhip_final_exp"""
+        ml = self.MillerLoopProducts(g2_lists, g1_lists)
+        n = len(ml)
+        if n == 0:
+            return []
+        out = ctypes.create_string_buffer(self.gt_bytes * n)
+        check(load().mlhip_final_exp(self.id, b"".join(g.raw for g in ml), n, out))
+        return [Gt(out.raw[i * self.gt_bytes : (i + 1) * self.gt_bytes], self) for i in range(n)]
+
     def PairingProduct(self, g2s: Sequence[G2], g1s: Sequence[G1]) -> Gt:
         """FExp(prod_i Pairing(g2s[i], g1s[i])) with one shared final exponentiation (additive API)."""
         if len(g2s) != len(g1s):
@@ -726,11 +752,14 @@ class G2Prepared:
             raise IndexError("G2Prepared: more pairs per product than prepared points")
         if index is not None and any(i < 0 or i >= self.m for i in index):
             raise IndexError("G2Prepared: point index out of range")
-        raw = _lib.g2_prepared_run(self._lib, self._h, c.gt_bytes, fused, b"".join(p.raw for l in g1_lists for p in l), index, ppp, n)
+        # (more than four pairs per product: include/mlhip.h, "products of any length")
+        run = _lib.g2_prepared_products if ppp > 4 else _lib.g2_prepared_run
+        raw = run(self._lib, self._h, c.gt_bytes, fused, b"".join(p.raw for l in g1_lists for p in l), index, ppp, n)
         return [Gt(raw[i * c.gt_bytes : (i + 1) * c.gt_bytes], c) for i in range(n)]
 
     def MillerLoopBatch(self, g1_lists: Sequence[Sequence[G1]], index=None) -> List[Gt]:
-        """out[k] = prod_j MillerLoop(g1_lists[k][j], Q[index[j]]) (without index: Q[j]); compare after FExp, as Curve.Pairing"""
+        """out[k] = prod_j MillerLoop(g1_lists[k][j], Q[index[j]]) (without index: Q[j]), any number of pairs per product; compare
+        after FExp, as Curve.Pairing"""
         return self._run(False, g1_lists, index)
 
     def PairingBatch(self, g1_lists: Sequence[Sequence[G1]], index=None) -> List[Gt]:
