@@ -1,7 +1,7 @@
 // msm_ed.h -- G1 bucket accumulation in extended twisted Edwards coordinates (ed28.h) for plans whose caller vouches for
 // the prime-order subgroup (mlhip_msm_plan_assume_srs; curves with C::HAS_EDWARDS: BLS12-377).  Part of msm_kernels.h.
-// The kernels mirror k_points_to28 / k_accumulate28_seg / k_accumulate_big_seg (msm_accumulate.h): same entry lists, same
-// state buffer (an EdExt28 has the footprint of an XYZZ28).  The buckets STAY in extended Edwards coordinates: the quad-lane
+// EdForm28 is the bucket form; its kernels are the shared bodies of msm_accumulate.h on it: same entry lists, same state
+// buffer (an EdExt28 has the footprint of an XYZZ28).  The buckets STAY in extended Edwards coordinates: the quad-lane
 // reduction kernels run their Edwards instantiation on them (msm_reduce.h: k_chunks_q28<C, true>, ed_quad28_add) and
 // only the W x nsel window sums return to the Weierstrass curve, for the host tail.
 #pragma once
@@ -38,7 +38,51 @@ __global__ void __launch_bounds__(256) k_points_to_ed28(const Affine<FpField<C>>
   }
 }
 
-// one thread per bucket; state[g] is the bucket in extended coordinates, between segments and for the reduction
+// The Edwards bucket form (see "bucket forms", msm_accumulate.h): Niels rows, EdExt28 accumulators and state -- the identity
+// is a value, there is no infinity flag -- in the buffer the Weierstrass form keeps its XYZZ28 in.  The buckets never take
+// the boundary form; what it inherits from G1Form28 is the boundary form of the slice sums, which the combine reads.
+template <class C>
+struct EdForm28 : G1Form28<C> {
+  static_assert(sizeof(EdExt28<C>) == sizeof(XYZZ28<C>), "the two bucket forms share the state buffer");
+  static constexpr bool HAS_BOUNDARY = false;
+  typedef FpField<C> BF;
+  typedef EdNiels28<C> RowMem, Row;
+  typedef XYZZ28<C> State;
+  typedef XYZZ<BF> LaneB;
+  typedef EdExt28<C> Acc;
+  static __device__ __forceinline__ void load_row(Row& r, const RowMem* rows, uint32_t i, int) { r = rows[i]; }
+  MLHIP_HD static void set_identity(Acc& a) { ed28_set_identity<C>(a); }
+  MLHIP_HD static void madd(Acc& a, const Row& q, bool negate) { ed28_madd<C>(a, q, negate); }
+  static __device__ __forceinline__ void load_state(Acc& a, const State* state, size_t g, int) {
+    a = reinterpret_cast<const EdExt28<C>*>(state)[g];
+  }
+  static __device__ __forceinline__ void store_state(State* state, size_t g, const Acc& a, int) {
+    reinterpret_cast<EdExt28<C>*>(state)[g] = a;
+  }
+  MLHIP_HD static void to_boundary(LaneB& r, const Acc& a) {
+    XYZZ28<C> w;
+    bool inf;
+    ed28_to_xyzz28<C>(w, inf, a);
+    xyzz28_to<C>(r, w, inf);
+  }
+  // the combine adds the bucket's earlier state on the Weierstrass side and maps the total back to extended Edwards
+  // coordinates (two inversions; a handful of buckets per segment)
+  static __device__ __forceinline__ bool state_to_boundary(XYZZ<BF>& r, const State* state, size_t g) {
+    Acc e;
+    load_state(e, state, g, 0);
+    to_boundary(r, e);
+    return true;
+  }
+  static __device__ __forceinline__ void boundary_to_state(State* state, size_t g, const XYZZ<BF>& sum) {
+    Affine<BF> a;
+    xyzz_to_affine<BF>(a, sum);  // (0, 0) for the point at infinity: ed28_from_affine maps it to the identity
+    Acc e;
+    ed28_from_affine<C>(e, a);
+    store_state(state, g, e, 0);
+  }
+};
+
+// state[g] is the bucket in extended coordinates, between segments and for the reduction
 template <class C>
 __global__ void __launch_bounds__(256) k_accumulate_ed28_seg(const EdNiels28<C>* __restrict__ points,
                                                              const uint32_t* __restrict__ sorted,
@@ -47,145 +91,29 @@ __global__ void __launch_bounds__(256) k_accumulate_ed28_seg(const EdNiels28<C>*
                                                              const uint32_t* __restrict__ order, uint32_t big_threshold,
                                                              uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count,
                                                              XYZZ28<C>* __restrict__ state, int flags) {
-  static_assert(sizeof(EdExt28<C>) == sizeof(XYZZ28<C>), "the two bucket forms share the state buffer");
-  size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= n_buckets) return;
-  const size_t g = order[tid];
-  const uint32_t cnt = counts[g];
-  const bool first = (flags & MLHIP_SEG_FIRST) != 0;
-  if (cnt > big_threshold) {  // k_accumulate_big_seg_ed adds this segment's entries to the bucket's state
-    uint32_t pos = atomicAdd(big_count, 1u);
-    big_list[pos] = (uint32_t)g;
-    return;
-  }
-  if (cnt == 0 && !first) return;
-  EdExt28<C>* const st = reinterpret_cast<EdExt28<C>*>(state);
-  EdExt28<C> acc;
-  if (first)
-    ed28_set_identity<C>(acc);
-  else
-    acc = st[g];
-  const size_t begin = offsets[g], end = begin + cnt;
-  if (cnt != 0) {
-    uint32_t e = sorted[begin];
-    EdNiels28<C> p = points[e & 0x7fffffffu];
-    for (size_t k = begin; k < end; k++) {
-      uint32_t en = e;
-      EdNiels28<C> pn = p;
-      if (k + 1 < end) {  // prefetch the next index and point under this addition
-        en = sorted[k + 1];
-        pn = points[en & 0x7fffffffu];
-      }
-      ed28_madd<C>(acc, p, (e >> 31) != 0);
-      e = en;
-      p = pn;
-    }
-  }
-  st[g] = acc;
+  accumulate_seg_body<EdForm28<C>>(points, sorted, offsets, counts, n_buckets, order, big_threshold, big_list, big_count, state,
+                                   flags, nullptr);
 }
 
-// the long buckets of a segment: their slice sums come from the Weierstrass long-bucket kernels on the original points
-// (k_big_slices: boundary form); thread 0 adds the bucket's earlier state on the Weierstrass side and maps the total back
-// to extended Edwards coordinates (two inversions; a handful of buckets per segment)
+// (the slice sums come in the boundary form: from k_big_slices on the original points, or k_big_slices28 on the Niels rows)
 template <class C, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_accumulate_big_seg_ed(const uint32_t* __restrict__ big_list,
                                                                  const uint32_t* __restrict__ big_count,
                                                                  const uint32_t* __restrict__ prefix,
                                                                  const XYZZ<FpField<C>>* __restrict__ partials,
                                                                  XYZZ28<C>* __restrict__ state, int flags) {
-  typedef FpField<C> F;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(smem);
-  EdExt28<C>* const st = reinterpret_cast<EdExt28<C>*>(state);
-  const uint32_t nbig = *big_count;
-  const bool first = (flags & MLHIP_SEG_FIRST) != 0;
-  for (uint32_t bi = blockIdx.x; bi < nbig; bi += gridDim.x) {
-    const uint32_t g = big_list[bi];
-    XYZZ<F> sum;
-    big_bucket_total<F, BLOCK>(sum, sh, partials, prefix, bi);
-    if (threadIdx.x == 0) {
-      if (!first) {
-        const EdExt28<C> e = st[g];
-        XYZZ28<C> w;
-        bool inf;
-        ed28_to_xyzz28<C>(w, inf, e);
-        XYZZ<F> prev;
-        xyzz28_to<C>(prev, w, inf);
-        xyzz_add_ool<F>(sum, prev);
-      }
-      Affine<F> a;
-      xyzz_to_affine<F>(a, sum);  // (0, 0) for the point at infinity: ed28_from_affine maps it to the identity
-      EdExt28<C> e;
-      ed28_from_affine<C>(e, a);
-      st[g] = e;
-    }
-    __syncthreads();
-  }
+  accumulate_big_body<EdForm28<C>, BLOCK>(big_list, big_count, prefix, partials, state, flags, nullptr);
 }
 
-// ---- the slice sums of long buckets from the CARRY-FREE rows (round 4: a shifted-base table keeps no boundary-form rows) --
-// k_big_slices (msm_accumulate.h) with the per-thread loop of the accumulation kernels: Weierstrass rows (Affine28, xyzz28_madd)
-// or, ED, Niels triples (ed28_madd); the thread's sum is converted to the boundary form for the LDS tree, so the partial sums
-// have the format the combine kernels (k_accumulate_big_seg, k_accumulate_big_seg_ed) already read.
+// the slice sums of long G1 buckets from the carry-free rows: Weierstrass rows or, ED, Niels triples
 template <class C, int BLOCK, bool ED>
 __global__ void __launch_bounds__(BLOCK) k_big_slices28(const void* __restrict__ rows, const uint32_t* __restrict__ sorted,
                                                         const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
                                                         const uint32_t* __restrict__ big_list, const uint32_t* __restrict__ big_count,
                                                         const uint32_t* __restrict__ prefix,
                                                         XYZZ<FpField<C>>* __restrict__ partials) {
-  typedef FpField<C> F;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(smem);
-  __shared__ uint32_t s_bi;
-  const uint32_t nbig = *big_count;
-  if (nbig == 0) return;
-  const uint32_t total = prefix[nbig];
-  for (uint32_t sid = blockIdx.x; sid < total; sid += gridDim.x) {
-    if (threadIdx.x == 0) {  // the bucket this slice belongs to: last entry with prefix <= sid
-      uint32_t lo = 0, hi = nbig - 1;
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi + 1) >> 1;
-        if (prefix[mid] <= sid)
-          lo = mid;
-        else
-          hi = mid - 1;
-      }
-      s_bi = lo;
-    }
-    __syncthreads();
-    const uint32_t bi = s_bi;
-    const uint32_t g = big_list[bi];
-    const size_t first = offsets[g], last = first + counts[g];
-    const size_t begin = first + (size_t)(sid - prefix[bi]) * BIG_SLICE;
-    const size_t end = begin + BIG_SLICE < last ? begin + BIG_SLICE : last;
-    XYZZ28<C> w;
-    bool inf = true;
-    if constexpr (ED) {
-      if constexpr (C::HAS_EDWARDS) {
-        const EdNiels28<C>* pts = static_cast<const EdNiels28<C>*>(rows);
-        EdExt28<C> acc;
-        ed28_set_identity<C>(acc);
-        for (size_t k = begin + threadIdx.x; k < end; k += BLOCK) {
-          const uint32_t e = sorted[k];
-          const EdNiels28<C> q = pts[e & 0x7fffffffu];
-          ed28_madd<C>(acc, q, (e >> 31) != 0);
-        }
-        ed28_to_xyzz28<C>(w, inf, acc);
-      }
-    } else {
-      const Affine28<C>* pts = static_cast<const Affine28<C>*>(rows);
-      for (size_t k = begin + threadIdx.x; k < end; k += BLOCK) {
-        const uint32_t e = sorted[k];
-        const Affine28<C> q = pts[e & 0x7fffffffu];
-        xyzz28_madd<C>(w, inf, q, (e >> 31) != 0);
-      }
-    }
-    XYZZ<F> acc;
-    xyzz28_to<C>(acc, w, inf);
-    block_tree_sum_auto<F, BLOCK>(sh, acc);
-    if (threadIdx.x == 0) partials[sid] = sh[0];
-    __syncthreads();
-  }
+  typedef typename std::conditional<ED, EdForm28<C>, G1Form28<C>>::type Fm;
+  big_slices_body<Fm, BLOCK>(static_cast<const typename Fm::RowMem*>(rows), sorted, offsets, counts, big_list, big_count, prefix,
+                             partials);
 }
-
 }  // namespace mlhip

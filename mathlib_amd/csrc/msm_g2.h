@@ -1,5 +1,6 @@
-// msm_g2.h -- G2 over lane pairs: accumulation (boundary form and carry-free form), segmented variants, bucket
-// reduction.  Part of msm_kernels.h.
+// msm_g2.h -- G2 over lane pairs: the boundary-form accumulation and slices (second implementation; slices of plain plans),
+// the two carry-free bucket forms (G2Form28, G2KcForm28) with their kernels over the shared bodies of msm_accumulate.h, and
+// the bucket reduction.  Part of msm_kernels.h.
 #pragma once
 // (included by msm_kernels.h after its common headers and constants)
 
@@ -186,217 +187,213 @@ __global__ void __launch_bounds__(256) k_points_to28_g2(const Affine<Fp2Field<C>
   reinterpret_cast<Fp28<C>*>(out)[t] = v;
 }
 
+// a bucket's carry-free state: two XYZZ28L, one per lane; ZZ = 0 limbs in both for the point at infinity
 template <class C>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_accumulate28_lp(const AffineG2_28<C>* __restrict__ points,
-                                                         const uint32_t* __restrict__ sorted,
-                                                         const uint32_t* __restrict__ offsets,
-                                                         const uint32_t* __restrict__ counts, size_t n_buckets,
-                                                         const uint32_t* __restrict__ order, uint32_t big_threshold,
-                                                         uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count,
-                                                         XYZZ<Fp2Field<C>>* __restrict__ buckets) {
-  typedef PairDevice<C> B;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t pair = t >> 1;  // both lanes of a pair share the bucket: every branch below is pair-uniform
-  if (pair >= n_buckets) return;
-  const int hi = (int)(threadIdx.x & 1u);
-  const size_t g = order[pair];
-  const uint32_t cnt = counts[g];
-  if (cnt > big_threshold) {  // summed in slices by k_big_slices / k_accumulate_big (boundary form)
-    if (!hi) {
-      uint32_t pos = atomicAdd(big_count, 1u);
-      big_list[pos] = (uint32_t)g;
-    }
-    return;
-  }
-  XYZZ28L<Fp28<C>> acc;
-  bool inf = true;
-  const size_t begin = offsets[g], end = begin + cnt;
-  if (cnt != 0) {
-    uint32_t e = sorted[begin];
-    Affine28L<Fp28<C>> p, pn;
-    p.x = points[e & 0x7fffffffu].c[hi];
-    p.y = points[e & 0x7fffffffu].c[2 + hi];
-    for (size_t k = begin; k < end; k++) {
-      uint32_t en = e;
-      pn = p;
-      if (k + 1 < end) {  // prefetch the next index and point under this addition
-        en = sorted[k + 1];
-        pn.x = points[en & 0x7fffffffu].c[hi];
-        pn.y = points[en & 0x7fffffffu].c[2 + hi];
-      }
-      xyzz28_lp_madd<C, B>(acc, inf, p, (e >> 31) != 0);
-      e = en;
-      p = pn;
-    }
-  }
-  // back to the boundary form, one Fp2 component per lane
-  XYZZ<Fp2LField<C>> r;
+__device__ __forceinline__ bool lp28_load_state(XYZZ28L<Fp28<C>>& r, const XYZZ28L<Fp28<C>>* src, size_t idx, int hi) {
+  r = src[2 * idx + hi];
+  return lp28_all_zero<C, PairDevice<C>>(r.zz);  // infinity
+}
+template <class C>
+__device__ __forceinline__ void lp28_store_state(XYZZ28L<Fp28<C>>* dst, size_t idx, XYZZ28L<Fp28<C>> r, bool inf, int hi) {
   if (inf) {
-    xyzz_set_inf<Fp2LField<C>>(r);
-  } else {
-    fp28_to_fp<C>(r.x.v, acc.x);
-    fp28_to_fp<C>(r.y.v, acc.y);
-    fp28_to_fp<C>(r.zz.v, acc.zz);
-    fp28_to_fp<C>(r.zzz.v, acc.zzz);
+#pragma unroll
+    for (int i = 0; i < C::N28; i++) r.x.l[i] = r.y.l[i] = r.zz.l[i] = r.zzz.l[i] = 0;
   }
-  lp_store_xyzz<C>(buckets, g, r, hi);
+  dst[2 * idx + hi] = r;
 }
 
-// ---- segmented G2 accumulation (see k_accumulate28_seg): the state of bucket g is two XYZZ28L, one per lane ------
+// LDS tree over the BLOCK / 2 lane pairs of a workgroup, in the boundary form; the sum is left in sh[0]
+template <class C, int BLOCK>
+__device__ __forceinline__ void block_tree_sum_lp(XYZZ<Fp2Field<C>>* sh, const XYZZ<Fp2LField<C>>& mine, int hi) {
+  const uint32_t pid = threadIdx.x >> 1;
+  lp_store_xyzz<C>(sh, pid, mine, hi);
+  __syncthreads();
+  for (uint32_t s = BLOCK / 4; s > 0; s >>= 1) {
+    if (pid < s) {  // pair-uniform
+      XYZZ<Fp2LField<C>> a, b;
+      lp_load_xyzz<C>(a, sh, pid, hi);
+      lp_load_xyzz<C>(b, sh, pid + s, hi);
+      xyzz_add_lp_ool<C>(a, b);
+      lp_store_xyzz<C>(sh, pid, a, hi);
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the G2 bucket forms (see "bucket forms", msm_accumulate.h) ---------------------------------------------------------
+// G2Form28: the pair split by component (ec28_lp.h): each lane holds one Fp2 component of the point and of the accumulator,
+// every Fp2 product is one fused dual product.
+template <class C>
+struct G2Form28 {
+  static constexpr int LANES = 2;
+  static constexpr bool HAS_BOUNDARY = true;
+  typedef Fp2Field<C> BF;
+  typedef AffineG2_28<C> RowMem;
+  typedef Affine28L<Fp28<C>> Row;
+  typedef XYZZ28L<Fp28<C>> State;
+  typedef XYZZ<Fp2LField<C>> LaneB;
+  struct Acc {
+    XYZZ28L<Fp28<C>> p;
+    bool inf;
+  };
+  static __device__ __forceinline__ void load_row(Row& r, const RowMem* rows, uint32_t i, int hi) {
+    r.x = rows[i].c[hi];
+    r.y = rows[i].c[2 + hi];
+  }
+  MLHIP_HD static void set_identity(Acc& a) { a.inf = true; }
+  MLHIP_HD static void madd(Acc& a, const Row& q, bool negate) { xyzz28_lp_madd<C, PairDevice<C>>(a.p, a.inf, q, negate); }
+  static __device__ __forceinline__ void load_state(Acc& a, const State* state, size_t g, int hi) {
+    a.p = state[2 * g + hi];
+    const uint32_t z = fp28_all_zero<C>(a.p.zz) ? 1u : 0u;
+    a.inf = (z & pair_xchg_u32(z)) != 0;  // ZZ = 0 in Fp2: both components
+  }
+  static __device__ __forceinline__ void store_state(State* state, size_t g, const Acc& a, int hi) {
+    lp28_store_state<C>(state, g, a.p, a.inf, hi);
+  }
+  static __device__ __forceinline__ void to_boundary(LaneB& r, const Acc& a) {
+    if (a.inf) {
+      xyzz_set_inf<Fp2LField<C>>(r);
+    } else {
+      fp28_to_fp<C>(r.x.v, a.p.x);
+      fp28_to_fp<C>(r.y.v, a.p.y);
+      fp28_to_fp<C>(r.zz.v, a.p.zz);
+      fp28_to_fp<C>(r.zzz.v, a.p.zzz);
+    }
+  }
+  static __device__ __forceinline__ void load_lane(LaneB& r, const XYZZ<BF>* src, size_t i, int hi) {
+    lp_load_xyzz<C>(r, src, i, hi);
+  }
+  static __device__ __forceinline__ void store_lane(XYZZ<BF>* dst, size_t i, const LaneB& r, int hi) {
+    lp_store_xyzz<C>(dst, i, r, hi);
+  }
+  template <int BLOCK>
+  static __device__ __forceinline__ void block_sum(XYZZ<BF>* sh, const LaneB& mine, int hi) {
+    block_tree_sum_lp<C, BLOCK>(sh, mine, hi);
+  }
+  // whole buckets on one thread, for the combine: both lanes' halves
+  static __device__ __forceinline__ bool state_to_boundary(XYZZ<BF>& r, const State* state, size_t g) {
+    const State lo = state[2 * g], up = state[2 * g + 1];
+    if (fp28_all_zero<C>(lo.zz) && fp28_all_zero<C>(up.zz)) return false;
+    fp28_to_fp<C>(r.x.c0, lo.x);
+    fp28_to_fp<C>(r.x.c1, up.x);
+    fp28_to_fp<C>(r.y.c0, lo.y);
+    fp28_to_fp<C>(r.y.c1, up.y);
+    fp28_to_fp<C>(r.zz.c0, lo.zz);
+    fp28_to_fp<C>(r.zz.c1, up.zz);
+    fp28_to_fp<C>(r.zzz.c0, lo.zzz);
+    fp28_to_fp<C>(r.zzz.c1, up.zzz);
+    return true;
+  }
+  static __device__ __forceinline__ void boundary_to_state(State* state, size_t g, const XYZZ<BF>& sum) {
+    State lo, up;
+    if (xyzz_is_inf<BF>(sum)) {
+#pragma unroll
+      for (int i = 0; i < C::N28; i++) {
+        lo.x.l[i] = lo.y.l[i] = lo.zz.l[i] = lo.zzz.l[i] = 0;
+        up.x.l[i] = up.y.l[i] = up.zz.l[i] = up.zzz.l[i] = 0;
+      }
+    } else {
+      fp28_from_fp<C>(lo.x, sum.x.c0);
+      fp28_from_fp<C>(up.x, sum.x.c1);
+      fp28_from_fp<C>(lo.y, sum.y.c0);
+      fp28_from_fp<C>(up.y, sum.y.c1);
+      fp28_from_fp<C>(lo.zz, sum.zz.c0);
+      fp28_from_fp<C>(up.zz, sum.zz.c1);
+      fp28_from_fp<C>(lo.zzz, sum.zzz.c0);
+      fp28_from_fp<C>(up.zzz, sum.zzz.c1);
+    }
+    state[2 * g] = lo;
+    state[2 * g + 1] = up;
+  }
+};
+
+// G2KcForm28: the pair split by coordinate (ec28_kc.h): lane A (hi = 0) owns X and ZZ, lane B owns Y and ZZZ, every Fp2
+// product is a one-lane Karatsuba product.  Rows, state and buckets keep the layouts of G2Form28 -- a lane simply reads both
+// components of its two coordinates (state[2 g] holds the real parts {x, y, zz, zzz}, state[2 g + 1] the imaginary parts)
+// and the x or the y half of a point (56 + 56 contiguous bytes) -- so the state is bit-identical and the long-bucket kernels
+// of G2Form28 serve both.
+template <class C>
+struct G2KcForm28 : G2Form28<C> {
+  typedef Fp2Field<C> BF;
+  typedef AffineG2_28<C> RowMem;
+  typedef XYZZ28L<Fp28<C>> State;
+  typedef Fp2x28<C> Row;
+  struct Acc {
+    Fp2x28<C> u, z;  // A: X, ZZ   B: Y, ZZZ
+    bool inf;
+  };
+  struct LaneB {
+    Fp<C> u0, u1, z0, z1;
+  };
+  static __device__ __forceinline__ void load_row(Row& r, const RowMem* rows, uint32_t i, int hi) {
+    r.c0 = rows[i].c[2 * hi];
+    r.c1 = rows[i].c[2 * hi + 1];
+  }
+  MLHIP_HD static void set_identity(Acc& a) { a.inf = true; }
+  MLHIP_HD static void madd(Acc& a, const Row& q, bool negate) { xyzz28_kc_madd<C, KcDevice<C>>(a.u, a.z, a.inf, q, negate); }
+  static __device__ __forceinline__ void load_state(Acc& a, const State* state, size_t g, int hi) {
+    const Fp28<C>* st = reinterpret_cast<const Fp28<C>*>(state + 2 * g);
+    a.u.c0 = st[hi];
+    a.u.c1 = st[4 + hi];
+    a.z.c0 = st[2 + hi];
+    a.z.c1 = st[6 + hi];
+    const bool zf[1] = {fp28_all_zero<C>(a.z.c0) && fp28_all_zero<C>(a.z.c1)};
+    a.inf = KcDevice<C>::of_a(zf);  // ZZ = 0 in Fp2
+  }
+  static __device__ __forceinline__ void store_state(State* state, size_t g, Acc& a, int hi) {
+    Fp28<C>* st = reinterpret_cast<Fp28<C>*>(state + 2 * g);
+    if (a.inf) {
+      fp28_zero<C>(a.u.c0);
+      fp28_zero<C>(a.u.c1);
+      fp28_zero<C>(a.z.c0);
+      fp28_zero<C>(a.z.c1);
+    }
+    st[hi] = a.u.c0;
+    st[4 + hi] = a.u.c1;
+    st[2 + hi] = a.z.c0;
+    st[6 + hi] = a.z.c1;
+  }
+  static __device__ __forceinline__ void to_boundary(LaneB& r, const Acc& a) {
+    if (a.inf) {  // as xyzz_set_inf: X = Y = 1, ZZ = ZZZ = 0
+      fp_one<C>(r.u0);
+      fp_zero<C>(r.u1);
+      fp_zero<C>(r.z0);
+      fp_zero<C>(r.z1);
+    } else {
+      fp28_to_fp<C>(r.u0, a.u.c0);
+      fp28_to_fp<C>(r.u1, a.u.c1);
+      fp28_to_fp<C>(r.z0, a.z.c0);
+      fp28_to_fp<C>(r.z1, a.z.c1);
+    }
+  }
+  static __device__ __forceinline__ void store_lane(XYZZ<BF>* dst, size_t i, const LaneB& r, int hi) {
+    Fp<C>* q = reinterpret_cast<Fp<C>*>(dst + i);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
+    q[2 * hi] = r.u0;
+    q[2 * hi + 1] = r.u1;
+    q[4 + 2 * hi] = r.z0;
+    q[5 + 2 * hi] = r.z1;
+  }
+};
+
+// segmented G2 accumulation (carry-free form; curves with u^2 = -1 may take the coordinate split, test build only)
 template <class C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_accumulate28_lp_seg(
     const AffineG2_28<C>* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
     const uint32_t* __restrict__ counts, size_t n_buckets, const uint32_t* __restrict__ order, uint32_t big_threshold,
     uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count, XYZZ28L<Fp28<C>>* __restrict__ state, int flags,
     XYZZ<Fp2Field<C>>* __restrict__ buckets) {
-  typedef PairDevice<C> B;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t pair = t >> 1;  // both lanes of a pair share the bucket: every branch below is pair-uniform
-  if (pair >= n_buckets) return;
-  const int hi = (int)(threadIdx.x & 1u);
-  const size_t g = order[pair];
-  const uint32_t cnt = counts[g];
-  const bool first = (flags & MLHIP_SEG_FIRST) != 0, last = (flags & MLHIP_SEG_LAST) != 0;
-  if (cnt > big_threshold) {
-    if (!hi) {
-      uint32_t pos = atomicAdd(big_count, 1u);
-      big_list[pos] = (uint32_t)g;
-    }
-    return;
-  }
-  const bool to_boundary = last && !(flags & MLHIP_SEG_KEEP28);
-  if (cnt == 0 && !first && !to_boundary) return;
-  XYZZ28L<Fp28<C>> acc;
-  bool inf = true;
-  if (!first) {
-    acc = state[2 * g + hi];
-    const uint32_t z = fp28_all_zero<C>(acc.zz) ? 1u : 0u;
-    inf = (z & pair_xchg_u32(z)) != 0;  // ZZ = 0 in Fp2: both components
-  }
-  const size_t begin = offsets[g], end = begin + cnt;
-  if (cnt != 0) {
-    uint32_t e = sorted[begin];
-    Affine28L<Fp28<C>> p, pn;
-    p.x = points[e & 0x7fffffffu].c[hi];
-    p.y = points[e & 0x7fffffffu].c[2 + hi];
-    for (size_t k = begin; k < end; k++) {
-      uint32_t en = e;
-      pn = p;
-      if (k + 1 < end) {
-        en = sorted[k + 1];
-        pn.x = points[en & 0x7fffffffu].c[hi];
-        pn.y = points[en & 0x7fffffffu].c[2 + hi];
-      }
-      xyzz28_lp_madd<C, B>(acc, inf, p, (e >> 31) != 0);
-      e = en;
-      p = pn;
-    }
-  }
-  if (to_boundary) {
-    XYZZ<Fp2LField<C>> r;
-    if (inf) {
-      xyzz_set_inf<Fp2LField<C>>(r);
-    } else {
-      fp28_to_fp<C>(r.x.v, acc.x);
-      fp28_to_fp<C>(r.y.v, acc.y);
-      fp28_to_fp<C>(r.zz.v, acc.zz);
-      fp28_to_fp<C>(r.zzz.v, acc.zzz);
-    }
-    lp_store_xyzz<C>(buckets, g, r, hi);
-  } else {
-    if (inf) {
-#pragma unroll
-      for (int i = 0; i < C::N28; i++) acc.x.l[i] = acc.y.l[i] = acc.zz.l[i] = acc.zzz.l[i] = 0;
-    }
-    state[2 * g + hi] = acc;
-  }
+  accumulate_seg_body<G2Form28<C>>(points, sorted, offsets, counts, n_buckets, order, big_threshold, big_list, big_count, state,
+                                   flags, buckets);
 }
 
-// ---- the same segment kernel with the pair split by coordinate (ec28_kc.h): lane A owns X and ZZ, lane B owns Y and ZZZ,
-// every Fp2 product is a one-lane Karatsuba product.  State, points and buckets keep their layouts: a lane simply reads
-// both components of its two coordinates (state[2 g] holds the real parts {x, y, zz, zzz}, state[2 g + 1] the imaginary
-// parts) and the x or the y half of a point (56 + 56 contiguous bytes).  Bit-identical state to k_accumulate28_lp_seg.
 template <class C>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_accumulate28_kc_seg(
     const AffineG2_28<C>* __restrict__ points, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
     const uint32_t* __restrict__ counts, size_t n_buckets, const uint32_t* __restrict__ order, uint32_t big_threshold,
     uint32_t* __restrict__ big_list, uint32_t* __restrict__ big_count, XYZZ28L<Fp28<C>>* __restrict__ state, int flags,
     XYZZ<Fp2Field<C>>* __restrict__ buckets) {
-  typedef KcDevice<C> B;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t pair = t >> 1;  // both lanes of a pair share the bucket: every branch below is pair-uniform
-  if (pair >= n_buckets) return;
-  const int hi = (int)(threadIdx.x & 1u);  // 0: lane A (X, ZZ)   1: lane B (Y, ZZZ)
-  const size_t g = order[pair];
-  const uint32_t cnt = counts[g];
-  const bool first = (flags & MLHIP_SEG_FIRST) != 0, last = (flags & MLHIP_SEG_LAST) != 0;
-  if (cnt > big_threshold) {
-    if (!hi) {
-      uint32_t pos = atomicAdd(big_count, 1u);
-      big_list[pos] = (uint32_t)g;
-    }
-    return;
-  }
-  const bool to_boundary = last && !(flags & MLHIP_SEG_KEEP28);
-  if (cnt == 0 && !first && !to_boundary) return;
-  Fp2x28<C> u, z;  // A: X, ZZ   B: Y, ZZZ
-  bool inf = true;
-  Fp28<C>* const st = reinterpret_cast<Fp28<C>*>(state + 2 * g);  // {x, y, zz, zzz} real parts, then the imaginary parts
-  if (!first) {
-    u.c0 = st[hi];
-    u.c1 = st[4 + hi];
-    z.c0 = st[2 + hi];
-    z.c1 = st[6 + hi];
-    const bool zf[1] = {fp28_all_zero<C>(z.c0) && fp28_all_zero<C>(z.c1)};
-    inf = B::of_a(zf);  // ZZ = 0 in Fp2
-  }
-  const size_t begin = offsets[g], end = begin + cnt;
-  if (cnt != 0) {
-    uint32_t e = sorted[begin];
-    Fp2x28<C> p, pn;
-    p.c0 = points[e & 0x7fffffffu].c[2 * hi];
-    p.c1 = points[e & 0x7fffffffu].c[2 * hi + 1];
-    for (size_t k = begin; k < end; k++) {
-      uint32_t en = e;
-      pn = p;
-      if (k + 1 < end) {  // prefetch the next index and point under this addition
-        en = sorted[k + 1];
-        pn.c0 = points[en & 0x7fffffffu].c[2 * hi];
-        pn.c1 = points[en & 0x7fffffffu].c[2 * hi + 1];
-      }
-      xyzz28_kc_madd<C, B>(u, z, inf, p, (e >> 31) != 0);
-      e = en;
-      p = pn;
-    }
-  }
-  if (to_boundary) {
-    Fp<C>* const q = reinterpret_cast<Fp<C>*>(buckets + g);  // x.c0 x.c1 y.c0 y.c1 zz.c0 zz.c1 zzz.c0 zzz.c1
-    Fp<C> r0, r1, r2, r3;
-    if (inf) {  // as xyzz_set_inf: X = Y = 1, ZZ = ZZZ = 0
-      fp_one<C>(r0);
-      fp_zero<C>(r1);
-      fp_zero<C>(r2);
-      fp_zero<C>(r3);
-    } else {
-      fp28_to_fp<C>(r0, u.c0);
-      fp28_to_fp<C>(r1, u.c1);
-      fp28_to_fp<C>(r2, z.c0);
-      fp28_to_fp<C>(r3, z.c1);
-    }
-    q[2 * hi] = r0;
-    q[2 * hi + 1] = r1;
-    q[4 + 2 * hi] = r2;
-    q[5 + 2 * hi] = r3;
-  } else {
-    if (inf) {
-#pragma unroll
-      for (int i = 0; i < C::N28; i++) u.c0.l[i] = u.c1.l[i] = z.c0.l[i] = z.c1.l[i] = 0;
-    }
-    st[hi] = u.c0;
-    st[4 + hi] = u.c1;
-    st[2 + hi] = z.c0;
-    st[6 + hi] = z.c1;
-  }
+  accumulate_seg_body<G2KcForm28<C>>(points, sorted, offsets, counts, n_buckets, order, big_threshold, big_list, big_count,
+                                     state, flags, buckets);
 }
 
 template <class C, int BLOCK>
@@ -406,58 +403,20 @@ __global__ void __launch_bounds__(BLOCK) k_accumulate_big_seg_g2(const uint32_t*
                                                                  const XYZZ<Fp2Field<C>>* __restrict__ partials,
                                                                  XYZZ28L<Fp28<C>>* __restrict__ state, int flags,
                                                                  XYZZ<Fp2Field<C>>* __restrict__ buckets) {
-  typedef Fp2Field<C> F;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<F>* sh = reinterpret_cast<XYZZ<F>*>(smem);
-  const uint32_t nbig = *big_count;
-  const bool first = (flags & MLHIP_SEG_FIRST) != 0;
-  const bool last = (flags & MLHIP_SEG_LAST) != 0 && !(flags & MLHIP_SEG_KEEP28);
-  for (uint32_t bi = blockIdx.x; bi < nbig; bi += gridDim.x) {
-    const uint32_t g = big_list[bi];
-    XYZZ<F> sum;
-    big_bucket_total<F, BLOCK>(sum, sh, partials, prefix, bi);
-    if (threadIdx.x == 0) {
-      if (!first) {
-        const XYZZ28L<Fp28<C>> lo = state[2 * g], up = state[2 * g + 1];
-        if (!(fp28_all_zero<C>(lo.zz) && fp28_all_zero<C>(up.zz))) {
-          XYZZ<F> prev;
-          fp28_to_fp<C>(prev.x.c0, lo.x);
-          fp28_to_fp<C>(prev.x.c1, up.x);
-          fp28_to_fp<C>(prev.y.c0, lo.y);
-          fp28_to_fp<C>(prev.y.c1, up.y);
-          fp28_to_fp<C>(prev.zz.c0, lo.zz);
-          fp28_to_fp<C>(prev.zz.c1, up.zz);
-          fp28_to_fp<C>(prev.zzz.c0, lo.zzz);
-          fp28_to_fp<C>(prev.zzz.c1, up.zzz);
-          xyzz_add_ool<F>(sum, prev);
-        }
-      }
-      if (last) {
-        buckets[g] = sum;
-      } else {
-        XYZZ28L<Fp28<C>> lo, up;
-        if (xyzz_is_inf<F>(sum)) {
-#pragma unroll
-          for (int i = 0; i < C::N28; i++) {
-            lo.x.l[i] = lo.y.l[i] = lo.zz.l[i] = lo.zzz.l[i] = 0;
-            up.x.l[i] = up.y.l[i] = up.zz.l[i] = up.zzz.l[i] = 0;
-          }
-        } else {
-          fp28_from_fp<C>(lo.x, sum.x.c0);
-          fp28_from_fp<C>(up.x, sum.x.c1);
-          fp28_from_fp<C>(lo.y, sum.y.c0);
-          fp28_from_fp<C>(up.y, sum.y.c1);
-          fp28_from_fp<C>(lo.zz, sum.zz.c0);
-          fp28_from_fp<C>(up.zz, sum.zz.c1);
-          fp28_from_fp<C>(lo.zzz, sum.zzz.c0);
-          fp28_from_fp<C>(up.zzz, sum.zzz.c1);
-        }
-        state[2 * g] = lo;
-        state[2 * g + 1] = up;
-      }
-    }
-    __syncthreads();
-  }
+  accumulate_big_body<G2Form28<C>, BLOCK>(big_list, big_count, prefix, partials, state, flags, buckets);
+}
+
+// k_big_slices_lp from the carry-free rows of a shifted-base table: BLOCK / 2 lane pairs stride over the slice's entries
+template <class C, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_big_slices_lp28(const AffineG2_28<C>* __restrict__ points,
+                                                           const uint32_t* __restrict__ sorted,
+                                                           const uint32_t* __restrict__ offsets,
+                                                           const uint32_t* __restrict__ counts,
+                                                           const uint32_t* __restrict__ big_list,
+                                                           const uint32_t* __restrict__ big_count,
+                                                           const uint32_t* __restrict__ prefix,
+                                                           XYZZ<Fp2Field<C>>* __restrict__ partials) {
+  big_slices_body<G2Form28<C>, BLOCK>(points, sorted, offsets, counts, big_list, big_count, prefix, partials);
 }
 
 template <class C>
@@ -546,20 +505,6 @@ template <class C>
 __device__ __noinline__ void xyzz28_lp_add_ool(XYZZ28L<Fp28<C>>& acc, bool& inf, const XYZZ28L<Fp28<C>>& q, bool q_inf) {
   xyzz28_lp_add<C, PairDevice<C>>(acc, inf, q, q_inf);
 }
-template <class C>
-__device__ __forceinline__ bool lp28_load_state(XYZZ28L<Fp28<C>>& r, const XYZZ28L<Fp28<C>>* src, size_t idx, int hi) {
-  r = src[2 * idx + hi];
-  return lp28_all_zero<C, PairDevice<C>>(r.zz);  // infinity
-}
-template <class C>
-__device__ __forceinline__ void lp28_store_state(XYZZ28L<Fp28<C>>* dst, size_t idx, XYZZ28L<Fp28<C>> r, bool inf, int hi) {
-  if (inf) {
-#pragma unroll
-    for (int i = 0; i < C::N28; i++) r.x.l[i] = r.y.l[i] = r.zz.l[i] = r.zzz.l[i] = 0;
-  }
-  dst[2 * idx + hi] = r;
-}
-
 template <class C>
 __global__ void __launch_bounds__(256) k_chunks_lp28(const XYZZ28L<Fp28<C>>* __restrict__ buckets, size_t n_chunks, int l_eff,
                                                      XYZZ28L<Fp28<C>>* __restrict__ A, XYZZ28L<Fp28<C>>* __restrict__ W0) {
@@ -677,85 +622,6 @@ __global__ void __launch_bounds__(BLOCK) k_group_combine_lp(const XYZZ<Fp2Field<
     __syncthreads();
   }
   if (pid == 0) lp_store_xyzz<C>(out, (size_t)o, acc, hi);
-}
-
-// k_big_slices_lp from the carry-free rows of a shifted-base table (AffineG2_28; see k_big_slices28, msm_ed.h): the pair's
-// sum is accumulated with the lane-pair carry-free mixed addition and converted to the boundary form for the LDS tree.
-template <class C, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_big_slices_lp28(const AffineG2_28<C>* __restrict__ points,
-                                                           const uint32_t* __restrict__ sorted,
-                                                           const uint32_t* __restrict__ offsets,
-                                                           const uint32_t* __restrict__ counts,
-                                                           const uint32_t* __restrict__ big_list,
-                                                           const uint32_t* __restrict__ big_count,
-                                                           const uint32_t* __restrict__ prefix,
-                                                           XYZZ<Fp2Field<C>>* __restrict__ partials) {
-  typedef Fp2LField<C> FL;
-  typedef PairDevice<C> B;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<Fp2Field<C>>* sh = reinterpret_cast<XYZZ<Fp2Field<C>>*>(smem);
-  __shared__ uint32_t s_bi;
-  constexpr uint32_t PAIRS = BLOCK / 2;
-  const uint32_t pid = threadIdx.x >> 1;
-  const int hi = lane_is_hi() ? 1 : 0;
-  const uint32_t nbig = *big_count;
-  if (nbig == 0) return;
-  const uint32_t total = prefix[nbig];
-  for (uint32_t sid = blockIdx.x; sid < total; sid += gridDim.x) {
-    if (threadIdx.x == 0) {
-      uint32_t lo = 0, up = nbig - 1;
-      while (lo < up) {
-        const uint32_t mid = (lo + up + 1) >> 1;
-        if (prefix[mid] <= sid)
-          lo = mid;
-        else
-          up = mid - 1;
-      }
-      s_bi = lo;
-    }
-    __syncthreads();
-    const uint32_t bi = s_bi;
-    const uint32_t g = big_list[bi];
-    const size_t first = offsets[g], last = first + counts[g];
-    const size_t begin = first + (size_t)(sid - prefix[bi]) * BIG_SLICE;
-    const size_t end = begin + BIG_SLICE < last ? begin + BIG_SLICE : last;
-    XYZZ28L<Fp28<C>> a28;
-    bool inf = true;
-    for (size_t k = begin + pid; k < end; k += PAIRS) {  // pair-uniform bounds
-      const uint32_t e = sorted[k];
-      Affine28L<Fp28<C>> q;
-      q.x = points[e & 0x7fffffffu].c[hi];
-      q.y = points[e & 0x7fffffffu].c[2 + hi];
-      xyzz28_lp_madd<C, B>(a28, inf, q, (e >> 31) != 0);
-    }
-    XYZZ<FL> acc, b;
-    if (inf) {
-      xyzz_set_inf<FL>(acc);
-    } else {
-      fp28_to_fp<C>(acc.x.v, a28.x);
-      fp28_to_fp<C>(acc.y.v, a28.y);
-      fp28_to_fp<C>(acc.zz.v, a28.zz);
-      fp28_to_fp<C>(acc.zzz.v, a28.zzz);
-    }
-    lp_store_xyzz<C>(sh, pid, acc, hi);
-    __syncthreads();
-    for (uint32_t s2 = PAIRS / 2; s2 > 0; s2 >>= 1) {
-      if (pid < s2) {  // pair-uniform
-        XYZZ<FL> a;
-        lp_load_xyzz<C>(a, sh, pid, hi);
-        lp_load_xyzz<C>(b, sh, pid + s2, hi);
-        xyzz_add_lp_ool<C>(a, b);
-        lp_store_xyzz<C>(sh, pid, a, hi);
-      }
-      __syncthreads();
-    }
-    if (pid == 0) {
-      XYZZ<FL> a;
-      lp_load_xyzz<C>(a, sh, 0, hi);
-      lp_store_xyzz<C>(partials, sid, a, hi);
-    }
-    __syncthreads();
-  }
 }
 
 }  // namespace mlhip

@@ -3,13 +3,23 @@
 //   k_coarse_hist / k_coarse_scatter / k_fine_sort   two-level LDS counting sort of the (window, bucket) keys
 //                 (k_digits / k_scan / k_scatter: the global-atomic variant for n > 2^24, MLHIP_LEGACY_SORT=1)
 //   k_order_*     buckets ordered by population, so that a wave's lanes run equally long loops
-//   k_points_to28 / k_accumulate28      G1: points into the carry-free form (fp28.h), one thread per bucket:
-//                 XYZZ += points[idx] (mixed additions, gathered reads); k_accumulate is the boundary-form variant
-//   k_points_to28_g2 / k_accumulate28_lp / k_accumulate_lp   G2: two lanes per bucket (one Fp2 component each)
-//   k_points_to_ed28 / k_accumulate_ed28_seg   G1 of a subgroup-trusted plan on a curve with a twisted Edwards model
-//                 (BLS12-377): 7-product unified mixed additions (ed28.h, msm_ed.h), buckets handed on as XYZZ28
-//   k_big_prefix / k_big_slices / k_accumulate_big  buckets longer than the threshold (skewed scalars): slices of 4096
-//                 entries, one workgroup per slice (LDS tree), then the slice sums of each bucket
+//   bucket accumulation: three steps, each written once over a bucket form (msm_accumulate.h: "bucket forms") --
+//                 accumulate_seg_body: one bucket per lane (G2: per lane pair), acc += points28[idx] (mixed additions,
+//                 gathered reads), on the state the segments before left; big_slices_body / accumulate_big_body: buckets
+//                 longer than the threshold (skewed scalars) in slices of 4096 entries, one workgroup per slice (LDS
+//                 tree), then the slice sums of each bucket into its state.  Forms and their kernels:
+//     G1Form28    k_points_to28 / k_accumulate28_seg / k_big_slices28<.., false> / k_accumulate_big_seg   carry-free
+//                 Weierstrass rows (fp28.h, ec28.h)
+//     EdForm28    k_points_to_ed28 / k_accumulate_ed28_seg / k_big_slices28<.., true> / k_accumulate_big_seg_ed   G1 of a
+//                 subgroup-trusted plan on a curve with a twisted Edwards model (BLS12-377): 7-product unified mixed
+//                 additions (ed28.h, msm_ed.h), buckets handed on in extended coordinates
+//     G2Form28    k_points_to28_g2 / k_accumulate28_lp_seg / k_big_slices_lp28 / k_accumulate_big_seg_g2   two lanes per
+//                 bucket, one Fp2 component each (ec28_lp.h); G2KcForm28 / k_accumulate28_kc_seg: one coordinate pair each
+//                 (ec28_kc.h; test build)
+//   k_accumulate / k_accumulate_lp / k_big_slices / k_big_slices_lp   the same on 32-bit Montgomery limbs, written out by
+//                 themselves: the second implementation the parity tests compare with (MLHIP_ACC32, test build); the
+//                 slices also serve plain plans, whose long buckets gather the caller's boundary-form points
+//   k_accumulate_q28   one bucket per quad of lanes for MSMs with few buckets (msm_reduce.h)
 //   k_chunks_q / k_masked_sums_q   G1 bucket reduction, one point per quad of lanes (ec_quad.h): per 16 consecutive
 //                 buckets sum and locally weighted sum, then per window the plain / bit-masked sums of the chunk sums
 //                 (k_chunks / k_masked_sums: one lane per point; *_lp: G2 lane pairs)
@@ -30,7 +40,7 @@
 // into the carry-free form), launch_accumulate (THE choice of bucket kernel, with the long-bucket step: launch_big_slices
 // and the kernel that adds the slice sums), launch_reduce, finish_train (reduce, copy to h_out, `done`).  What one pass does
 // differently from a tile hangs on launch_accumulate's `one_pass` and is listed there and at plan_launch: it skips the
-// long-bucket step below big_bucket_threshold, may take the quad kernel, reaches the test build's boundary-form kernels,
+// long-bucket step below big_bucket_threshold, may take the quad kernel or the test build's MLHIP_ACC32 kernels,
 // uploads a host-buffer call's points itself, sets the conv_* cache after every conversion, and places ev[0..3] / the wait
 // for ev_join where the tiles place ev_tile / the waits for ev_seg.
 // Replaces gnark-crypto's MultiExp behind MultiScalarMul (reference

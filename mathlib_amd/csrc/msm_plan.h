@@ -249,41 +249,31 @@ void host_tail(const mlhip_msm_plan* p, XYZZ<F>& total) {
 // there are none)
 // (`row0`: a folded plan keeps carry-free rows only -- the slices gather from d_points28 + row0, in the form the table holds;
 // `sv`: the plan whose entry lists (sorted / offsets / counts) describe this tile)
-template <class F, int BB>
+template <class F>
 void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t st, const mlhip_msm_plan* sv, size_t row0) {
   typedef typename F::Curve C;
+  constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;
+  constexpr int BLOCK = 256;  // one XYZZ<F> of LDS per lane (G2: per lane pair): 48 KB for both groups
   k_big_prefix<<<dim3(1), dim3(1024), 0, st>>>(sv->d_counts, p->d_biglist, p->d_bigcount, p->d_bigprefix);
-  if (p->fold) {
-    if constexpr (std::is_same<F, Fp2Field<C>>::value) {
-      k_big_slices_lp28<C, 256><<<dim3(1024), dim3(256), 128 * sizeof(XYZZ<F>), st>>>(
-          (const AffineG2_28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->d_bigcount,
-          p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
-    } else {
-      bool done_ed = false;
-      if constexpr (C::HAS_EDWARDS) {
-        if (p->conv_ed) {
-          k_big_slices28<C, BB, true><<<dim3(1024), dim3(BB), BB * sizeof(XYZZ<F>), st>>>(
-              (const EdNiels28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->d_bigcount,
-              p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
-          done_ed = true;
-        }
-      }
-      if (!done_ed)
-        k_big_slices28<C, BB, false><<<dim3(1024), dim3(BB), BB * sizeof(XYZZ<F>), st>>>(
-            (const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->d_bigcount,
-            p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
-    }
+  auto slices = [&](auto kernel, auto rows) {
+    kernel<<<dim3(1024), dim3(BLOCK), (BLOCK / (kG2 ? 2 : 1)) * sizeof(XYZZ<F>), st>>>(
+        rows, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->d_bigcount, p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
+  };
+  if (!p->fold) {  // a plain plan: the boundary-form rows the caller gave
+    if constexpr (kG2)
+      slices(k_big_slices_lp<C, BLOCK>, d_points);
+    else
+      slices(k_big_slices<F, BLOCK>, d_points);
     return;
   }
-  if constexpr (std::is_same<F, Fp2Field<C>>::value) {
-    // G2: 128 lane pairs per slice (48 KB of LDS)
-    k_big_slices_lp<C, 256><<<dim3(1024), dim3(256), 128 * sizeof(XYZZ<F>), st>>>(d_points, sv->d_sorted, sv->d_offsets,
-                                                                                  sv->d_counts, p->d_biglist, p->d_bigcount,
-                                                                                  p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
+  // a folded plan: the carry-free rows of its table, in the form the table holds
+  if constexpr (kG2) {
+    slices(k_big_slices_lp28<C, BLOCK>, (const AffineG2_28<C>*)p->d_points28 + row0);
   } else {
-    k_big_slices<F, BB><<<dim3(1024), dim3(BB), BB * sizeof(XYZZ<F>), st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts,
-                                                                          p->d_biglist, p->d_bigcount, p->d_bigprefix,
-                                                                          (XYZZ<F>*)p->d_bigpart);
+    if constexpr (C::HAS_EDWARDS) {
+      if (p->conv_ed) return slices(k_big_slices28<C, BLOCK, true>, (const void*)((const EdNiels28<C>*)p->d_points28 + row0));
+    }
+    slices(k_big_slices28<C, BLOCK, false>, (const void*)((const Affine28<C>*)p->d_points28 + row0));
   }
 }
 
@@ -491,7 +481,7 @@ void launch_convert(const mlhip_msm_plan* p, const Affine<F>* src, size_t len, s
 //   sv        the plan whose entry lists (sorted / offsets / counts / order) describe the segment: p itself, a sort-ahead
 //             helper record, or the G1 plan of a shared-scalar MSM
 //   row0      first carry-free row of the segment in d_points28 (a folded plan: fold_row of its tile)
-//   d_points  the segment's points in the boundary form, read by the boundary-form kernels and the slices of a plain plan
+//   d_points  the segment's points in the boundary form, read by the MLHIP_ACC32 kernels and the slices of a plain plan
 //             (a folded plan gathers from d_points28 + row0 only: a token)
 //   flags     MLHIP_SEG_FIRST / _LAST / _KEEP28 for the segment kernels
 //   ev_mid    recorded between the accumulation and the long-bucket step (null: no event)
@@ -511,83 +501,61 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
   // (2) too few buckets to fill the chip with one lane each: one bucket per quad of lanes (shorter dependent chains), ahead
   //     of the Edwards test.  The quad kernel keeps no state between segments, so tiles never use it.
   const bool quad = !kG2 && one_pass && p->d_points28 && p->reduce28 && nbuckets <= QUAD_ACC_MAX_BUCKETS && !getenv("MLHIP_NO_QUAD_ACC");
-  // (3, 4) the test build's boundary-form buckets (MLHIP_REDUCE32 / MLHIP_REDUCE_ONE_LANE / MLHIP_ACC32): one pass writes
-  //     d_buckets through the kernels without segment state; a tile of such a plan goes through the segment kernels
-  //     without MLHIP_SEG_KEEP28, which leave the boundary form on the last tile.  The product build instantiates none of
-  //     the boundary-form kernels: nothing is launched, and launch_reduce reports the missing bucket state.
-  const bool boundary = one_pass && !(p->reduce28 && p->d_points28);
+  // (3) every carry-free plan goes through the segment kernels of its bucket form, one pass ("first and last") or tile.  The
+  //     test build's boundary-form reductions (MLHIP_REDUCE32 / MLHIP_REDUCE_ONE_LANE) come without MLHIP_SEG_KEEP28: the
+  //     last segment leaves d_buckets, and one pass touches no state (such a plan has none before its first train).  Only
+  //     MLHIP_ACC32 (no carry-free rows; test build, one pass) takes kernels of its own: the second implementation on
+  //     32-bit limbs.  The product build instantiates none of those: nothing is launched, and launch_reduce reports the
+  //     missing bucket state.
   const dim3 grid((unsigned)(((kG2 ? 2 : 1) * nbuckets + p->acc_block - 1) / p->acc_block)), block(p->acc_block);
-  if constexpr (kG2) {
-    typedef XYZZ28L<Fp28<C>> S;
-    const AffineG2_28<C>* rows = (const AffineG2_28<C>*)p->d_points28 + row0;
-    if (boundary) {
-      if constexpr (kBuildAlt) {
-        if (p->d_points28)  // (MLHIP_REDUCE32=1: the buckets leave in the boundary form)
-          k_accumulate28_lp<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                                     big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
-        else  // (MLHIP_ACC32=1)
-          k_accumulate_lp<C><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                                   big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
-      }
-    } else {
-      bool kc = false;
-      if constexpr (C::BETA == -1 && kBuildAlt) {
-        if (g2_split_by_coordinate()) {
-          k_accumulate28_kc_seg<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                                         big_threshold, p->d_biglist, p->d_bigcount, (S*)p->d_state28, flags,
-                                                         (X*)p->d_buckets);
-          kc = true;
-        }
-      }
-      if (!kc)
-        k_accumulate28_lp_seg<C><<<grid, block, 0, st>>>(rows, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                                       big_threshold, p->d_biglist, p->d_bigcount, (S*)p->d_state28, flags,
-                                                       (X*)p->d_buckets);
+  auto seg = [&](auto kernel, auto rows, auto state, auto... buckets) {
+    kernel<<<grid, block, 0, st>>>(rows + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order, big_threshold,
+                                   p->d_biglist, p->d_bigcount, state, flags, buckets...);
+  };
+  if (!p->d_points28) {
+    if constexpr (kBuildAlt) {
+      if constexpr (kG2)
+        k_accumulate_lp<C><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                                 big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+      else
+        k_accumulate<F><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
+                                              big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
     }
+  } else if constexpr (kG2) {
+    typedef XYZZ28L<Fp28<C>> S;
+    bool kc = false;
+    if constexpr (C::BETA == -1 && kBuildAlt) {
+      if ((kc = g2_split_by_coordinate()))
+        seg(k_accumulate28_kc_seg<C>, (const AffineG2_28<C>*)p->d_points28, (S*)p->d_state28, (X*)p->d_buckets);
+    }
+    if (!kc) seg(k_accumulate28_lp_seg<C>, (const AffineG2_28<C>*)p->d_points28, (S*)p->d_state28, (X*)p->d_buckets);
   } else if (quad) {
     k_accumulate_q28<C><<<dim3((unsigned)((4 * nbuckets + 255) / 256)), dim3(256), 0, st>>>(
         (const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, big_threshold, p->d_biglist,
         p->d_bigcount, (XYZZ28<C>*)p->d_state28);
-  } else if (ed) {  // (implies reduce28: the last segment leaves XYZZ28 for the reduction)
-    if constexpr (C::HAS_EDWARDS)
-      k_accumulate_ed28_seg<C><<<grid, block, 0, st>>>((const EdNiels28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets,
-                                                     sv->d_counts, nbuckets, sv->d_order, big_threshold, p->d_biglist,
-                                                     p->d_bigcount, (XYZZ28<C>*)p->d_state28, flags);
-  } else if (!boundary) {
-    k_accumulate28_seg<C><<<grid, block, 0, st>>>((const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets,
-                                                sv->d_counts, nbuckets, sv->d_order, big_threshold, p->d_biglist, p->d_bigcount,
-                                                (XYZZ28<C>*)p->d_state28, flags, (X*)p->d_buckets);
-  } else if constexpr (kBuildAlt) {
-    if (p->d_points28)  // (MLHIP_REDUCE32=1 / MLHIP_REDUCE_ONE_LANE=1: the buckets leave in the boundary form)
-      k_accumulate28<C><<<grid, block, 0, st>>>((const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts,
-                                              nbuckets, sv->d_order, big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
-    else  // (MLHIP_ACC32=1)
-      k_accumulate<F><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                            big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+  } else if (ed) {  // (implies reduce28: the last segment leaves its extended coordinates for the reduction)
+    if constexpr (C::HAS_EDWARDS) seg(k_accumulate_ed28_seg<C>, (const EdNiels28<C>*)p->d_points28, (XYZZ28<C>*)p->d_state28);
+  } else {
+    seg(k_accumulate28_seg<C>, (const Affine28<C>*)p->d_points28, (XYZZ28<C>*)p->d_state28, (X*)p->d_buckets);
   }
   if (ev_mid) HIPCHK(hipEventRecord(ev_mid, st));
   if (!long_buckets) return 0;
-  // (5) the slices of a plain plan gather from d_points, those of a folded plan from d_points28 + row0
-  launch_big_slices<F, BB>(p, d_points, st, sv, row0);
-  const dim3 bgrid(256), bblock(BB);
-  const size_t blds = BB * sizeof(X);
-  if (boundary) {
-    if constexpr (kBuildAlt)
-      k_accumulate_big<F, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
-                                                          (X*)p->d_buckets);
-  } else if constexpr (kG2) {
-    k_accumulate_big_seg_g2<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
-                                                               (XYZZ28L<Fp28<C>>*)p->d_state28, flags, (X*)p->d_buckets);
+  // (4) the slices of a plain plan gather from d_points, those of a folded plan from d_points28 + row0
+  launch_big_slices<F>(p, d_points, st, sv, row0);
+  auto combine = [&](auto kernel, auto state, auto... buckets) {
+    kernel<<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, state,
+                                                        flags, buckets...);
+  };
+  if constexpr (kG2) {
+    combine(k_accumulate_big_seg_g2<C, BB>, (XYZZ28L<Fp28<C>>*)p->d_state28, (X*)p->d_buckets);
   } else {
     if constexpr (C::HAS_EDWARDS) {
       if (ed) {
-        k_accumulate_big_seg_ed<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix,
-                                                                   (const X*)p->d_bigpart, (XYZZ28<C>*)p->d_state28, flags);
+        combine(k_accumulate_big_seg_ed<C, BB>, (XYZZ28<C>*)p->d_state28);
         return 0;
       }
     }
-    k_accumulate_big_seg<C, BB><<<bgrid, bblock, blds, st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart,
-                                                            (XYZZ28<C>*)p->d_state28, flags, (X*)p->d_buckets);
+    combine(k_accumulate_big_seg<C, BB>, (XYZZ28<C>*)p->d_state28, (X*)p->d_buckets);
   }
   return 0;
 }
@@ -605,13 +573,13 @@ int finish_train(mlhip_msm_plan* p, bool prof, hipStream_t st) {
 
 // One pass over all n points: "one segment that is first and last" of the train below, with the differences listed at
 // launch_accumulate, and
-//   (6) a host-buffer call's points (upload_src) ride the auxiliary stream ahead of the conversion -- or, without the
+//   (5) a host-buffer call's points (upload_src) ride the auxiliary stream ahead of the conversion -- or, without the
 //       carry-free copy and its stream, a blocking copy first;
-//   (7) conv_src / conv_n / conv_ed are set after every conversion (the train clears conv_src at its start unless the copy
+//   (6) conv_src / conv_n / conv_ed are set after every conversion (the train clears conv_src at its start unless the copy
 //       is cached, and restores it at its end only for resident, static points);
-//   (8) events: memset of d_zero, then ev[0]; ev[2] once the conversion is queued; ev[3] between the accumulation and the
+//   (7) events: memset of d_zero, then ev[0]; ev[2] once the conversion is queued; ev[3] between the accumulation and the
 //       long buckets (tiles: ev[0] on the first tile ahead of the memset, ev_tile[s][0..2], ev[3] in stream_end);
-//   (9) the wait for ev_join sits immediately before the first kernel that reads the points (tiles: ev_seg / ev_seg_sc).
+//   (8) the wait for ev_join sits immediately before the first kernel that reads the points (tiles: ev_seg / ev_seg_sc).
 template <class C, class F>
 int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, int mont, size_t n, hipStream_t st) {
   typedef Affine<F> A;
@@ -662,8 +630,8 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
     }
     if (prof) HIPCHK(hipEventRecord(p->ev[2], st));
     if (p->d_points28) HIPCHK(hipStreamWaitEvent(st, p->ev_join, 0));
-    // (the Edwards kernels always leave XYZZ28 and read no MLHIP_SEG_KEEP28)
-    const int flags = MLHIP_SEG_FIRST | MLHIP_SEG_LAST | (use_ed ? 0 : MLHIP_SEG_KEEP28);
+    // (the Edwards form always leaves its state and reads no MLHIP_SEG_KEEP28)
+    const int flags = MLHIP_SEG_FIRST | MLHIP_SEG_LAST | (p->reduce28 ? MLHIP_SEG_KEEP28 : 0);
     if (int rc = launch_accumulate<C, F>(p, p, 0, (const A*)d_points, flags, use_ed, n, true, prof ? p->ev[3] : nullptr, st)) return rc;
     return finish_train<C, F>(p, prof, st);
   }

@@ -477,11 +477,40 @@ def test_g2_wire_codec_vs_oracle(lib, mlhip, curve):
 # alternate code paths selected by environment switches (read when a plan is created / a batch is launched):
 # every one must give the same bytes as the default path
 # ---------------------------------------------------------------------------------------------
+_LONG_BUCKET_INPUTS = {}
+
+
+def _long_bucket_inputs(cid, group, n):
+    """Inputs whose buckets go to the sliced long-bucket path (above max(256, 8 x the mean length) at c = 9 and c = 16), with
+    their cref results, made once per (curve, group): `third` -- every third scalar equal, one bucket of n / 3 entries per
+    window, one slice (G1 only); `equal` -- all scalars equal, n entries, three slices of 4096 for n = 9000 (the tree of
+    big_bucket_total).  Two of the points are the point at infinity, one of them inside the long bucket."""
+    import numpy as np
+    from oracle import cref
+
+    key = (cid, group, n)
+    if key not in _LONG_BUCKET_INPUTS:
+        pts = bytearray(cref.gen_points(cid, group, 16180 + group, 33988, n))
+        size = len(pts) // n
+        for i in (3, n - 2):
+            pts[i * size:(i + 1) * size] = bytes(size)
+        pts = bytes(pts)
+        one = _rand_scalars(1, 4242 + cid, 252)
+        third = _rand_scalars(n, 4243 + cid, 252)
+        third[::3] = one
+        sets = {"equal": np.tile(one, (n, 1))}
+        if group == 1:
+            sets["third"] = third
+        _LONG_BUCKET_INPUTS[key] = (pts, [(name, sc.tobytes(), cref.msm(cid, group, pts, sc, n, False, 0, 8))
+                                          for name, sc in sorted(sets.items())])
+    return _LONG_BUCKET_INPUTS[key]
+
+
 @pytest.mark.parametrize("curve", CURVES)
 @pytest.mark.parametrize("switch", ["MLHIP_LEGACY_SORT", "MLHIP_ACC32", "MLHIP_REDUCE_ONE_LANE", "MLHIP_REDUCE32", "MLHIP_NO_QUAD_ACC",
                                     "MLHIP_NO_PLAN_CACHE", "MLHIP_ACC_BLOCK=256", "MLHIP_RED_BLOCK=64", "MLHIP_CHUNK_LOG2=3",
                                     "MLHIP_STREAM_SEGMENTS=2", "MLHIP_STREAM_SEGMENTS=5", "MLHIP_REDUCE32+MLHIP_STREAM_SEGMENTS=3",
-                                    "MLHIP_SCATTER_STAGED=0", "MLHIP_HOST_THREADS=1"])
+                                    "MLHIP_REDUCE_ONE_LANE+MLHIP_STREAM_SEGMENTS=3", "MLHIP_SCATTER_STAGED=0", "MLHIP_HOST_THREADS=1"])
 def test_msm_alternate_paths(lib, mlhip, curve, switch, monkeypatch):
     g = load_golden(curve)
     cid = g["curve_id"]
@@ -501,13 +530,26 @@ def test_msm_alternate_paths(lib, mlhip, curve, switch, monkeypatch):
         out = ctypes.create_string_buffer(g1b)
         mlhip.check(lib.mlhip_msm_g1(cid, p, sc, 0, len(case["points"]), 5, out))
         assert out.raw == _h(case["expected"]), (curve, switch, case["name"])
+    if "MLHIP_REDUCE" in switch:
+        # long buckets under a boundary-form reduction: the slices, the combine and its exit into d_buckets, in one pass
+        # (through the segment kernels, "first and last", with no bucket state) and in three segments
+        if "MLHIP_STREAM_SEGMENTS" not in switch:
+            monkeypatch.setenv("MLHIP_STREAM_SEGMENTS", "0")
+        n = 9000
+        lpts, sets = _long_bucket_inputs(cid, 1, n)
+        for name, sc, lexp in sets:
+            for window_c in (9, 16):
+                out = ctypes.create_string_buffer(g1b)
+                mlhip.check(lib.mlhip_msm_g1(cid, lpts, sc, 0, n, window_c, out))
+                assert out.raw == lexp, (curve, switch, "long buckets", name, window_c)
 
 
 @pytest.mark.parametrize("curve", CURVES)
 @pytest.mark.parametrize("switches", [("MLHIP_ACC32",), ("MLHIP_ACC32", "MLHIP_STREAM_SEGMENTS=2"), ("MLHIP_LEGACY_SORT",),
                                       ("MLHIP_REDUCE32",), ("MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=3"),
                                       ("MLHIP_G2_KC",), ("MLHIP_G2_KC", "MLHIP_STREAM_SEGMENTS=3"),
-                                      ("MLHIP_G2_KC", "MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=2")])
+                                      ("MLHIP_G2_KC", "MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=2"),
+                                      ("MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=2")])
 def test_msm_g2_alternate_paths(lib, mlhip, curve, switches, monkeypatch):
     """G2 on the boundary-form accumulation (MLHIP_ACC32=1), alone and together with a forced segment count: with no
     carry-free copy of the points a BLS12-381 G2 plan cannot stream and must fall back to one pass, not fail.
@@ -535,6 +577,19 @@ def test_msm_g2_alternate_paths(lib, mlhip, curve, switches, monkeypatch):
         out = ctypes.create_string_buffer(g2b)
         mlhip.check(lib.mlhip_msm_g2(cid, pts, sc.tobytes(), 0, n, c, out))
         assert out.raw == exp, (curve, switches, c)
+    if switches in (("MLHIP_REDUCE32",), ("MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=2"), ("MLHIP_G2_KC",),
+                    ("MLHIP_G2_KC", "MLHIP_REDUCE32", "MLHIP_STREAM_SEGMENTS=2")):
+        # one long bucket per window (all scalars equal): the long-bucket combine and, under MLHIP_REDUCE32, its exit into
+        # the boundary form; with MLHIP_G2_KC the coordinate split beside it
+        if len(switches) == 1:
+            monkeypatch.setenv("MLHIP_STREAM_SEGMENTS", "0")
+        n = 4000
+        lpts, sets = _long_bucket_inputs(cid, 2, n)
+        for name, lsc, lexp in sets:
+            for c in (9, 16):
+                out = ctypes.create_string_buffer(g2b)
+                mlhip.check(lib.mlhip_msm_g2(cid, lpts, lsc, 0, n, c, out))
+                assert out.raw == lexp, (curve, switches, "long buckets", name, c)
 
 
 @pytest.mark.parametrize("curve", CURVES)
