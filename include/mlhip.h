@@ -151,13 +151,16 @@ MLHIP_API int mlhip_msm_plan_destroy(mlhip_msm_plan* plan);
 /* d_points / d_scalars are device pointers; stream is a hipStream_t (NULL = default stream).
  * out_affine is HOST memory; the call returns after the result is there.  When out_xyzz is non-NULL
  * the un-normalised partial sum (X,Y,ZZ,ZZZ) is written there too (multi-GPU combine): x = X/ZZ, y = Y/ZZZ is out_affine,
- * but the representation is not canonical -- two runs of one MSM can give different bytes for the same point. */
+ * but the representation is not canonical -- two runs of one MSM can give different bytes for the same point.
+ * (A device-result plan: see "device results" below -- both outputs are DEVICE pointers and the call returns once
+ * everything is queued, in order on `stream`.) */
 MLHIP_API int mlhip_msm_run(mlhip_msm_plan* plan, const void* d_points, const void* d_scalars, int scalars_mont, size_t n,
                   void* stream, void* out_affine, void* out_xyzz);
 /* The same in two halves, so consecutive MSMs pipeline: mlhip_msm_launch enqueues the kernels and the
  * D2H of the window sums on `stream` and returns; mlhip_msm_finish waits for them and runs the O(1) host
  * tail.  With two plans on two streams the sort of MSM k+1 overlaps the bucket accumulation of MSM k and
- * the host tail of MSM k overlaps GPU work (a Groth16 prover issues 4-5 MSMs back to back). */
+ * the host tail of MSM k overlaps GPU work (a Groth16 prover issues 4-5 MSMs back to back).
+ * (A device-result plan: see "device results" below -- mlhip_msm_finish queues the tail as a kernel and does not wait.) */
 MLHIP_API int mlhip_msm_launch(mlhip_msm_plan* plan, const void* d_points, const void* d_scalars, int scalars_mont, size_t n,
                      void* stream);
 MLHIP_API int mlhip_msm_finish(mlhip_msm_plan* plan, void* out_affine, void* out_xyzz);
@@ -178,7 +181,8 @@ MLHIP_API int mlhip_msm_launch_shared(mlhip_msm_plan* g1_plan, mlhip_msm_plan* g
  * windows W; [9] is 1 when the last launch summed its buckets in twisted Edwards coordinates (a subgroup-trusted
  * BLS12-377 G1 plan or table with the SRS promise, mlhip_msm_plan_assume_srs), else 0; [10] is 1 when the plan reads the
  * shifted-base tables of a mlhip_bases handle ([8] is then the number of digits a scalar is cut into).  Returns the number of
- * values written (at most `cap`, at most 11). */
+ * values written (at most `cap`, at most 11).
+ * (With cap >= 12 a twelfth value, with cap >= 13 a thirteenth: "short scalars" and "device results" below.) */
 MLHIP_API int mlhip_msm_plan_set_profiling(mlhip_msm_plan* plan, int on);
 /* The caller declares (on != 0) that this plan's points are a fixed SRS: (1) the point buffer at a given device address
  * holds the same points at every launch until the promise is taken back (the plan keeps its converted copy of them and
@@ -237,6 +241,52 @@ MLHIP_API int mlhip_msm_plan_timings(mlhip_msm_plan* plan, float* ms, int cap);
  * 0.125 / 0.25 / 0.5: the full-width plan already skips zero digits). */
 #define MLHIP_WINDOW_BITS(window_c, scalar_bits) \
   ((int)((window_c) < 0 || (window_c) > 255 ? 0xFF : (window_c)) | (int)(((scalar_bits) < 0 || (scalar_bits) > 256 ? 0x3FF : (scalar_bits)) << 8))
+
+/* ---- device results: plans and handles that leave their result in device memory --------------------------------------------
+ * For callers who hold device pointers and a stream and want to keep both: a batch verifier that hands sum r_k A_k and
+ * sum r_k B_k straight to mlhip_pairing_prepared_device, a prover with several MSMs in flight on one plan's stream, K results
+ * gathered in one device array and fetched with one copy.  The launch half of an MSM never waited for the host; with this
+ * flavour the tail (per-window sums, the Horner pass over the windows, the conversion to an affine point) is a kernel too
+ * (msm_tail.h), and nothing waits.
+ *
+ * How it is said.  The symbol table does not grow: a flag travels in window_c,
+ *     MLHIP_WINDOW_DEVICE_RESULT, OR-ed onto a plain window_c or onto MLHIP_WINDOW_BITS(window_c, scalar_bits),
+ * and is ACCEPTED by exactly three entry points -- mlhip_msm_plan_create, mlhip_bases_create, mlhip_bases_create_device --
+ * which take it off and read the rest of window_c as before (the handles still reject a scalar-width packing, as a width
+ * above 20; mlhip_bases_create with the flag never spreads over a device list).  mlhip_msm_g1, mlhip_msm_g2, mlhip_msm_g1g2,
+ * mlhip_msm_multi and mlhip_bases_create_multi -- results in host memory or over a device list -- REJECT it with
+ * MLHIP_EINVAL: no handle, nothing written.  mlhip_msm_plan_timings reports the flavour as a thirteenth value, [12], when
+ * cap >= 13 (1 for a device-result plan, else 0; the call then returns 13, and with cap <= 12 exactly what it returned
+ * before).  include/mlhip_device_result.h wraps this in inline functions for C, C++ and cgo:
+ * mlhip_msm_plan_create_device_result(curve_id, group, max_n, window_c, scalar_bits, &plan),
+ * mlhip_msm_plan_is_device_result(plan, &on), mlhip_msm_run_device(plan, d_points, d_scalars, scalars_mont, n, stream,
+ * d_out_affine, d_out_xyzz), mlhip_msm_finish_device(plan, d_out_affine, d_out_xyzz),
+ * mlhip_bases_create_device_result(curve_id, group, points, points_on_device, n, window_c, &bases) and
+ * mlhip_bases_msm_to_device(bases, d_scalars, scalars_mont, n, stream, d_out_affine).
+ *
+ * A device-result plan.  mlhip_msm_launch and mlhip_msm_launch_shared are what they are for every plan (in a shared launch
+ * each plan may be of either flavour and is finished in its own way).  mlhip_msm_finish(plan, d_out_affine, d_out_xyzz):
+ * both are DEVICE pointers on the plan's device, d_out_xyzz may be NULL; the call queues the tail kernel on the stream of the
+ * pending launch, queues the delivery of the result, records the plan's completion event and returns WITHOUT waiting.
+ * mlhip_msm_run is launch + finish: asynchronous and in order on `stream`, like every other _device form.  The kernel writes the
+ * affine point and the XYZZ value into a slot the plan owns; delivery is one asynchronous copy of that slot per requested
+ * output, on the same stream -- no kernel of the library dereferences the caller's output pointers.  n = 0 takes the same
+ * path: the all-zero affine point (and the XYZZ form of infinity) arrive in stream order.  The bytes are those of a
+ * host-result plan of the same geometry.
+ *
+ * Ordering.  Work on one stream is in order.  A launch on a plan whose previous work was queued on ANOTHER stream makes the
+ * new stream wait for that work on the device (never the host).  mlhip_msm_plan_destroy, mlhip_msm_plan_assume_srs and -- with
+ * profiling on -- mlhip_msm_plan_timings wait for the plan's unfinished work on the host; [5] is then the time of the tail
+ * kernel.  The caller's inputs may be rewritten, and the output read, by work queued behind the call on the same stream.
+ * One MSM at a time per plan, as always: launch, finish, launch.  Capture into a hipGraph is neither promised nor tested.
+ *
+ * A device-result handle (mlhip_bases_create / _create_device with the flag; mlhip_bases_plan shows [12] = 1).
+ * mlhip_bases_msm_device(bases, d_scalars, scalars_mont, n, stream, d_out_affine) is asynchronous and in order on `stream`
+ * with a DEVICE output; n = 0 writes the all-zero point in stream order; the handle's lock covers the enqueue only.
+ * mlhip_bases_msm (host scalars, host result) on such a handle is MLHIP_EINVAL -- use mlhip_bases_msm_device.
+ * mlhip_bases_msm_batch*, mlhip_bases_checked_subgroup and mlhip_bases_batch_tabled are what they are for every handle.
+ * curve_id is a MLHIP_CURVE_* value.  Measured: profiles/msm_device_result_ab.txt, DESIGN.md section 16. */
+#define MLHIP_WINDOW_DEVICE_RESULT (1 << 20) /* OR-ed onto a plain window_c or onto MLHIP_WINDOW_BITS(c, bits) */
 
 /* ---- products of any length: K products of m pairs each, for any m ------------------------------------------------------------
  * For callers with K independent products of MORE than four pairs: K aggregated signatures over m messages each, K
@@ -360,7 +410,8 @@ MLHIP_API int mlhip_bases_create_multi(int curve, int group, const int* devices,
                              int window_c, mlhip_bases** bases);
 MLHIP_API int mlhip_bases_msm(mlhip_bases* bases, const void* scalars, int scalars_mont, size_t n, void* out_affine);
 /* the same MSM with the n scalars already in device memory (a prover whose witness was computed on the device); `stream`
- * as in mlhip_msm_run; single-device handles only (MLHIP_EINVAL for a table spread over several devices) */
+ * as in mlhip_msm_run; single-device handles only (MLHIP_EINVAL for a table spread over several devices)
+ * (a device-result handle: see "device results" above -- out_affine is a DEVICE pointer, written in order on `stream`) */
 MLHIP_API int mlhip_bases_msm_device(mlhip_bases* bases, const void* d_scalars, int scalars_mont, size_t n, void* stream,
                            void* out_affine);
 /* the plan a single-device handle runs its MSMs on (NULL otherwise) -- for mlhip_msm_plan_set_profiling /

@@ -329,6 +329,60 @@ def msm_bits(curve: int, group: int, points, scalars, scalars_mont: bool, scalar
     return out.raw
 
 
+WINDOW_DEVICE_RESULT = 1 << 20
+"""MLHIP_WINDOW_DEVICE_RESULT of include/mlhip.h: OR-ed onto a plain window_c or onto window_bits(c, bits)"""
+
+
+def mlhip_msm_plan_create_device_result(lib, curve: int, group: int, max_n: int, window_c: int, scalar_bits: int, plan_ref) -> int:
+    """include/mlhip_device_result.h: a plan that leaves its result in device memory (the return code, as the C function)"""
+    return lib.mlhip_msm_plan_create(curve, group, max_n, window_bits(window_c, scalar_bits) | WINDOW_DEVICE_RESULT, plan_ref)
+
+
+def mlhip_msm_plan_is_device_result(lib, plan):
+    """include/mlhip_device_result.h: (return code, 1 for a device-result plan / 0 for a host-result one)"""
+    buf = (c_float * 13)()
+    k = lib.mlhip_msm_plan_timings(plan, buf, 13)
+    return (k, 0) if k < 0 else (EINVAL, 0) if k < 13 else (0, int(buf[12] != 0.0))
+
+
+def mlhip_msm_run_device(lib, plan, d_points, d_scalars, scalars_mont: int, n: int, stream, d_out_affine, d_out_xyzz) -> int:
+    """include/mlhip_device_result.h: mlhip_msm_run on a device-result plan, device outputs, in order on `stream`"""
+    rc, on = mlhip_msm_plan_is_device_result(lib, plan)
+    if rc or not on:
+        return rc or EINVAL
+    return lib.mlhip_msm_run(plan, d_points, d_scalars, scalars_mont, n, stream, d_out_affine, d_out_xyzz)
+
+
+def mlhip_msm_finish_device(lib, plan, d_out_affine, d_out_xyzz) -> int:
+    """include/mlhip_device_result.h: mlhip_msm_finish on a device-result plan: queues the tail and the delivery, no wait"""
+    rc, on = mlhip_msm_plan_is_device_result(lib, plan)
+    if rc or not on:
+        return rc or EINVAL
+    return lib.mlhip_msm_finish(plan, d_out_affine, d_out_xyzz)
+
+
+def mlhip_bases_create_device_result(lib, curve: int, group: int, points, points_on_device: int, n: int, window_c: int, bases_ref) -> int:
+    """include/mlhip_device_result.h: a device-result handle over host points or points in the current device's memory"""
+    wc = (0xFF if not 0 <= window_c <= 255 else window_c) | WINDOW_DEVICE_RESULT
+    fn = lib.mlhip_bases_create_device if points_on_device else lib.mlhip_bases_create
+    return fn(curve, group, points, n, wc, bases_ref)
+
+
+def mlhip_bases_msm_to_device(lib, bases, d_scalars, scalars_mont: int, n: int, stream, d_out_affine) -> int:
+    """include/mlhip_device_result.h: mlhip_bases_msm_device on a device-result handle, device output, in order on `stream`"""
+    rc, on = mlhip_msm_plan_is_device_result(lib, lib.mlhip_bases_plan(bases))
+    if rc or not on:
+        return rc or EINVAL
+    return lib.mlhip_bases_msm_device(bases, d_scalars, scalars_mont, n, stream, d_out_affine)
+
+
+def bases_create_device_result(curve: int, group: int, points, n: int, window_c: int = 0, points_on_device: bool = False):
+    """a device-result handle (c_void_p) on the library this process runs on; destroy it with mlhip_bases_destroy"""
+    h = c_void_p()
+    check(mlhip_bases_create_device_result(concrete(), curve, group, points, 1 if points_on_device else 0, n, window_c, byref(h)))
+    return h
+
+
 def batch_index(index_lists):
     """the base_index array of mlhip_bases_msm_batch* (one uint32 per pair, segment after segment), or None"""
     if index_lists is None:
@@ -468,11 +522,16 @@ def plan_timings(lib, handle):
 class MsmPlan:
     """Device workspace for repeated MSMs over device-resident points/scalars (include/mlhip.h)."""
 
-    def __init__(self, curve: int, group: int, max_n: int, window_c: int = 0, scalar_bits: int = 0):
-        """scalar_bits != 0: a plan for scalars below 2^scalar_bits (mlhip_msm_plan_create_bits; 0 = full width)"""
+    def __init__(self, curve: int, group: int, max_n: int, window_c: int = 0, scalar_bits: int = 0, device_result: bool = False):
+        """scalar_bits != 0: a plan for scalars below 2^scalar_bits (mlhip_msm_plan_create_bits; 0 = full width);
+        device_result: the plan leaves its result in device memory (mlhip_msm_plan_create_device_result: run_device /
+        finish_device instead of run / finish)"""
         self._h = c_void_p()
         lib = self._lib = concrete()
-        if scalar_bits:
+        self._device_result = bool(device_result)
+        if device_result:
+            check(mlhip_msm_plan_create_device_result(lib, curve, group, max_n, window_c, scalar_bits, byref(self._h)))
+        elif scalar_bits:
             check(mlhip_msm_plan_create_bits(lib, curve, group, max_n, window_c, scalar_bits, byref(self._h)))
         else:
             check(lib.mlhip_msm_plan_create(curve, group, max_n, window_c, byref(self._h)))
@@ -502,7 +561,28 @@ class MsmPlan:
         check(rc)
         return bits
 
+    def is_device_result(self) -> bool:
+        """does the plan leave its result in device memory?  (mlhip_msm_plan_is_device_result)"""
+        rc, on = mlhip_msm_plan_is_device_result(self._lib, self._h)
+        check(rc)
+        return bool(on)
+
+    def run_device(self, d_points: int, d_scalars: int, n: int, scalars_mont: bool, stream: int, d_out: int, d_out_xyzz: int = 0) -> None:
+        """mlhip_msm_run_device: the affine result at the device pointer d_out (the XYZZ value at d_out_xyzz unless 0), in
+        order on `stream`; returns once everything is queued"""
+        check(mlhip_msm_run_device(self._lib, self._h, c_void_p(d_points), c_void_p(d_scalars), 1 if scalars_mont else 0, n,
+                                   c_void_p(stream), c_void_p(d_out), c_void_p(d_out_xyzz) if d_out_xyzz else None))
+
+    def finish_device(self, d_out: int, d_out_xyzz: int = 0) -> None:
+        """mlhip_msm_finish_device after launch / launch_shared: queues the tail and the delivery, does not wait"""
+        check(mlhip_msm_finish_device(self._lib, self._h, c_void_p(d_out), c_void_p(d_out_xyzz) if d_out_xyzz else None))
+
+    def _host_result_only(self, what: str) -> None:
+        if self._device_result:
+            raise MlhipError(EINVAL, "MsmPlan.%s returns host bytes: a device-result plan has %s_device" % (what, what))
+
     def run(self, d_points: int, d_scalars: int, n: int, scalars_mont: bool, stream: int = 0, want_xyzz: bool = False):
+        self._host_result_only("run")
         out = ctypes.create_string_buffer(self.point_bytes)
         xyzz = ctypes.create_string_buffer(2 * self.point_bytes) if want_xyzz else None
         check(
@@ -522,6 +602,7 @@ class MsmPlan:
                                              1 if scalars_mont else 0, n, c_void_p(stream)))
 
     def finish(self, want_xyzz: bool = False):
+        self._host_result_only("finish")
         out = ctypes.create_string_buffer(self.point_bytes)
         xyzz = ctypes.create_string_buffer(2 * self.point_bytes) if want_xyzz else None
         check(self._lib.mlhip_msm_finish(self._h, out, xyzz))

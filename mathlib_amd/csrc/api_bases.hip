@@ -72,8 +72,13 @@ bool bases_want_tables(int group, size_t n, int window_c, int fr_bits, size_t pt
   return true;
 }
 
+// window_c may carry MLHIP_WINDOW_DEVICE_RESULT (mlhip_bases_create / _create_device pass it on; the shards of a device
+// list never have it): the handle's plan is then a device-result plan.  What is left is a plain width: a scalar-width
+// packing is a width above 20.
 int bases_create_single(int curve, int group, const void* points, size_t n, int window_c, size_t ptsz,
                                mlhip_bases** out, bool points_on_device = false) {
+  const bool device_result = window_c > 0 && (window_c & MLHIP_WINDOW_DEVICE_RESULT);
+  if (device_result) window_c &= ~MLHIP_WINDOW_DEVICE_RESULT;
   int rc = ensure_device();
   if (rc) return rc;
   mlhip_bases* b = new mlhip_bases();
@@ -87,10 +92,10 @@ int bases_create_single(int curve, int group, const void* points, size_t n, int 
     int fold_c = 0;
     size_t fold_tile = 0;
     if (bases_want_tables(group, n, window_c, ops->fr_bits, ptsz, &fold_c, &fold_tile)) {
-      if (plan_create_ex(curve, group, n, fold_c, fold_tile, &b->plan) != 0) b->plan = nullptr;  // (the plain plan below)
+      if (plan_create_ex(curve, group, n, fold_c, fold_tile, &b->plan, 0, device_result) != 0) b->plan = nullptr;  // (the plain plan below)
     }
   }
-  rc = b->plan ? 0 : plan_create_ex(curve, group, n, window_c, 0, &b->plan);
+  rc = b->plan ? 0 : plan_create_ex(curve, group, n, window_c, 0, &b->plan, 0, device_result);
   if (!rc && (hipMalloc(&b->d_pts, n * b->ptsz) != hipSuccess || hipMalloc(&b->d_sc, n * 32) != hipSuccess))
     rc = mlhip_rt::fail(MLHIP_ENOMEM, "hipMalloc of the bases failed");
   if (!rc && hipMemcpy(b->d_pts, points, n * b->ptsz, points_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice) != hipSuccess)
@@ -131,7 +136,7 @@ int bases_create_single(int curve, int group, const void* points, size_t n, int 
       const bool trusted = b->plan->trust_subgroup;
       mlhip_msm_plan_destroy(b->plan);
       b->plan = nullptr;
-      rc = plan_create_ex(curve, group, n, window_c, 0, &b->plan);
+      rc = plan_create_ex(curve, group, n, window_c, 0, &b->plan, 0, device_result);
       if (rc) {
         mlhip_bases_destroy(b);
         return rc;
@@ -216,8 +221,12 @@ int mlhip_bases_create(int curve, int group, const void* points, size_t n, int w
   const size_t ptsz = ops->point_size(group);
   if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
   if (!points || n == 0) return mlhip_rt::fail(MLHIP_EINVAL, "bases need at least one point");
-  const std::vector<int> devs = spread_devices(n, false);
-  if (!devs.empty()) return bases_create_on(devs, curve, group, points, n, window_c, ptsz, out);
+  // (a device-result handle stays on the calling thread's device: its result is a pointer on that device)
+  const bool device_result = window_c > 0 && (window_c & MLHIP_WINDOW_DEVICE_RESULT);
+  if (!device_result) {
+    const std::vector<int> devs = spread_devices(n, false);
+    if (!devs.empty()) return bases_create_on(devs, curve, group, points, n, window_c, ptsz, out);
+  }
   return bases_create_single(curve, group, points, n, window_c, ptsz, out);
 }
 
@@ -241,6 +250,8 @@ int mlhip_bases_create_multi(int curve, int group, const int* devices, int n_dev
   const size_t ptsz = ops->point_size(group);
   if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
   if (!points || n == 0) return mlhip_rt::fail(MLHIP_EINVAL, "bases need at least one point");
+  if (window_c > 0 && (window_c & MLHIP_WINDOW_DEVICE_RESULT))
+    return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_create_multi: MLHIP_WINDOW_DEVICE_RESULT is for handles on one device");
   if (n_devices < 1 || n_devices > 64 || !devices) return mlhip_rt::fail(MLHIP_EINVAL, "device list: 1 .. 64 entries");
   std::vector<int> devs(devices, devices + n_devices);
   for (int d : devs)
@@ -261,6 +272,8 @@ int mlhip_bases_checked_subgroup(mlhip_bases* b) {
 
 int mlhip_bases_msm(mlhip_bases* b, const void* scalars, int scalars_mont, size_t n, void* out_affine) {
   if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (b->plan && b->plan->device_result)
+    return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm: a device-result handle leaves its result in device memory; use mlhip_bases_msm_device");
   if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
   if (n == 0) {
     memset(out_affine, 0, b->ptsz);
@@ -299,11 +312,14 @@ int mlhip_bases_msm_device(mlhip_bases* b, const void* d_scalars, int scalars_mo
   if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_device: the handle is spread over several devices");
   if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
-  if (n == 0) {
+  // (a device-result handle: out_affine is a device pointer, written in stream order -- the all-zero point too -- and the
+  // call returns once everything is queued: the mutex covers the enqueue only)
+  const bool device_result = b->plan->device_result;
+  if (n == 0 && !device_result) {
     memset(out_affine, 0, b->ptsz);
     return 0;
   }
-  if (!d_scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (n && !d_scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   std::lock_guard<std::mutex> lk(b->mu);
   return mlhip_msm_run(b->plan, b->d_pts, d_scalars, scalars_mont, n, stream, out_affine, nullptr);

@@ -150,6 +150,53 @@ void pool_release(PoolEntry* e, bool failed) {
   e->busy = false;
 }
 
+// The window_c of an entry point that returns its result in host memory or over a device list: MLHIP_WINDOW_DEVICE_RESULT is
+// not for it (checked before anything is written).
+int reject_device_result(int window_c, const char* who) {
+  if (window_c > 0 && (window_c & MLHIP_WINDOW_DEVICE_RESULT))
+    return mlhip_rt::fail(MLHIP_EINVAL, std::string(who) + ": MLHIP_WINDOW_DEVICE_RESULT is for mlhip_msm_plan_create, mlhip_bases_create and mlhip_bases_create_device");
+  return 0;
+}
+
+// A launch on `st`: remembered for the finish of a device-result plan, whose previous finish may still be queued on
+// ANOTHER stream -- the new stream then waits for it on the device (the slot, d_out and the sort buffers are being read).
+int plan_begin_on(mlhip_msm_plan* p, hipStream_t st) {
+  p->pending_stream = st;
+  if (p->device_result && p->done_queued && p->done_stream != st) HIPCHK(hipStreamWaitEvent(st, p->done, 0));
+  return 0;
+}
+
+// the unfinished work of a device-result plan (nothing to wait for on a host-result plan: its finish has waited)
+void plan_wait_done(mlhip_msm_plan* p) {
+  if (p->device_result && p->done_queued) (void)hipEventSynchronize(p->done);
+}
+
+// the phase times of a device-result plan's last profiled finish, read once its work is done (plan_finish reads them in the
+// call itself for a host-result plan); [5] is the tail kernel's time
+int plan_read_device_times(mlhip_msm_plan* p) {
+  if (!p->device_result || !p->times_stale || p->pending) return 0;
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipEventSynchronize(p->done));
+  p->times_stale = false;
+  if (p->timed_n != 0 && p->tiles_timed > 0) {
+    p->ms[0] = p->ms[1] = p->ms[2] = 0;
+    for (int s = 0; s < p->tiles_timed; s++) {
+      float a = 0, b = 0;
+      HIPCHK(hipEventElapsedTime(&a, p->ev_tile[s][0], p->ev_tile[s][1]));
+      HIPCHK(hipEventElapsedTime(&b, p->ev_tile[s][1], p->ev_tile[s][2]));
+      p->ms[1] += a;
+      p->ms[2] += b;
+    }
+    HIPCHK(hipEventElapsedTime(&p->ms[3], p->ev[3], p->ev[4]));
+    HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
+  } else if (p->timed_n != 0 && p->tiles_timed == 0) {
+    for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
+    HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
+  }
+  HIPCHK(hipEventElapsedTime(&p->ms[5], p->ev_tail[0], p->ev_tail[1]));
+  return 0;
+}
+
 // can this plan run the segment train (plan_stream / plan_stream_shared)?  The condition stream_begin checks.
 bool plan_can_stream(const mlhip_msm_plan* p) {
   return p->aux && p->d_points28;
@@ -275,7 +322,9 @@ void unpack_window(int packed, int& window_c, int& scalar_bits) {
 // fold_tile != 0: a plan over shifted-base tables (msm_fold.h, mlhip_internal.h) -- window_c is the digit width, the
 // 2^(c-1) buckets all digits share are cut into groups of at most 2^15 for the reduction; the table itself is built by
 // mlhip_tu_plan_fold_build_* (mlhip_bases_create).
-int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits) {
+// device_result: the plan leaves its result in device memory (include/mlhip.h, "device results"; msm_tail.h)
+int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits,
+                   bool device_result) {
   if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null plan pointer");
   *out = nullptr;
   const CurveOps* ops = curve_ops(curve);
@@ -312,6 +361,7 @@ int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold
   p->bits = bits;
   p->Wd = digits;
   p->max_n = max_n;
+  p->device_result = device_result;
   if (fold_tile) {
     p->fold = 1;
     p->fold_tile = fold_tile;
@@ -496,6 +546,7 @@ int mlhip_msm_multi(int curve, int group, const int* devices, int n_devices, con
   if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 (G1) or 2 (G2)");
   if (!out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
   if (n_devices < 1 || n_devices > 64 || !devices) return mlhip_rt::fail(MLHIP_EINVAL, "device list: 1 .. 64 entries");
+  if (int rc_flag = reject_device_result(window_c, "mlhip_msm_multi")) return rc_flag;
   if (n == 0) {
     memset(out_affine, 0, ptsz);
     return 0;
@@ -509,21 +560,27 @@ int mlhip_msm_multi(int curve, int group, const int* devices, int n_devices, con
 }
 
 int mlhip_msm_plan_create(int curve, int group, size_t max_n, int window_c, mlhip_msm_plan** out) {
-  int c = 0, bits = 0;  // (window_c may carry a scalar width: MLHIP_WINDOW_BITS)
+  // (window_c may carry MLHIP_WINDOW_DEVICE_RESULT, taken off first, and a scalar width: MLHIP_WINDOW_BITS)
+  const bool device_result = window_c > 0 && (window_c & MLHIP_WINDOW_DEVICE_RESULT);
+  if (device_result) window_c &= ~MLHIP_WINDOW_DEVICE_RESULT;
+  int c = 0, bits = 0;
   unpack_window(window_c, c, bits);
-  return plan_create_ex(curve, group, max_n, c, 0, out, bits);
+  return plan_create_ex(curve, group, max_n, c, 0, out, bits, device_result);
 }
 
 int mlhip_msm_plan_destroy(mlhip_msm_plan* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->device);
-  void* ptrs[] = {p->d_digits, p->d_sorted, p->d_zero, p->d_offsets, p->d_biglist, p->d_buckets, p->d_A, p->d_W0, p->d_out,
+  plan_wait_done(p);  // (a device-result plan: its last finish may still be running)
+  void* ptrs[] = {p->d_result, p->d_digits, p->d_sorted, p->d_zero, p->d_offsets, p->d_biglist, p->d_buckets, p->d_A, p->d_W0, p->d_out,
                   p->d_order, p->d_hist, p->d_tilesums, p->d_coarse_off, p->d_points28, p->d_blockhist, p->d_state28, p->d_bigprefix, p->d_bigpart, p->d_binprefix};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (p->h_out) (void)hipHostFree(p->h_out);
   for (int i = 0; i < 5; i++)
     if (p->ev[i]) (void)hipEventDestroy(p->ev[i]);
+  for (int i = 0; i < 2; i++)
+    if (p->ev_tail[i]) (void)hipEventDestroy(p->ev_tail[i]);
   if (p->done) (void)hipEventDestroy(p->done);
   if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
   if (p->ev_join) (void)hipEventDestroy(p->ev_join);
@@ -553,6 +610,7 @@ int mlhip_msm_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scal
   if (n && (!d_points || !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null device pointer");
   HIPCHK(hipSetDevice(p->device));
   hipStream_t st = (hipStream_t)stream;
+  if (int rc_order = plan_begin_on(p, st)) return rc_order;
   int rc = curve_ops(p->curve)->plan_launch(p, d_points, d_scalars, scalars_mont, n, st);
   if (rc) {
     // a failure part-way through the launch train: `done` may never have been recorded, so a later finish must not
@@ -591,6 +649,8 @@ int mlhip_msm_launch_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, const void* 
   HIPCHK(hipSetDevice(g1->device));
   hipStream_t st = (hipStream_t)stream;
   void *p1 = const_cast<void*>(d_points_g1), *p2 = const_cast<void*>(d_points_g2), *sc = const_cast<void*>(d_scalars);
+  if (int rc_order = plan_begin_on(g1, st)) return rc_order;
+  if (int rc_order = plan_begin_on(g2, st)) return rc_order;
   return plan_shared(g1, g2, p1, p2, sc, nullptr, nullptr, nullptr, scalars_mont, n, st);
 }
 
@@ -599,6 +659,7 @@ int mlhip_msm_g1g2(int curve, const void* points_g1, const void* points_g2, cons
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   if (!out_g1 || !out_g2) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
+  if (int rc_flag = reject_device_result(window_c, "mlhip_msm_g1g2")) return rc_flag;
   if (n == 0) {  // the points at infinity, as for mlhip_msm_g1 / _g2
     memset(out_g1, 0, ops->g1);
     memset(out_g2, 0, ops->g2);
@@ -667,6 +728,8 @@ int mlhip_msm_plan_assume_srs(mlhip_msm_plan* p, int on) {
   if (!p) return mlhip_rt::fail(MLHIP_EINVAL, "null plan");
   if (p->pending) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_plan_assume_srs with a launch pending");
   if (p->fold) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_plan_assume_srs: this plan reads the tables of a mlhip_bases handle");
+  (void)hipSetDevice(p->device);
+  plan_wait_done(p);  // (a device-result plan: unfinished work still reads the carry-free copy this call gives up)
   p->conv_src = nullptr;  // whatever carry-free copy the plan holds was made under the other promise
   p->points_static = p->trust_subgroup = on != 0;
   if (on) plan_reserve_edwards(p);
@@ -675,7 +738,8 @@ int mlhip_msm_plan_assume_srs(mlhip_msm_plan* p, int on) {
 
 int mlhip_msm_plan_timings(mlhip_msm_plan* p, float* ms, int cap) {
   if (!p || !ms) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
-  int k = cap < 12 ? cap : 12;
+  if (int rc_times = plan_read_device_times(p)) return rc_times;
+  int k = cap < 13 ? cap : 13;
   for (int i = 0; i < k && i < 6; i++) ms[i] = p->ms[i];
   if (k >= 7) ms[6] = p->tiles_timed > 0 ? (float)p->tiles_timed : 1.0f;
   if (k >= 8) ms[7] = (float)p->c;
@@ -683,11 +747,13 @@ int mlhip_msm_plan_timings(mlhip_msm_plan* p, float* ms, int cap) {
   if (k >= 10) ms[9] = p->last_ed ? 1.0f : 0.0f;
   if (k >= 11) ms[10] = p->fold ? 1.0f : 0.0f;
   if (k >= 12) ms[11] = (float)p->bits;  // the plan's scalar width (fr_bits: full width)
+  if (k >= 13) ms[12] = p->device_result ? 1.0f : 0.0f;  // the result stays in device memory ("device results")
   return k;
 }
 
 int mlhip_msm_g1(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
                  void* out_affine) {
+  if (int rc_flag = reject_device_result(window_c, "mlhip_msm_g1")) return rc_flag;
   int c = 0, bits = 0;  // (window_c may carry a scalar width: MLHIP_WINDOW_BITS)
   unpack_window(window_c, c, bits);
   return msm_host_buffers(curve, MLHIP_GROUP_G1, points, scalars, scalars_mont, n, c, out_affine, bits);
@@ -695,6 +761,7 @@ int mlhip_msm_g1(int curve, const void* points, const void* scalars, int scalars
 
 int mlhip_msm_g2(int curve, const void* points, const void* scalars, int scalars_mont, size_t n, int window_c,
                  void* out_affine) {
+  if (int rc_flag = reject_device_result(window_c, "mlhip_msm_g2")) return rc_flag;
   int c = 0, bits = 0;
   unpack_window(window_c, c, bits);
   return msm_host_buffers(curve, MLHIP_GROUP_G2, points, scalars, scalars_mont, n, c, out_affine, bits);

@@ -115,6 +115,18 @@ struct mlhip_msm_plan {
   bool pending = false;
   size_t pending_n = 0;
   float ms[6] = {0, 0, 0, 0, 0, 0};
+  // A device-result plan (include/mlhip.h, "device results"; msm_tail.h): mlhip_msm_finish queues the tail kernel behind the
+  // pending launch, on its stream, and returns without waiting.  The kernel writes [affine | XYZZ] into d_result; the
+  // caller's device pointers receive copies of it.  No h_out.  `done` is recorded by that finish: a launch on another
+  // stream waits for it on the device, destroy / assume_srs / timings wait for it on the host.
+  bool device_result = false;
+  void* d_result = nullptr;
+  hipStream_t pending_stream = nullptr;  // the stream of the pending launch (set by mlhip_msm_launch / _launch_shared)
+  hipStream_t done_stream = nullptr;     // the stream `done` was last recorded on
+  bool done_queued = false;              // ... and whether it ever was
+  hipEvent_t ev_tail[2] = {nullptr, nullptr};  // around the tail kernel, under profiling: [5] of mlhip_msm_plan_timings
+  bool times_stale = false;  // a profiled finish whose events mlhip_msm_plan_timings has not read yet
+  size_t timed_n = 0;        // ... and its n (0: no phase events but the tail's)
   // tiles of device-resident inputs: the entry lists of tile s + 1 are sorted on `sort_stream`, in one of two helper
   // records that hold sort buffers only, while tile s accumulates (msm_plan.h: sort_ahead_*)
   mlhip_msm_plan* sort_helper[2] = {nullptr, nullptr};

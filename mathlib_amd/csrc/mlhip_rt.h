@@ -51,7 +51,9 @@ struct HostCall {
 int pick_window(size_t n, int fr_bits);
 // fold_tile != 0: a plan over shifted-base tables (msm_fold.h, mlhip_internal.h)
 // scalar_bits: 0 or >= the curve's fr_bits = full width; 1 .. fr_bits - 1 = a short-scalar plan (ignored when fold_tile != 0)
-int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits = 0);
+// device_result: the plan leaves its result in device memory (include/mlhip.h, "device results")
+int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold_tile, mlhip_msm_plan** out, int scalar_bits = 0,
+                   bool device_result = false);
 // the window width the library picks for n scalars of `bits` bits in `group` (bits == fr_bits: pick_window(n, fr_bits))
 int pick_window_bits(size_t n, int bits, int fr_bits, int group = MLHIP_GROUP_G1);
 void plan_reserve_edwards(mlhip_msm_plan* p);

@@ -86,4 +86,5 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 #include "point_sum.h"
 #include "msm_bases_batch.h"
 #include "msm_fold.h"
+#include "msm_tail.h"
 #include "msm_plan.h"

@@ -156,7 +156,13 @@ int plan_alloc(mlhip_msm_plan* p) {
     p->fold_nsel2 = 4 + p->nb + lgW;
   }
   HIPCHK(hipMalloc(&p->d_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * p->xyzz_size));
-  HIPCHK(hipHostMalloc(&p->h_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * p->xyzz_size, hipHostMallocDefault));
+  if (p->device_result) {
+    // a device-result plan (msm_tail.h): no host copy of the partial sums; the tail kernel writes [affine | XYZZ] here
+    HIPCHK(hipMalloc(&p->d_result, p->pt_size + p->xyzz_size));
+    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&p->ev_tail[i]));
+  } else {
+    HIPCHK(hipHostMalloc(&p->h_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * p->xyzz_size, hipHostMallocDefault));
+  }
   for (int i = 0; i < 5; i++) HIPCHK(hipEventCreate(&p->ev[i]));
   HIPCHK(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
   {  // the auxiliary stream: point conversion beside the sort, and the uploads of a streamed host-buffer MSM
@@ -561,11 +567,13 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
 }
 
 // the tail of both sequences: bucket sums -> partial sums -> h_out, then `done` (plan_finish waits for it)
+// (a device-result plan stops at the partial sums: its finish queues the tail kernel behind them and records `done`)
 template <class C, class F>
 int finish_train(mlhip_msm_plan* p, bool prof, hipStream_t st) {
   if (int rc_red = launch_reduce<C, F>(p, st)) return rc_red;
   if (prof) HIPCHK(hipEventRecord(p->ev[4], st));
   HIPCHK(hipGetLastError());
+  if (p->device_result) return 0;
   HIPCHK(hipMemcpyAsync(p->h_out, p->d_out, ((size_t)p->W * p->nsel + p->fold_nsel2) * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(p->done, st));
   return 0;
@@ -928,10 +936,70 @@ int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1
   return stream_end<C, F2>(p2, c2, st);
 }
 
+// What the tail kernel needs of a plan (msm_tail.h: MsmTailArgs).
+inline int msm_tail_args(const mlhip_msm_plan* p, MsmTailArgs& a) {
+  memset(&a, 0, sizeof(a));
+  a.nsel = p->nsel;
+  a.lgL = p->lgL;
+  a.empty = p->pending_n == 0;
+  if (p->fold) {
+    // one window and no Horner pass: the combined entries, or the only group's own (host_tail_fold with W = 1 adds V_0 to
+    // 2^lgM times an empty sum).  Several groups without the combined entries do not occur: plan_alloc combines whenever
+    // W > 1 (a folded plan has the carry-free reduction and at most 16 groups).
+    if (!p->fold_nsel2 && p->W != 1) return mlhip_rt::fail(MLHIP_EINVAL, "device-result plan: bucket groups without their combined sums");
+    a.W = 1;
+    a.first = p->fold_nsel2 ? p->W * p->nsel : 0;
+    a.nb = p->fold_nsel2 ? p->fold_nsel2 - 4 : p->nb;
+    return 0;
+  }
+  if (p->W > MSM_TAIL_MAX_W) return mlhip_rt::fail(MLHIP_EINVAL, "device-result plan: more windows than the tail kernel holds");
+  a.W = p->W;
+  a.nb = p->nb;
+  a.horner = 1;
+  int down[MSM_TAIL_MAX_W] = {};
+  msm_window_shifts(p->bits, p->c, down);  // (a short-scalar plan: its own, shorter layout)
+  for (int w = 0; w < p->W; w++) a.down[w] = (unsigned char)down[w];
+  return 0;
+}
+
+// mlhip_msm_finish of a device-result plan: ONE launch on the stream of the pending launch -- the tail kernel into the
+// plan's slot -- then the delivery (a copy of the slot per requested output: no kernel of the library dereferences the
+// caller's pointers) and `done`.  No allocation and no host wait; the phase times are read by mlhip_msm_plan_timings.
+template <class C, class F>
+int plan_finish_device(mlhip_msm_plan* p, void* d_out_affine, void* d_out_xyzz) {
+  typedef Affine<F> A;
+  typedef XYZZ<F> X;
+  constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;
+  if (!p->pending) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_finish without a pending mlhip_msm_launch");
+  p->pending = false;
+  MsmTailArgs a;
+  if (int rc = msm_tail_args(p, a)) return rc;
+  hipStream_t st = p->pending_stream;
+  A* slot_affine = (A*)p->d_result;
+  X* slot_xyzz = (X*)((char*)p->d_result + sizeof(A));
+  const bool prof = p->profiling;
+  if (prof) HIPCHK(hipEventRecord(p->ev_tail[0], st));
+  if constexpr (kG2)
+    k_msm_tail<TailLanePair<C>, 2><<<dim3(1), dim3(128), 0, st>>>((const X*)p->d_out, a, slot_xyzz, slot_affine);
+  else
+    k_msm_tail<TailOneLane<F>, 1><<<dim3(1), dim3(64), 0, st>>>((const X*)p->d_out, a, slot_xyzz, slot_affine);
+  if (prof) HIPCHK(hipEventRecord(p->ev_tail[1], st));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(d_out_affine, slot_affine, sizeof(A), hipMemcpyDefault, st));
+  if (d_out_xyzz) HIPCHK(hipMemcpyAsync(d_out_xyzz, slot_xyzz, sizeof(X), hipMemcpyDefault, st));
+  HIPCHK(hipEventRecord(p->done, st));
+  p->done_stream = st;
+  p->done_queued = true;
+  p->times_stale = prof;
+  p->timed_n = p->pending_n;
+  return 0;
+}
+
 template <class C, class F>
 int plan_finish(mlhip_msm_plan* p, void* out_affine, void* out_xyzz) {
   typedef Affine<F> A;
   typedef XYZZ<F> X;
+  if (p->device_result) return plan_finish_device<C, F>(p, out_affine, out_xyzz);
   X total;
   if (!p->pending) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_msm_finish without a pending mlhip_msm_launch");
   p->pending = false;
