@@ -30,6 +30,7 @@ package hip
 #include "mlhip.h"
 #include "mlhip_bits.h"
 #include "mlhip_products.h"
+#include "mlhip_subgroup.h"
 */
 import "C"
 
@@ -511,7 +512,26 @@ func (c *Curve) MulBatchG1(a []driver.G1, b []driver.Zr) []driver.G1 {
 	for i := range a {
 		points[i] = a[i].(*gurvy381.G1).G1Affine
 	}
-	return c.scalarMulG1(points, 1, b)
+	return c.scalarMulG1(points, 1, b, false)
+}
+
+// MulBatchSubgroupG1 is MulBatchG1 for points the caller knows to be in G1 (decoded with the subgroup check, MSM outputs
+// over checked bases, generators and their multiples): the same results from the curve's endomorphism and a split of the
+// scalar (mlhip_scalar_mul_subgroup).  A point outside G1 gives an undefined result for its own product; G1.Mul and
+// MulBatchG1 accept any point of the curve.
+func (c *Curve) MulBatchSubgroupG1(a []driver.G1, b []driver.Zr) []driver.G1 {
+	n := len(a)
+	if len(b) != n {
+		panic("hip: MulBatchSubgroupG1 length mismatch")
+	}
+	if n == 0 {
+		return nil
+	}
+	points := make([]bls12381.G1Affine, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G1).G1Affine
+	}
+	return c.scalarMulG1(points, 1, b, true)
 }
 
 // BaseMulBatchG1 returns base.Mul(b[i]) for every i: one base (a generator, a Pedersen base), many scalars.  From 2^12
@@ -521,10 +541,10 @@ func (c *Curve) BaseMulBatchG1(base driver.G1, b []driver.Zr) []driver.G1 {
 	if len(b) == 0 {
 		return nil
 	}
-	return c.scalarMulG1([]bls12381.G1Affine{base.(*gurvy381.G1).G1Affine}, 0, b)
+	return c.scalarMulG1([]bls12381.G1Affine{base.(*gurvy381.G1).G1Affine}, 0, b, false)
 }
 
-func (c *Curve) scalarMulG1(points []bls12381.G1Affine, stride int, b []driver.Zr) []driver.G1 {
+func (c *Curve) scalarMulG1(points []bls12381.G1Affine, stride int, b []driver.Zr, subgroup bool) []driver.G1 {
 	n := len(b)
 	scalars := make([]fr.Element, n)
 	for i := range b {
@@ -532,6 +552,10 @@ func (c *Curve) scalarMulG1(points []bls12381.G1Affine, stride int, b []driver.Z
 	}
 	res := make([]bls12381.G1Affine, n)
 	check(func() C.int {
+		if subgroup {
+			return C.mlhip_scalar_mul_subgroup(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1,
+				unsafe.Pointer(&points[0]), C.size_t(stride), unsafe.Pointer(&scalars[0]), 1, C.size_t(n), unsafe.Pointer(&res[0]))
+		}
 		return C.mlhip_scalar_mul(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1,
 			unsafe.Pointer(&points[0]), C.size_t(stride), unsafe.Pointer(&scalars[0]), 1, C.size_t(n), unsafe.Pointer(&res[0]))
 	})
@@ -555,17 +579,33 @@ func (c *Curve) MulBatchG2(a []driver.G2, b []driver.Zr) []driver.G2 {
 	for i := range a {
 		points[i] = a[i].(*gurvy381.G2).G2Affine
 	}
-	return c.scalarMulG2(points, 1, b)
+	return c.scalarMulG2(points, 1, b, false)
+}
+
+// MulBatchSubgroupG2: the same for points the caller knows to be in G2.
+func (c *Curve) MulBatchSubgroupG2(a []driver.G2, b []driver.Zr) []driver.G2 {
+	n := len(a)
+	if len(b) != n {
+		panic("hip: MulBatchSubgroupG2 length mismatch")
+	}
+	if n == 0 {
+		return nil
+	}
+	points := make([]bls12381.G2Affine, n)
+	for i := range a {
+		points[i] = a[i].(*gurvy381.G2).G2Affine
+	}
+	return c.scalarMulG2(points, 1, b, true)
 }
 
 func (c *Curve) BaseMulBatchG2(base driver.G2, b []driver.Zr) []driver.G2 {
 	if len(b) == 0 {
 		return nil
 	}
-	return c.scalarMulG2([]bls12381.G2Affine{base.(*gurvy381.G2).G2Affine}, 0, b)
+	return c.scalarMulG2([]bls12381.G2Affine{base.(*gurvy381.G2).G2Affine}, 0, b, false)
 }
 
-func (c *Curve) scalarMulG2(points []bls12381.G2Affine, stride int, b []driver.Zr) []driver.G2 {
+func (c *Curve) scalarMulG2(points []bls12381.G2Affine, stride int, b []driver.Zr, subgroup bool) []driver.G2 {
 	n := len(b)
 	scalars := make([]fr.Element, n)
 	for i := range b {
@@ -573,6 +613,10 @@ func (c *Curve) scalarMulG2(points []bls12381.G2Affine, stride int, b []driver.Z
 	}
 	res := make([]bls12381.G2Affine, n)
 	check(func() C.int {
+		if subgroup {
+			return C.mlhip_scalar_mul_subgroup(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2,
+				unsafe.Pointer(&points[0]), C.size_t(stride), unsafe.Pointer(&scalars[0]), 1, C.size_t(n), unsafe.Pointer(&res[0]))
+		}
 		return C.mlhip_scalar_mul(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2,
 			unsafe.Pointer(&points[0]), C.size_t(stride), unsafe.Pointer(&scalars[0]), 1, C.size_t(n), unsafe.Pointer(&res[0]))
 	})

@@ -356,6 +356,44 @@ MLHIP_API int mlhip_scalar_mul_device(int curve, int group, const void* d_points
 MLHIP_API int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stride, const void* scalars,
                      int scalars_mont, size_t n, void* out_affine);
 
+/* ---- points promised in G1 / G2: batched Mul over the curve's endomorphisms ------------------------------------------------
+ * For callers who know where their points come from: decoded with subgroup_check = 1, outputs of MSMs over checked bases,
+ * generators and their multiples, the r_k A_k of a batch verifier.  The reference's own G1.Mul / G2.Mul are defined for every
+ * point of the curve, and the endomorphisms act as multiplications by known scalars on the prime-order subgroup ONLY -- so
+ * the library never takes this route by itself.
+ *
+ * Result.  With the promise kept -- every point is in the prime-order subgroup or is the point at infinity (all zero) --
+ * the bytes of the plain call on the same inputs: scalars_mont, unreduced 256-bit scalars (reduced mod r first), infinity in,
+ * s = 0 mod r, point_stride 0 or 1.  A point outside the subgroup gives an undefined RESULT for its own product and for no
+ * other, never a fault: no address depends on point data.
+ *
+ * How it is said.  The symbol table does not grow: the promise travels in the `group` argument of exactly two entry points,
+ * the host-buffer batched Mul and its _device form above, as MLHIP_GROUP_SUBGROUP(group) below; they take the flag off
+ * and read the rest as before.  include/mlhip_subgroup.h wraps this in two inline functions for C, C++ and cgo, which take a
+ * plain group: the batched Mul with the suffix _subgroup (curve_id, group, points, point_stride, scalars, scalars_mont, n,
+ * out_affine) and with _subgroup_device (.., d_out_affine, stream).  Every other entry point that takes a group -- the plan
+ * and handle constructors, the MSM over a device list, the batched MSMs -- rejects the flagged value as it rejects any
+ * group other than 1 or 2, and nothing inside the library produces it.
+ *
+ * Range.  group = MLHIP_GROUP_G1 or _G2; anything else makes the macro -1, which is MLHIP_EINVAL.  n = 0 returns 0 before
+ * any pointer or device is looked at.  A null pointer, an unknown curve id and point_stride > 1 are MLHIP_EINVAL before
+ * anything is launched.  The _device form is asynchronous and in order on `stream`, like the plain one.
+ *
+ * How it runs (msm_scalar_mul_endo.h).  G1 of the BLS12 curves: s = a + b x^2 with a, b < 2^128,
+ * [s]P = [a]P + [b](beta Px, -Py), joint signed 4-bit windows -- 128 doublings and at most 66 additions instead of 256 and
+ * 65.  G2 of every curve: the digits of s in base |x| (BLS12, four) or 6 x^2 (BN254, two) over Q, psi(Q), .., a 15-entry
+ * table of their sums, 64 steps of one doubling (BN254: two) and at most one addition.  Two routes the flag never changes:
+ * BN254 G1 -- E(Fp) has prime order there, the promise is vacuous and no short split exists without a lattice reduction:
+ * the flagged call is accepted and runs the plain kernel -- and point_stride = 0 from MLHIP_FIXED_BASE_MIN scalars on, where
+ * the fixed-base table has no doubling to save: accepted and ignored.  MLHIP_SCALAR_MUL_ENDO=0 sends every flagged call to
+ * the plain kernels (second implementation, A/B).
+ * Measured: profiles/scalar_mul_endo_ab.txt, DESIGN.md section 17 -- 2^20 products of per-point bases on one MI355X, flagged call
+ * against plain call in one process, same bytes, on two machines: G1 0.69 - 0.70 (BLS12-381) / 0.67 (BLS12-377) of the plain
+ * call's time, G2 0.54 - 0.58 / 0.53 - 0.56 and 0.72 - 0.76 on BN254 (the operation counts predict 0.67, 0.5 and 0.65); within
+ * 0.05 of that from 2^10 products on.  Every (curve, group) that has a split is ahead by far more than two identical plain
+ * runs differ (at most 0.012 of their time at 2^20), so all of them take it. */
+#define MLHIP_GROUP_SUBGROUP(group) ((group) == 1 || (group) == 2 ? ((group) | 0x100) : -1)
+
 /* K independent MSMs in one call: out[k] = sum_{offsets[k] <= i < offsets[k+1]} [scalars[i]] points[i] (the batched form of
  * MultiScalarMul / Mul2: an idemix or BBS verifier's many proofs of a few pairs each).
  * offsets: K+1 nondecreasing entries in HOST memory, offsets[0] = 0, offsets[K] = total pairs; anything else, or a null
@@ -611,6 +649,7 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_NO_QUAD_ACC=1              small MSMs: one bucket per lane instead of per quad
  *     MLHIP_G2_KC=1                    G2 buckets split by coordinate (one-lane Karatsuba Fp2 products; measured 3-5 % slower)
  *     MLHIP_PAIRING_ONE_LANE=1, MLHIP_PAIRING_SAT=1, MLHIP_SCALAR_MUL_ONE_LANE=1   one-lane / saturated-limb pairing and G2.Mul kernels
+ *     MLHIP_SCALAR_MUL_ENDO=0          batched Mul with MLHIP_GROUP_SUBGROUP: the plain double-and-add kernels (also the A/B switch)
  *   tests only
  *     MLHIP_FAULT_INJECT=sort_helper_alloc   the sort-ahead helper allocation "fails" (tests/test_gpu_parity.py)
  */

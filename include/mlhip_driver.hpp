@@ -16,7 +16,7 @@
 //   Curve::FExp(gt)                      driver/math.go:56-57                         -> mlhip_final_exp
 //   G1::Mul / Mul2 / Add / Sub / Neg     driver/math.go:249-288
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
-//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
+//   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, MulBatchSubgroup, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
 //             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, SumG1, SumG2
 #pragma once
@@ -31,6 +31,7 @@
 #include "mlhip.h"
 #include "mlhip_bits.h"
 #include "mlhip_products.h"
+#include "mlhip_subgroup.h"
 
 namespace mlhip_driver {
 
@@ -611,6 +612,16 @@ class Curve {
   std::vector<G2> MulBatch(const std::vector<G2>& points, const std::vector<Zr>& scalars) const {
     return mul_batch<G2>(MLHIP_GROUP_G2, g2_bytes, points, 1, scalars);
   }
+  // MulBatch for points the caller knows to be in G1 / G2 (decoded with the subgroup check, MSM outputs over checked bases,
+  // generators and their multiples): the same results from the curve's endomorphism and a split of the scalar
+  // (mlhip_scalar_mul_subgroup).  A point outside the subgroup gives an undefined result for its own product; G1.Mul, G2.Mul
+  // and MulBatch accept any point of the curve.
+  std::vector<G1> MulBatchSubgroup(const std::vector<G1>& points, const std::vector<Zr>& scalars) const {
+    return mul_batch<G1>(MLHIP_GROUP_G1, g1_bytes, points, 1, scalars, true);
+  }
+  std::vector<G2> MulBatchSubgroup(const std::vector<G2>& points, const std::vector<Zr>& scalars) const {
+    return mul_batch<G2>(MLHIP_GROUP_G2, g2_bytes, points, 1, scalars, true);
+  }
   // out[i] = base.Mul(scalars[i]): one base, many scalars -- from 2^12 scalars on through a table of the base's multiples that
   // the library keeps on the device for later calls with the same base
   std::vector<G1> BaseMulBatch(const G1& base, const std::vector<Zr>& scalars) const {
@@ -703,14 +714,16 @@ class Curve {
 
  private:
   template <class P>
-  std::vector<P> mul_batch(int group, size_t size, const std::vector<P>& points, size_t stride, const std::vector<Zr>& scalars) const {
+  std::vector<P> mul_batch(int group, size_t size, const std::vector<P>& points, size_t stride, const std::vector<Zr>& scalars,
+                           bool subgroup = false) const {
     if (stride != 0 && points.size() != scalars.size()) throw std::invalid_argument("MulBatch: length mismatch");
     std::vector<P> out;
     const size_t n = scalars.size();
     if (n == 0) return out;
     Bytes pts, sc, o(size * n);
     pack(points, scalars, pts, sc);
-    check(mlhip_scalar_mul(id, group, pts.data(), stride, sc.data(), scalars_mont ? 1 : 0, n, o.data()));
+    check(subgroup ? mlhip_scalar_mul_subgroup(id, group, pts.data(), stride, sc.data(), scalars_mont ? 1 : 0, n, o.data())
+                   : mlhip_scalar_mul(id, group, pts.data(), stride, sc.data(), scalars_mont ? 1 : 0, n, o.data()));
     for (size_t i = 0; i < n; i++) {
       P g;
       g.curve = this;

@@ -329,6 +329,23 @@ def msm_bits(curve: int, group: int, points, scalars, scalars_mont: bool, scalar
     return out.raw
 
 
+def GROUP_SUBGROUP(group: int) -> int:
+    """MLHIP_GROUP_SUBGROUP of include/mlhip.h: the group argument of mlhip_scalar_mul / _device with the caller's promise
+    that every point is in the prime-order subgroup (or at infinity); -1, which the library rejects, for any other group"""
+    return (group | 0x100) if group in (GROUP_G1, GROUP_G2) else -1
+
+
+def scalar_mul_subgroup(lib, curve: int, group: int, points, point_stride: int, scalars, scalars_mont: int, n: int, out) -> int:
+    """include/mlhip_subgroup.h: mlhip_scalar_mul for points promised in G1 / G2 (the return code, as the C function)"""
+    return lib.mlhip_scalar_mul(curve, GROUP_SUBGROUP(group), points, point_stride, scalars, scalars_mont, n, out)
+
+
+def scalar_mul_subgroup_device(lib, curve: int, group: int, d_points, point_stride: int, d_scalars, scalars_mont: int, n: int,
+                               d_out, stream) -> int:
+    """include/mlhip_subgroup.h: the same on device pointers, asynchronous and in order on `stream`"""
+    return lib.mlhip_scalar_mul_device(curve, GROUP_SUBGROUP(group), d_points, point_stride, d_scalars, scalars_mont, n, d_out, stream)
+
+
 WINDOW_DEVICE_RESULT = 1 << 20
 """MLHIP_WINDOW_DEVICE_RESULT of include/mlhip.h: OR-ed onto a plain window_c or onto window_bits(c, bits)"""
 

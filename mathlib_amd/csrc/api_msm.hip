@@ -158,6 +158,14 @@ int reject_device_result(int window_c, const char* who) {
   return 0;
 }
 
+// MLHIP_GROUP_SUBGROUP(group) of include/mlhip.h taken apart (mlhip_scalar_mul / _device only): true and the plain group
+// for the two flagged values, otherwise false and `group` as it came -- so every other value is rejected as before.
+bool take_subgroup_promise(int& group) {
+  if (group != MLHIP_GROUP_SUBGROUP(MLHIP_GROUP_G1) && group != MLHIP_GROUP_SUBGROUP(MLHIP_GROUP_G2)) return false;
+  group &= 0xFF;
+  return true;
+}
+
 // A launch on `st`: remembered for the finish of a device-result plan, whose previous finish may still be queued on
 // ANOTHER stream -- the new stream then waits for it on the device (the slot, d_out and the sort buffers are being read).
 int plan_begin_on(mlhip_msm_plan* p, hipStream_t st) {
@@ -769,24 +777,34 @@ int mlhip_msm_g2(int curve, const void* points, const void* scalars, int scalars
 
 int mlhip_scalar_mul_device(int curve, int group, const void* d_points, size_t point_stride, const void* d_scalars,
                             int mont, size_t n, void* d_out, void* stream) {
+  const bool subgroup = take_subgroup_promise(group);
   if (group != MLHIP_GROUP_G1 && group != MLHIP_GROUP_G2) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
   if (point_stride > 1) return mlhip_rt::fail(MLHIP_EINVAL, "point_stride must be 0 or 1");
+  if (subgroup) {  // a promised call checks what it can before it asks for a device (n = 0: nothing to do, nothing read)
+    if (n == 0) return 0;
+    if (!curve_ops(curve)) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
+    if (!d_points || !d_scalars || !d_out) return mlhip_rt::fail(MLHIP_EINVAL, "null device pointer");
+  }
   int rc = ensure_device();
   if (rc) return rc;
   if (n == 0) return 0;
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
-  return ops->scalar_mul(group, d_points, point_stride, d_scalars, mont, n, d_out, (hipStream_t)stream);
+  return ops->scalar_mul(group, d_points, point_stride, d_scalars, mont, n, d_out, (hipStream_t)stream, subgroup);
 }
 
 int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stride, const void* scalars, int mont,
                      size_t n, void* out) {
+  const int group_arg = group;  // (with the promise, as mlhip_scalar_mul_device takes it)
+  const bool subgroup = take_subgroup_promise(group);
+  if (subgroup && n == 0) return 0;
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   const size_t ptsz = ops->point_size(group);
   if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
   if (n == 0) return 0;
   if (!points || !scalars || !out) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (subgroup && point_stride > 1) return mlhip_rt::fail(MLHIP_EINVAL, "point_stride must be 0 or 1");
   int rc = ensure_device();
   if (rc) return rc;
   const size_t npts = point_stride ? n : 1;
@@ -796,7 +814,7 @@ int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stri
   void* ds = hc.up(scalars, n * 32);
   void* dout = hc.dev(n * ptsz);
   if (hc.rc) return hc.rc;
-  rc = mlhip_scalar_mul_device(curve, group, dp, point_stride, ds, mont, n, dout, hc.l.st);
+  rc = mlhip_scalar_mul_device(curve, group_arg, dp, point_stride, ds, mont, n, dout, hc.l.st);
   if (rc) return rc;
   return hc.down(out, dout, n * ptsz);
 }

@@ -185,7 +185,7 @@ struct mlhip_g2_prepared_tables {
      hipStream_t st))                                                                                                     \
   X(C, int, scalar_mul,                                                                                                   \
     (int group, const void* d_points, size_t point_stride, const void* d_scalars, int mont, size_t n, void* d_out,        \
-     hipStream_t st))                                                                                                     \
+     hipStream_t st, bool subgroup))                                                                                      \
   X(C, int, plan_fold_build, (mlhip_msm_plan * p, const void* d_points, size_t n, hipStream_t st))                        \
   X(C, int, msm_batch,                                                                                                    \
     (int group, const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,    \

@@ -80,6 +80,7 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 #include "msm_ed.h"
 #include "msm_reduce.h"
 #include "msm_g2.h"
+#include "msm_scalar_mul_endo.h"
 #include "msm_scalar_mul.h"
 #include "msm_batch.h"
 #include "msm_batch_bucket.h"

@@ -459,9 +459,11 @@ __global__ void __launch_bounds__(64) k_fixed_base_lp28(const AffineG2_28<C>* __
   o[2 + hi] = a.y.v;
 }
 
+// subgroup: the caller promises points of the prime-order subgroup (MLHIP_GROUP_SUBGROUP) -- the per-point products then run
+// the endomorphism split of msm_scalar_mul_endo.h where the curve and group have one; the table path below ignores it
 template <class C, class F>
 int scalar_mul_device(const void* d_points, size_t point_stride, const void* d_scalars, int mont, size_t n, void* d_out,
-                      hipStream_t st) {
+                      hipStream_t st, bool subgroup = false) {
   if (n == 0) return 0;
   const bool one_lane = mlhip_alt_switch("MLHIP_SCALAR_MUL_ONE_LANE");  // G2 on one lane per product: test build only
   (void)one_lane;
@@ -563,6 +565,10 @@ int scalar_mul_device(const void* d_points, size_t point_stride, const void* d_s
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(fb.last, st));
+    return 0;
+  }
+  if (subgroup && !one_lane && scalar_mul_endo_launch<C, F>(d_points, point_stride, d_scalars, mont, n, d_out, st)) {
+    HIPCHK(hipGetLastError());
     return 0;
   }
   if constexpr (!std::is_same<F, FpField<C>>::value) {

@@ -24,10 +24,10 @@ int MLHIP_TU_FN(plan_shared)(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d_poi
   return plan_stream_shared<MLHIP_TU_CURVE>(g1, g2, d_points_g1, d_points_g2, d_scalars, h_points_g1, h_points_g2, h_scalars, mont, n, st);
 }
 int MLHIP_TU_FN(scalar_mul)(int group, const void* d_points, size_t point_stride, const void* d_scalars, int mont,
-                              size_t n, void* d_out, hipStream_t st) {
+                              size_t n, void* d_out, hipStream_t st, bool subgroup) {
   if (group == MLHIP_GROUP_G1)
-    return scalar_mul_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, point_stride, d_scalars, mont, n, d_out, st);
-  return scalar_mul_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, point_stride, d_scalars, mont, n, d_out, st);
+    return scalar_mul_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, point_stride, d_scalars, mont, n, d_out, st, subgroup);
+  return scalar_mul_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, point_stride, d_scalars, mont, n, d_out, st, subgroup);
 }
 int MLHIP_TU_FN(plan_fold_build)(mlhip_msm_plan* p, const void* d_points, size_t n, hipStream_t st) {
   if (p->group == MLHIP_GROUP_G1) return plan_fold_build<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(p, d_points, n, st);

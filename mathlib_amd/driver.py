@@ -580,6 +580,23 @@ class Curve:
                                       1 if self.scalars_mont else 0, n, out))
         return [cls(out.raw[i * size : (i + 1) * size], self) for i in range(n)]
 
+    def MulBatchSubgroup(self, points: Sequence, scalars: Sequence[Zr]) -> list:
+        """MulBatch for points the caller knows to be in G1 / G2 (decoded with the subgroup check, MSM outputs over checked
+        bases, generators and their multiples): the same results from the curve's endomorphism and a split of the scalar
+        (mlhip_scalar_mul_subgroup).  A point outside the subgroup gives an undefined result for its own product; G1.Mul,
+        G2.Mul and MulBatch accept any point of the curve."""
+        if len(points) != len(scalars):
+            raise ValueError("MulBatchSubgroup: length mismatch")
+        n = len(points)
+        if n == 0:
+            return []
+        cls = type(points[0])
+        group, size = (GROUP_G1, self.g1_bytes) if cls is G1 else (GROUP_G2, self.g2_bytes)
+        out = ctypes.create_string_buffer(size * n)
+        check(_lib.scalar_mul_subgroup(load(), self.id, group, b"".join(p.raw for p in points), 1, self._scalars(scalars),
+                                  1 if self.scalars_mont else 0, n, out))
+        return [cls(out.raw[i * size : (i + 1) * size], self) for i in range(n)]
+
     def BaseMulBatch(self, base, scalars: Sequence[Zr]) -> list:
         """out[i] = base.Mul(scalars[i]): one base (a generator, a Pedersen base), many scalars.  From 2^12 scalars on the
         library multiplies through a table of the base's multiples that it keeps on the device for later calls with the
