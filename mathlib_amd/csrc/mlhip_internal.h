@@ -61,7 +61,7 @@ struct mlhip_msm_plan {
   int Wd = 0, fold = 0;
   size_t fold_tile = 0, fold_n = 0;  // rows per digit block; bases tabulated
   size_t fold_rows = 0;              // rows allocated in d_points28 (tiles x Wd x fold_tile): carry-free rows or Niels triples
-  // the W groups' sums are combined on the device into the sums of one window of W T chunks (k_group_combine_q / _lp);
+  // the W groups' sums are combined on the device into the sums of one window of W T chunks (msm_reduce.h: group_combine_body);
   // d_out / h_out then hold fold_nsel2 = 4 + nb + lg W more entries behind the W x nsel ones, and the host tail reads those
   int fold_nsel2 = 0;
   size_t pt_size, xyzz_size;
@@ -85,9 +85,10 @@ struct mlhip_msm_plan {
   // on plans that never take the Edwards path
   size_t points28_elem = 0, points28_elem_ed = 0;
   bool profiling = false;
-  bool reduce_one_lane = false;
-  bool reduce28 = false;  // G1: the reduction reads the carry-free bucket state (d_state28) -- k_chunks_q28 / k_masked_sums_q28
-  int red_block = 256;  // workgroup size of k_chunks_q (MLHIP_RED_BLOCK)
+  // which reduction form launch_reduce picks (msm_reduce.h: "reduction forms")
+  bool reduce_one_lane = false;  // LaneForm (test build)
+  bool reduce28 = false;  // the reduction reads the carry-free bucket state (d_state28): Quad28Form / Pair28Form; else QuadForm / PairForm
+  int red_block = 256;  // workgroup size of the quad forms' chunk kernels (MLHIP_RED_BLOCK)
   int acc_block = 64;  // workgroup size of the bucket-accumulation kernel (MLHIP_ACC_BLOCK)
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipEvent_t done = nullptr;

@@ -1,10 +1,11 @@
 // msm_accumulate.h -- bucket accumulation.  The boundary-form kernels on 32-bit Montgomery limbs (k_accumulate,
-// k_big_slices: the second implementation the parity tests compare with, and the slices of plain plans), the LDS trees,
-// and the three steps of the carry-free accumulation written once over a bucket form (accumulate_seg_body,
-// big_slices_body, accumulate_big_body; "bucket forms" below) with the G1 Weierstrass form and its kernels.  The Edwards
-// form is in msm_ed.h, the two G2 forms are in msm_g2.h.  Part of msm_kernels.h.
+// k_big_slices: the second implementation the parity tests compare with, and the slices of plain plans) and the three
+// steps of the carry-free accumulation written once over a bucket form (accumulate_seg_body, big_slices_body,
+// accumulate_big_body; "bucket forms" below) with the G1 Weierstrass form and its kernels, the quad-lane kernel of small
+// MSMs among them.  The Edwards form is in msm_ed.h, the two G2 forms are in msm_g2.h.  Part of msm_kernels.h.
 #pragma once
-// (included by msm_kernels.h after its common headers and constants)
+// (included by msm_kernels.h after its common headers, its constants and msm_reduce.h: the LDS trees, the out-of-line group
+// operations and the quad loads / stores are there)
 
 namespace mlhip {
 
@@ -45,96 +46,6 @@ __global__ void __launch_bounds__(256) k_points_to28(const Affine<FpField<C>>* _
   affine28_from<C>(q, points[i]);
   out[i] = q;
 }
-
-// out-of-line group operations for kernels that use several of them (bounds the code size)
-template <class F>
-__device__ __noinline__ void xyzz_madd_ool(XYZZ<F>& acc, const Affine<F>& q) {
-  xyzz_madd<F>(acc, q, false);
-}
-template <class F>
-__device__ __noinline__ void xyzz_add_ool(XYZZ<F>& acc, const XYZZ<F>& q) {
-  xyzz_add<F>(acc, q);
-}
-template <class F>
-__device__ __noinline__ void xyzz_dbl_ool(XYZZ<F>& r, const XYZZ<F>& p) {
-  xyzz_dbl<F>(r, p);
-}
-
-// LDS tree sum of one XYZZ per thread; result valid in sh[0] after return (all threads must call)
-template <class F, int BLOCK>
-__device__ void block_tree_sum(XYZZ<F>* sh, const XYZZ<F>& mine) {
-  const int tid = threadIdx.x;
-  sh[tid] = mine;
-  __syncthreads();
-  for (int s = BLOCK / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      XYZZ<F> a = sh[tid];
-      xyzz_add_ool<F>(a, sh[tid + s]);
-      sh[tid] = a;
-    }
-    __syncthreads();
-  }
-}
-
-// one XYZZ per quad of lanes (ec_quad.h): lane q of a quad holds coordinate q (X, Y, ZZ, ZZZ)
-template <class C>
-__device__ __forceinline__ void quad_load(Fp<C>& v, const XYZZ<FpField<C>>* arr, size_t idx) {
-  v = reinterpret_cast<const Fp<C>*>(arr + idx)[threadIdx.x & 3u];
-}
-template <class C>
-__device__ __forceinline__ void quad_store(XYZZ<FpField<C>>* arr, size_t idx, const Fp<C>& v) {
-  reinterpret_cast<Fp<C>*>(arr + idx)[threadIdx.x & 3u] = v;
-}
-template <class C>
-__device__ __forceinline__ void quad_set_inf(Fp<C>& v) {  // (1, 1, 0, 0)
-  Fp<C> one, zero;
-  fp_one<C>(one);
-  fp_zero<C>(zero);
-  fp_select<C>(v, (threadIdx.x & 2u) != 0, zero, one);
-}
-
-// quad g of window w owns buckets [g L, (g+1) L): A = sum B_b, W0 = sum_i i B_{gL+i} (msm_chunk_body's order)
-
-// The same tree for G1 with one point per QUAD of lanes: a group addition is 4 rounds of one field product per lane
-// instead of 14 in a row, so the 8 dependent levels cost ~3x less (the tree is pure latency: one workgroup, one
-// slice).  BLOCK / 4 quads first fold four entries each, then halve.
-template <class C, int BLOCK>
-__device__ void block_tree_sum_q(XYZZ<FpField<C>>* sh, const XYZZ<FpField<C>>& mine) {
-  typedef QuadDevice<C> B;
-  constexpr uint32_t NQ = BLOCK / 4;
-  const uint32_t quad = threadIdx.x >> 2;
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  Fp<C> acc, v;
-  quad_load<C>(acc, sh, quad);
-#pragma unroll 1
-  for (uint32_t j = 1; j < 4; j++) {
-    quad_load<C>(v, sh, quad + j * NQ);
-    quad_xyzz_add<C, B>(acc, v);
-  }
-  __syncthreads();  // every entry has been read
-  quad_store<C>(sh, quad, acc);
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t s = NQ / 2; s > 0; s >>= 1) {
-    if (quad < s) {  // quad-uniform
-      quad_load<C>(v, sh, quad + s);
-      quad_xyzz_add<C, B>(acc, v);
-      quad_store<C>(sh, quad, acc);
-    }
-    __syncthreads();
-  }
-}
-
-// the tree the long-bucket kernels use: quads for G1, one lane per point for G2
-template <class F, int BLOCK>
-__device__ __forceinline__ void block_tree_sum_auto(XYZZ<F>* sh, const XYZZ<F>& mine) {
-  if constexpr (std::is_same<F, FpField<typename F::Curve>>::value)
-    block_tree_sum_q<typename F::Curve, BLOCK>(sh, mine);
-  else
-    block_tree_sum<F, BLOCK>(sh, mine);
-}
-
 
 // ---- long buckets (skewed scalars: small values, equal values, plain sums of points) ---------------------------
 // A bucket above the threshold is cut into slices of BIG_SLICE entries; k_big_slices sums every slice with one
@@ -478,6 +389,49 @@ __global__ void __launch_bounds__(BLOCK) k_accumulate_big_seg(const uint32_t* __
                                                               XYZZ28<C>* __restrict__ state, int flags,
                                                               XYZZ<FpField<C>>* __restrict__ buckets) {
   accumulate_big_body<G1Form28<C>, BLOCK>(big_list, big_count, prefix, partials, state, flags, buckets);
+}
+
+// Bucket accumulation with one bucket per QUAD of lanes, for MSMs too small to fill the chip with one lane per bucket:
+// what such an MSM waits for is the chain of dependent additions of its fullest bucket, and on a quad an addition is four
+// rounds of one product per lane (quad28_xyzz_add; the point enters as (x, +-y, 1, 1)) instead of ten products in a row.
+// Leaves the carry-free bucket state the reduction reads (as k_accumulate28_seg with MLHIP_SEG_KEEP28).
+template <class C>
+__global__ void __launch_bounds__(256) k_accumulate_q28(const Affine28<C>* __restrict__ points,
+                                                        const uint32_t* __restrict__ sorted,
+                                                        const uint32_t* __restrict__ offsets,
+                                                        const uint32_t* __restrict__ counts, size_t n_buckets,
+                                                        uint32_t big_threshold, uint32_t* __restrict__ big_list,
+                                                        uint32_t* __restrict__ big_count, XYZZ28<C>* __restrict__ state) {
+  typedef QuadDevice28<C> B;
+  const size_t g = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+  if (g >= n_buckets) return;  // quad-uniform
+  const unsigned lane = threadIdx.x & 3u;
+  const uint32_t cnt = counts[g];
+  if (cnt > big_threshold) {  // k_big_slices / k_accumulate_big_seg write this bucket's state
+    if (lane == 0) {
+      const uint32_t pos = atomicAdd(big_count, 1u);
+      big_list[pos] = (uint32_t)g;
+    }
+    return;
+  }
+  Fp28<C> acc, one;
+  fp28_zero<C>(acc);
+  fp28_from_const<C>(one, C::ONE28);
+  const size_t begin = offsets[g], end = begin + cnt;
+#pragma unroll 1
+  for (size_t k = begin; k < end; k++) {
+    const uint32_t e = sorted[k];
+    const Fp28<C>* q = reinterpret_cast<const Fp28<C>*>(points + (e & 0x7fffffffu));  // x | y
+    Fp28<C> c = q[lane & 1u], n, b;
+    // the point at infinity is (0, 0): skip it (quad-uniform: lanes 0 and 1 hold x and y)
+    const unsigned z = B::quad_or((fp28_all_zero<C>(c) ? 1u : 0u) << lane);
+    if ((z & 3u) == 3u) continue;
+    fp28_neg<C>(n, c);
+    fp28_select<C>(c, lane == 1 && (e >> 31) != 0, n, c);
+    fp28_select<C>(b, lane >= 2, one, c);
+    quad28_xyzz_add<C, B>(acc, b);
+  }
+  quad28_store<C>(state, g, acc);
 }
 
 }  // namespace mlhip

@@ -203,22 +203,64 @@ MLHIP_HD void msm_accumulate_range(XYZZ<F>& acc, const Affine<F>* points, const 
 }
 
 // ---- bucket reduction, level 1 ---------------------------------------------------------------
-// Thread t of window w owns buckets [t*L, (t+1)*L): A = sum B_b ; W0 = sum_i i * B_{tL+i}.
-// `add(acc, q)` is the group addition to use: the kernels pass an out-of-line copy (one ~90 KB body per
-// kernel instead of three inlined ones), the host test passes xyzz_add itself.
+// Chunk g of window w owns buckets [g L, (g + 1) L): A = sum_i b[i], W0 = sum_i i b[i], as a running sum from the top
+// bucket down (acc += b[i]; w0 += acc; the last acc += b[0] adds nothing to w0).  Written once, over a reduction form R
+// (msm_reduce.h: "reduction forms"), which is the only place that knows how a point is kept, and the group addition
+// `add(acc, q)`: the kernels pass their form's (FormAdd), the host test the host backends of the quad and lane-pair
+// additions.  R::CHUNK_PREFETCH: the next bucket is loaded under the additions of this one (a second value stays live).
+template <class R, class AddFn>
+MLHIP_HD void reduce_chunk_body(size_t g, const typename R::Mem* buckets, typename R::Mem* A, typename R::Mem* W0, int l_eff,
+                                AddFn add) {
+  const typename R::Mem* b = buckets + R::MEMS * g * (size_t)l_eff;
+  typename R::V acc, w0, cur;
+  R::set_empty(acc);
+  R::set_empty(w0);
+  if constexpr (R::CHUNK_PREFETCH) R::load(cur, b, l_eff - 1);
+#pragma unroll 1
+  for (int i = l_eff - 1; i >= 0; i--) {
+    [[maybe_unused]] typename R::V nxt;  // (the prefetched bucket: not used without CHUNK_PREFETCH)
+    if constexpr (R::CHUNK_PREFETCH) {
+      nxt = cur;
+      if (i > 0) R::load(nxt, b, i - 1);
+    } else {
+      R::load(cur, b, i);
+    }
+    add(acc, cur);
+    if (i > 0) add(w0, acc);
+    if constexpr (R::CHUNK_PREFETCH) cur = nxt;
+  }
+  R::store(A, g, acc);
+  R::store(W0, g, w0);
+}
+
+// The same with one point per lane in the boundary form and the addition passed in: the ordering every form's chunk sums
+// reproduce, which the host test drives with xyzz_add itself.
+template <class F>
+struct ChunkLaneForm {
+  static constexpr bool CHUNK_PREFETCH = false;
+  static constexpr int MEMS = 1;
+  typedef XYZZ<F> Mem, V;
+  MLHIP_HD static void set_empty(V& v) { xyzz_set_inf<F>(v); }
+  MLHIP_HD static void load(V& v, const Mem* arr, size_t i) { v = arr[i]; }
+  MLHIP_HD static void store(Mem* arr, size_t i, const V& v) { arr[i] = v; }
+};
 template <class F, class AddFn>
 MLHIP_HD void msm_chunk_body(size_t g, const XYZZ<F>* buckets, XYZZ<F>* A, XYZZ<F>* W0, int l_eff, AddFn add) {
-  const XYZZ<F>* b = buckets + g * (size_t)l_eff;
-  XYZZ<F> acc, w0;
-  xyzz_set_inf<F>(acc);
-  xyzz_set_inf<F>(w0);
-  for (int i = l_eff - 1; i >= 1; i--) {
-    add(acc, b[i]);
-    add(w0, acc);
-  }
-  add(acc, b[0]);
-  A[g] = acc;
-  W0[g] = w0;
+  reduce_chunk_body<ChunkLaneForm<F>>(g, buckets, A, W0, l_eff, add);
+}
+
+// ---- bucket reduction, level 2: which chunk sums make up the nsel = 4 + log2 T sums of a window ------------------------
+// List sel of a window with T chunks (T a power of two): sel 0, 1 -> the two halves of sum_t W0[t]; sel 2, 3 -> the two
+// halves of sum_t A[t] (split at (T + 1) / 2); sel 4 + k -> the A[t] with bit k of t set.  Every list of T >= 2 has T / 2
+// elements (equal depth); at T = 1 the second halves are empty.  reduce_sel_index: element j of list sel -> t.
+MLHIP_HD uint32_t reduce_sel_count(int sel, uint32_t T) {
+  const uint32_t half = (T + 1) / 2;
+  return sel >= 4 ? T / 2 : (sel & 1) ? T - half : half;
+}
+MLHIP_HD uint32_t reduce_sel_index(int sel, uint32_t j, uint32_t T) {
+  const int k = sel < 4 ? 0 : sel - 4;
+  const uint32_t lo = (sel & 1) ? (T + 1) / 2 : 0u;
+  return sel < 4 ? lo + j : (((j >> k) << (k + 1)) | (1u << k) | (j & ((1u << k) - 1u)));
 }
 
 // ---- host tail of one window (msm_plan.h: host_tail; here so that the host-math test library can run it) ------------

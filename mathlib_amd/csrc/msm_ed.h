@@ -2,7 +2,7 @@
 // the prime-order subgroup (mlhip_msm_plan_assume_srs; curves with C::HAS_EDWARDS: BLS12-377).  Part of msm_kernels.h.
 // EdForm28 is the bucket form; its kernels are the shared bodies of msm_accumulate.h on it: same entry lists, same state
 // buffer (an EdExt28 has the footprint of an XYZZ28).  The buckets STAY in extended Edwards coordinates: the quad-lane
-// reduction kernels run their Edwards instantiation on them (msm_reduce.h: k_chunks_q28<C, true>, ed_quad28_add) and
+// reduction kernels run their Edwards instantiation on them (msm_reduce.h: Quad28Form<C, true>, ed_quad28_add) and
 // only the W x nsel window sums return to the Weierstrass curve, for the host tail.
 #pragma once
 // (included by msm_kernels.h after msm_accumulate.h)

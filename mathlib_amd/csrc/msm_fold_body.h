@@ -1,4 +1,4 @@
-// msm_fold_body.h -- per-thread bodies of the shifted-base-table kernels (msm_fold.h, msm_reduce.h: k_group_combine_q),
+// msm_fold_body.h -- per-thread bodies of the shifted-base-table kernels (msm_fold.h, msm_reduce.h: group_combine_body),
 // shared with the host-side emulation of tests/test_host_math.py (hm_fold_msm), like msm_body.h.
 #pragma once
 #include "ec_jac.h"
@@ -48,7 +48,7 @@ MLHIP_HD void fold_rows_body(const Affine<F>& P, int fr_bits, int c, size_t stri
   }
 }
 
-// k_group_combine_q: which of group g's nsel sums (two halves of sum W0, two halves of sum A, nb bit-masked sums of A) goes
+// group_combine_body: which of group g's nsel sums (two halves of sum W0, two halves of sum A, nb bit-masked sums of A) goes
 // into output o of the combined window -- slot (g, h), h = 0 / 1 -- or -1 for none.  Outputs: 0 = sum W0, 1 = sum A, 2 and 3
 // empty, 4 + k = B_k, the sum of the A[t'] with bit k of the global chunk index t' = g T + t set: bits below nb are bits of t
 // (group g's own masked sum, slot h = 0), bits from nb on are bits of g (group g's plain sum, both halves).

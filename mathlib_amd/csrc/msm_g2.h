@@ -1,6 +1,7 @@
 // msm_g2.h -- G2 over lane pairs: the boundary-form accumulation and slices (second implementation; slices of plain plans),
 // the two carry-free bucket forms (G2Form28, G2KcForm28) with their kernels over the shared bodies of msm_accumulate.h, and
-// the bucket reduction.  Part of msm_kernels.h.
+// the two reduction forms (PairForm, Pair28Form) with their kernels over the shared bodies of msm_reduce.h.  Part of
+// msm_kernels.h.
 #pragma once
 // (included by msm_kernels.h after its common headers and constants)
 
@@ -54,6 +55,32 @@ __device__ __forceinline__ void lp_store_xyzz(XYZZ<Fp2Field<C>>* dst, size_t idx
 template <class C>
 __device__ __noinline__ void xyzz_add_lp_ool(XYZZ<Fp2LField<C>>& acc, const XYZZ<Fp2LField<C>>& q) {
   xyzz_add<Fp2LField<C>>(acc, q);
+}
+
+// ---- the G2 reduction forms (see "reduction forms", msm_reduce.h) ------------------------------------------------------
+// PairForm: one point per lane pair in the boundary form -- the test build's reduction (MLHIP_REDUCE32 / MLHIP_ACC32), the
+// combine of folded plans and the tree of the long buckets.
+template <class C>
+struct PairForm {
+  static constexpr int LANES = 2;
+  static constexpr bool CHUNK_PREFETCH = false, TREE_HAND_OVER = true;
+  typedef Fp2Field<C> BF;
+  typedef XYZZ<BF> Mem;
+  typedef XYZZ<Fp2LField<C>> V;
+  static __device__ __forceinline__ int hi() { return lane_is_hi() ? 1 : 0; }
+  static constexpr int MEMS = 1;
+  static __device__ __forceinline__ void set_empty(V& v) { xyzz_set_inf<Fp2LField<C>>(v); }
+  static __device__ __forceinline__ void load(V& v, const Mem* arr, size_t i) { lp_load_xyzz<C>(v, arr, i, hi()); }
+  static __device__ __forceinline__ void store(Mem* arr, size_t i, const V& v) { lp_store_xyzz<C>(arr, i, v, hi()); }
+  static __device__ __forceinline__ void add(V& a, const V& b) { xyzz_add_lp_ool<C>(a, b); }
+  static __device__ __forceinline__ void store_out(XYZZ<BF>* out, size_t i, const V& v) { store(out, i, v); }
+};
+
+// LDS tree over the BLOCK / 2 lane pairs of a workgroup, in the boundary form; the sum is left in sh[0]
+template <class C, int BLOCK>
+__device__ __forceinline__ void block_tree_sum_lp(XYZZ<Fp2Field<C>>* sh, const XYZZ<Fp2LField<C>>& mine) {
+  XYZZ<Fp2LField<C>> acc = mine;
+  group_tree_sum<PairForm<C>>(sh, acc, threadIdx.x >> 1, BLOCK / 2);
 }
 
 template <class C>
@@ -140,7 +167,7 @@ __global__ void __launch_bounds__(BLOCK) k_big_slices_lp(const Affine<Fp2Field<C
     const size_t first = offsets[g], last = first + counts[g];
     const size_t begin = first + (size_t)(sid - prefix[bi]) * BIG_SLICE;
     const size_t end = begin + BIG_SLICE < last ? begin + BIG_SLICE : last;
-    XYZZ<FL> acc, b;
+    XYZZ<FL> acc;
     xyzz_set_inf<FL>(acc);
     for (size_t k = begin + pid; k < end; k += PAIRS) {  // pair-uniform bounds
       const uint32_t e = sorted[k];
@@ -148,18 +175,7 @@ __global__ void __launch_bounds__(BLOCK) k_big_slices_lp(const Affine<Fp2Field<C
       lp_load_affine<C>(q, points, e & 0x7fffffffu, hi);
       xyzz_madd<FL>(acc, q, (e >> 31) != 0);
     }
-    lp_store_xyzz<C>(sh, pid, acc, hi);
-    __syncthreads();
-    for (uint32_t s2 = PAIRS / 2; s2 > 0; s2 >>= 1) {
-      if (pid < s2) {  // pair-uniform
-        XYZZ<FL> a;
-        lp_load_xyzz<C>(a, sh, pid, hi);
-        lp_load_xyzz<C>(b, sh, pid + s2, hi);
-        xyzz_add_lp_ool<C>(a, b);
-        lp_store_xyzz<C>(sh, pid, a, hi);
-      }
-      __syncthreads();
-    }
+    block_tree_sum_lp<C, BLOCK>(sh, acc);
     if (pid == 0) {
       XYZZ<FL> a;
       lp_load_xyzz<C>(a, sh, 0, hi);
@@ -189,35 +205,12 @@ __global__ void __launch_bounds__(256) k_points_to28_g2(const Affine<Fp2Field<C>
 
 // a bucket's carry-free state: two XYZZ28L, one per lane; ZZ = 0 limbs in both for the point at infinity
 template <class C>
-__device__ __forceinline__ bool lp28_load_state(XYZZ28L<Fp28<C>>& r, const XYZZ28L<Fp28<C>>* src, size_t idx, int hi) {
-  r = src[2 * idx + hi];
-  return lp28_all_zero<C, PairDevice<C>>(r.zz);  // infinity
-}
-template <class C>
 __device__ __forceinline__ void lp28_store_state(XYZZ28L<Fp28<C>>* dst, size_t idx, XYZZ28L<Fp28<C>> r, bool inf, int hi) {
   if (inf) {
 #pragma unroll
     for (int i = 0; i < C::N28; i++) r.x.l[i] = r.y.l[i] = r.zz.l[i] = r.zzz.l[i] = 0;
   }
   dst[2 * idx + hi] = r;
-}
-
-// LDS tree over the BLOCK / 2 lane pairs of a workgroup, in the boundary form; the sum is left in sh[0]
-template <class C, int BLOCK>
-__device__ __forceinline__ void block_tree_sum_lp(XYZZ<Fp2Field<C>>* sh, const XYZZ<Fp2LField<C>>& mine, int hi) {
-  const uint32_t pid = threadIdx.x >> 1;
-  lp_store_xyzz<C>(sh, pid, mine, hi);
-  __syncthreads();
-  for (uint32_t s = BLOCK / 4; s > 0; s >>= 1) {
-    if (pid < s) {  // pair-uniform
-      XYZZ<Fp2LField<C>> a, b;
-      lp_load_xyzz<C>(a, sh, pid, hi);
-      lp_load_xyzz<C>(b, sh, pid + s, hi);
-      xyzz_add_lp_ool<C>(a, b);
-      lp_store_xyzz<C>(sh, pid, a, hi);
-    }
-    __syncthreads();
-  }
 }
 
 // ---- the G2 bucket forms (see "bucket forms", msm_accumulate.h) ---------------------------------------------------------
@@ -267,8 +260,8 @@ struct G2Form28 {
     lp_store_xyzz<C>(dst, i, r, hi);
   }
   template <int BLOCK>
-  static __device__ __forceinline__ void block_sum(XYZZ<BF>* sh, const LaneB& mine, int hi) {
-    block_tree_sum_lp<C, BLOCK>(sh, mine, hi);
+  static __device__ __forceinline__ void block_sum(XYZZ<BF>* sh, const LaneB& mine, int) {
+    block_tree_sum_lp<C, BLOCK>(sh, mine);
   }
   // whole buckets on one thread, for the combine: both lanes' halves
   static __device__ __forceinline__ bool state_to_boundary(XYZZ<BF>& r, const State* state, size_t g) {
@@ -419,119 +412,71 @@ __global__ void __launch_bounds__(BLOCK) k_big_slices_lp28(const AffineG2_28<C>*
   big_slices_body<G2Form28<C>, BLOCK>(points, sorted, offsets, counts, big_list, big_count, prefix, partials);
 }
 
-template <class C>
-__global__ void __launch_bounds__(256) k_chunks_lp(const XYZZ<Fp2Field<C>>* __restrict__ buckets, size_t n_chunks, int l_eff,
-                                                   XYZZ<Fp2Field<C>>* __restrict__ A, XYZZ<Fp2Field<C>>* __restrict__ W0) {
-  typedef Fp2LField<C> FL;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t g = t >> 1;
-  if (g >= n_chunks) return;
-  const int hi = lane_is_hi() ? 1 : 0;
-  XYZZ<FL> acc, w0, b;
-  xyzz_set_inf<FL>(acc);
-  xyzz_set_inf<FL>(w0);
-  for (int i = l_eff - 1; i >= 1; i--) {
-    lp_load_xyzz<C>(b, buckets, g * (size_t)l_eff + i, hi);
-    xyzz_add_lp_ool<C>(acc, b);
-    xyzz_add_lp_ool<C>(w0, acc);
-  }
-  lp_load_xyzz<C>(b, buckets, g * (size_t)l_eff, hi);
-  xyzz_add_lp_ool<C>(acc, b);
-  lp_store_xyzz<C>(A, g, acc, hi);
-  lp_store_xyzz<C>(W0, g, w0, hi);
-}
-
-// same selection scheme as k_masked_sums; BLOCK threads = BLOCK/2 lane pairs, LDS tree over pairs
-template <class C, int BLOCK>
-__global__ void __launch_bounds__(BLOCK) k_masked_sums_lp(const XYZZ<Fp2Field<C>>* __restrict__ A,
-                                                          const XYZZ<Fp2Field<C>>* __restrict__ W0, uint32_t T, int nsel,
-                                                          XYZZ<Fp2Field<C>>* __restrict__ out) {
-  typedef Fp2LField<C> FL;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<Fp2Field<C>>* sh = reinterpret_cast<XYZZ<Fp2Field<C>>*>(smem);
-  constexpr uint32_t PAIRS = BLOCK / 2;
-  const uint32_t pid = threadIdx.x >> 1;
-  const int hi = lane_is_hi() ? 1 : 0;
-  const uint32_t w = blockIdx.x / nsel;
-  const int sel = blockIdx.x % nsel;
-  const XYZZ<Fp2Field<C>>* src = (sel < 2 ? W0 : A) + (size_t)w * T;
-  XYZZ<FL> acc, b;
-  xyzz_set_inf<FL>(acc);
-  if (sel < 4) {
-    const uint32_t half = (T + 1) / 2;
-    const uint32_t lo = (sel & 1) ? half : 0u, hi_t = (sel & 1) ? T : half;
-    for (uint32_t t = lo + pid; t < hi_t; t += PAIRS) {
-      lp_load_xyzz<C>(b, src, t, hi);
-      xyzz_add_lp_ool<C>(acc, b);
-    }
-  } else {
-    const int k = sel - 4;
-    const uint32_t lowmask = (1u << k) - 1u;
-    for (uint32_t j = pid; j < T / 2; j += PAIRS) {
-      uint32_t t = ((j >> k) << (k + 1)) | (1u << k) | (j & lowmask);
-      lp_load_xyzz<C>(b, src, t, hi);
-      xyzz_add_lp_ool<C>(acc, b);
-    }
-  }
-  // the upper half of the pairs hands its sums to the lower half first, so the tree needs PAIRS / 2 slots only (48 KB for
-  // 512 threads: twice the pairs per block, half the strided additions per pair, one more tree level)
-  if (pid >= PAIRS / 2) lp_store_xyzz<C>(sh, pid - PAIRS / 2, acc, hi);
-  __syncthreads();
-  if (pid < PAIRS / 2) {
-    lp_load_xyzz<C>(b, sh, pid, hi);
-    xyzz_add_lp_ool<C>(acc, b);
-  }
-  __syncthreads();
-  if (pid < PAIRS / 2) lp_store_xyzz<C>(sh, pid, acc, hi);
-  __syncthreads();
-  for (uint32_t s = PAIRS / 4; s > 0; s >>= 1) {
-    if (pid < s) {  // pair-uniform
-      XYZZ<FL> a;
-      lp_load_xyzz<C>(a, sh, pid, hi);
-      lp_load_xyzz<C>(b, sh, pid + s, hi);
-      xyzz_add_lp_ool<C>(a, b);
-      lp_store_xyzz<C>(sh, pid, a, hi);
-    }
-    __syncthreads();
-  }
-  if (pid == 0) lp_store_xyzz<C>(out, blockIdx.x, [&] { XYZZ<FL> a; lp_load_xyzz<C>(a, sh, 0, hi); return a; }(), hi);
-}
-
-// ---- the G2 reduction on the carry-free bucket state (BLS12-381; ec28_lp.h: xyzz28_lp_add) -----------------------------
-// As k_chunks_q28 / k_masked_sums_q28 for G1: the buckets come as the accumulation kernel keeps them (two XYZZ28L per
-// bucket, one per lane; ZZ = 0 limbs in both for an empty bucket), the chunk sums stay in that form, the W x nsel sums that
-// travel to the host leave in the boundary form.
+// ---- the G2 reduction ------------------------------------------------------------------------------------------------
+// Pair28Form: lane pairs on the carry-free bucket state (ec28_lp.h: xyzz28_lp_add), as Quad28Form for G1 -- the buckets come
+// as the accumulation kernel keeps them (two XYZZ28L per bucket, one per lane; ZZ = 0 limbs in both for an empty bucket),
+// the chunk sums stay in that form, the W x nsel sums that travel to the host leave in the boundary form.  The lane's value,
+// its loads, stores and conversion are G2Form28's.  No prefetch in the chunk loop: k_chunks_lp28 sits at 256 VGPRs.
 template <class C>
 __device__ __noinline__ void xyzz28_lp_add_ool(XYZZ28L<Fp28<C>>& acc, bool& inf, const XYZZ28L<Fp28<C>>& q, bool q_inf) {
   xyzz28_lp_add<C, PairDevice<C>>(acc, inf, q, q_inf);
 }
 template <class C>
-__global__ void __launch_bounds__(256) k_chunks_lp28(const XYZZ28L<Fp28<C>>* __restrict__ buckets, size_t n_chunks, int l_eff,
-                                                     XYZZ28L<Fp28<C>>* __restrict__ A, XYZZ28L<Fp28<C>>* __restrict__ W0) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t g = t >> 1;
-  if (g >= n_chunks) return;
-  const int hi = (int)(threadIdx.x & 1u);
-  XYZZ28L<Fp28<C>> acc, w0, b;
-  bool acc_inf = true, w0_inf = true;
-  for (int i = l_eff - 1; i >= 1; i--) {
-    const bool b_inf = lp28_load_state<C>(b, buckets, g * (size_t)l_eff + i, hi);
-    xyzz28_lp_add_ool<C>(acc, acc_inf, b, b_inf);
-    xyzz28_lp_add_ool<C>(w0, w0_inf, acc, acc_inf);
+struct Pair28Form {
+  typedef G2Form28<C> Fm;
+  static constexpr int LANES = 2;
+  static constexpr bool CHUNK_PREFETCH = false, TREE_HAND_OVER = true;
+  typedef Fp2Field<C> BF;
+  typedef XYZZ28L<Fp28<C>> Mem;  // (two per point: MEMS)
+  typedef typename Fm::Acc V;
+  static __device__ __forceinline__ int hi() { return (int)(threadIdx.x & 1u); }
+  static constexpr int MEMS = 2;
+  static __device__ __forceinline__ void set_empty(V& v) { Fm::set_identity(v); }
+  static __device__ __forceinline__ void load(V& v, const Mem* arr, size_t i) { Fm::load_state(v, arr, i, hi()); }
+  static __device__ __forceinline__ void store(Mem* arr, size_t i, const V& v) { Fm::store_state(arr, i, v, hi()); }
+  static __device__ __forceinline__ void add(V& a, const V& b) { xyzz28_lp_add_ool<C>(a.p, a.inf, b.p, b.inf); }
+  static __device__ __forceinline__ void store_out(XYZZ<BF>* out, size_t i, const V& v) {
+    typename Fm::LaneB r;
+    Fm::to_boundary(r, v);
+    Fm::store_lane(out, i, r, hi());
   }
-  const bool b_inf = lp28_load_state<C>(b, buckets, g * (size_t)l_eff, hi);
-  xyzz28_lp_add_ool<C>(acc, acc_inf, b, b_inf);
-  lp28_store_state<C>(A, g, acc, acc_inf, hi);
-  lp28_store_state<C>(W0, g, w0, w0_inf, hi);
+};
+
+// boundary form (MLHIP_REDUCE32 / MLHIP_ACC32, test build)
+template <class C>
+__global__ void __launch_bounds__(256) k_chunks_lp(const XYZZ<Fp2Field<C>>* __restrict__ buckets, size_t n_chunks, int l_eff,
+                                                   XYZZ<Fp2Field<C>>* __restrict__ A, XYZZ<Fp2Field<C>>* __restrict__ W0) {
+  reduce_chunks_body<PairForm<C>>(buckets, n_chunks, l_eff, A, W0);
+}
+template <class C, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) k_masked_sums_lp(const XYZZ<Fp2Field<C>>* __restrict__ A,
+                                                          const XYZZ<Fp2Field<C>>* __restrict__ W0, uint32_t T, int nsel,
+                                                          XYZZ<Fp2Field<C>>* __restrict__ out) {
+  reduce_masked_body<PairForm<C>, BLOCK>(A, W0, T, nsel, out);
 }
 
+// carry-free form: the G2 reduction
+template <class C>
+__global__ void __launch_bounds__(256) k_chunks_lp28(const XYZZ28L<Fp28<C>>* __restrict__ buckets, size_t n_chunks, int l_eff,
+                                                     XYZZ28L<Fp28<C>>* __restrict__ A, XYZZ28L<Fp28<C>>* __restrict__ W0) {
+  reduce_chunks_body<Pair28Form<C>>(buckets, n_chunks, l_eff, A, W0);
+}
+// Written out, not over reduce_masked_body: with the lane's value as Pair28Form::V (state and flag in one struct, handed to
+// the out-of-line addition by reference) the kernel needed 16 B more scratch per lane on the 14-limb curves than with the
+// loose states and flags below.  Same lists (reduce_sel_index), same tree schedule (the upper half of the pairs hands its
+// sums to the lower half, then PAIRS / 2 slots of two lane entries), same exit as Pair28Form::store_out.
+template <class C>
+__device__ __forceinline__ bool lp28_load_state(XYZZ28L<Fp28<C>>& r, const XYZZ28L<Fp28<C>>* src, size_t idx, int hi) {
+  r = src[2 * idx + hi];
+  return lp28_all_zero<C, PairDevice<C>>(r.zz);  // infinity
+}
 template <class C, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_masked_sums_lp28(const XYZZ28L<Fp28<C>>* __restrict__ A,
                                                             const XYZZ28L<Fp28<C>>* __restrict__ W0, uint32_t T, int nsel,
                                                             XYZZ<Fp2Field<C>>* __restrict__ out) {
   typedef XYZZ28L<Fp28<C>> X;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  X* sh = reinterpret_cast<X*>(smem);  // PAIRS / 2 slots of two lane entries
+  X* sh = reinterpret_cast<X*>(smem);
   constexpr uint32_t PAIRS = BLOCK / 2;
   const uint32_t pid = threadIdx.x >> 1;
   const int hi = (int)(threadIdx.x & 1u);
@@ -540,23 +485,11 @@ __global__ void __launch_bounds__(BLOCK) k_masked_sums_lp28(const XYZZ28L<Fp28<C
   const X* src = (sel < 2 ? W0 : A) + (size_t)2 * w * T;
   X acc, b;
   bool inf = true;
-  if (sel < 4) {
-    const uint32_t half = (T + 1) / 2;
-    const uint32_t lo = (sel & 1) ? half : 0u, hi_t = (sel & 1) ? T : half;
-    for (uint32_t t = lo + pid; t < hi_t; t += PAIRS) {
-      const bool b_inf = lp28_load_state<C>(b, src, t, hi);
-      xyzz28_lp_add_ool<C>(acc, inf, b, b_inf);
-    }
-  } else {
-    const int k = sel - 4;
-    const uint32_t lowmask = (1u << k) - 1u;
-    for (uint32_t j = pid; j < T / 2; j += PAIRS) {
-      const uint32_t t = ((j >> k) << (k + 1)) | (1u << k) | (j & lowmask);
-      const bool b_inf = lp28_load_state<C>(b, src, t, hi);
-      xyzz28_lp_add_ool<C>(acc, inf, b, b_inf);
-    }
+  const uint32_t count = reduce_sel_count(sel, T);
+  for (uint32_t j = pid; j < count; j += PAIRS) {
+    const bool b_inf = lp28_load_state<C>(b, src, reduce_sel_index(sel, j, T), hi);
+    xyzz28_lp_add_ool<C>(acc, inf, b, b_inf);
   }
-  // the upper half of the pairs hands its sums to the lower half, then a tree over PAIRS / 2 slots
   if (pid >= PAIRS / 2) lp28_store_state<C>(sh, pid - PAIRS / 2, acc, inf, hi);
   __syncthreads();
   if (pid < PAIRS / 2) {
@@ -575,53 +508,16 @@ __global__ void __launch_bounds__(BLOCK) k_masked_sums_lp28(const XYZZ28L<Fp28<C
     __syncthreads();
   }
   if (pid == 0) {
-    XYZZ<Fp2LField<C>> r;
-    if (inf) {
-      xyzz_set_inf<Fp2LField<C>>(r);
-    } else {
-      fp28_to_fp<C>(r.x.v, acc.x);
-      fp28_to_fp<C>(r.y.v, acc.y);
-      fp28_to_fp<C>(r.zz.v, acc.zz);
-      fp28_to_fp<C>(r.zzz.v, acc.zzz);
-    }
-    lp_store_xyzz<C>(out, blockIdx.x, r, hi);
+    typename G2Form28<C>::Acc r{acc, inf};
+    Pair28Form<C>::store_out(out, blockIdx.x, r);
   }
 }
 
-// ---- folded plans (msm_fold.h): the W bucket groups' sums combined into one window's, on lane pairs -----------------
-// k_group_combine_q (msm_reduce.h) for G2: one block per output of the combined window, one lane PAIR per input slot
-// (group g, half h; fold_combine_src), an LDS tree of lane-pair additions in the boundary form.  Launched with 4 W threads.
-// Host tail of a 2^20-point G2 MSM over shifted-base tables: 0.30 ms (2 W jobs on the host pool, 3 W additions) -> one
-// window's 19 doublings on the calling thread.
+// the combine of a folded G2 plan (msm_reduce.h: group_combine_body), in the boundary form; launched with 4 W threads
 template <class C, int BLOCK>
 __global__ void __launch_bounds__(BLOCK) k_group_combine_lp(const XYZZ<Fp2Field<C>>* __restrict__ in, int W, int nsel, int nb,
                                                             XYZZ<Fp2Field<C>>* __restrict__ out) {
-  typedef Fp2LField<C> FL;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  XYZZ<Fp2Field<C>>* sh = reinterpret_cast<XYZZ<Fp2Field<C>>*>(smem);
-  const uint32_t pid = threadIdx.x >> 1;
-  const int hi = lane_is_hi() ? 1 : 0;
-  const int o = blockIdx.x;
-  const uint32_t NP = 2u * (uint32_t)W;
-  XYZZ<FL> acc, b;
-  xyzz_set_inf<FL>(acc);
-  if (pid < NP) {  // pair-uniform
-    const int g = (int)(pid >> 1);
-    const int src = fold_combine_src(o, g, (int)(pid & 1u), nb);
-    if (src >= 0) lp_load_xyzz<C>(acc, in, (size_t)g * nsel + src, hi);
-  }
-  lp_store_xyzz<C>(sh, pid, acc, hi);
-  __syncthreads();
-#pragma unroll 1
-  for (uint32_t s = NP / 2; s > 0; s >>= 1) {
-    if (pid < s) {  // pair-uniform
-      lp_load_xyzz<C>(b, sh, pid + s, hi);
-      xyzz_add_lp_ool<C>(acc, b);
-      lp_store_xyzz<C>(sh, pid, acc, hi);
-    }
-    __syncthreads();
-  }
-  if (pid == 0) lp_store_xyzz<C>(out, (size_t)o, acc, hi);
+  group_combine_body<PairForm<C>>(in, W, nsel, nb, out);
 }
 
 }  // namespace mlhip

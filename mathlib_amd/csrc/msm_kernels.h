@@ -19,10 +19,20 @@
 //   k_accumulate / k_accumulate_lp / k_big_slices / k_big_slices_lp   the same on 32-bit Montgomery limbs, written out by
 //                 themselves: the second implementation the parity tests compare with (MLHIP_ACC32, test build); the
 //                 slices also serve plain plans, whose long buckets gather the caller's boundary-form points
-//   k_accumulate_q28   one bucket per quad of lanes for MSMs with few buckets (msm_reduce.h)
-//   k_chunks_q / k_masked_sums_q   G1 bucket reduction, one point per quad of lanes (ec_quad.h): per 16 consecutive
-//                 buckets sum and locally weighted sum, then per window the plain / bit-masked sums of the chunk sums
-//                 (k_chunks / k_masked_sums: one lane per point; *_lp: G2 lane pairs)
+//   k_accumulate_q28   one bucket per quad of lanes for MSMs with few buckets (msm_accumulate.h)
+//   bucket reduction: three levels and the LDS tree over a workgroup's lane groups, each written once over a reduction
+//                 form (msm_reduce.h: "reduction forms") -- reduce_chunks_body: per 16 consecutive buckets sum and locally
+//                 weighted sum; reduce_masked_body: per window the half / bit-masked sums of the chunk sums
+//                 (msm_body.h: reduce_sel_index); group_combine_body: the groups of a folded plan into one window;
+//                 group_tree_sum.  Forms and their kernels:
+//     Quad28Form  k_chunks_q28 / k_masked_sums_q28 (<.., true>: Edwards)   G1, one point per quad of lanes on the
+//                 accumulation's carry-free bucket state (ec_quad28.h)
+//     Pair28Form  k_chunks_lp28   G2, lane pairs on the carry-free state (ec28_lp.h); k_masked_sums_lp28 is written out
+//                 beside it (msm_g2.h: on the shared body it needed more scratch), as is the quad tree of the long G1
+//                 buckets, block_tree_sum_q (msm_reduce.h)
+//     QuadForm / PairForm   k_group_combine_q / _lp and the trees of the long buckets, in the boundary form; with
+//                 k_chunks_q / k_masked_sums_q / k_chunks_lp / k_masked_sums_lp the test build's MLHIP_REDUCE32
+//     LaneForm    k_chunks / k_masked_sums   one lane per point (MLHIP_REDUCE_ONE_LANE, test build)
 //   k_msm_batch_chunk / k_msm_batch_sum (+ _lp for G2)   many small MSMs per call: Straus chunks of <= P pairs per lane,
 //                 then segmented sums of <= 32 partials per lane (msm_batch.h)
 //   k_msm_bucket_digits / k_msm_bucket_accumulate / k_msm_bucket_combine   the segments of such a call that are long enough
@@ -76,9 +86,9 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 }  // namespace mlhip
 
 #include "msm_sort.h"
+#include "msm_reduce.h"
 #include "msm_accumulate.h"
 #include "msm_ed.h"
-#include "msm_reduce.h"
 #include "msm_g2.h"
 #include "msm_scalar_mul_endo.h"
 #include "msm_scalar_mul.h"

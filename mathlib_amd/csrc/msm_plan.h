@@ -150,7 +150,7 @@ int plan_alloc(mlhip_msm_plan* p) {
     HIPCHK(hipMalloc(&p->d_A, (size_t)p->W * p->T * chunk_size));
     HIPCHK(hipMalloc(&p->d_W0, (size_t)p->W * p->T * chunk_size));
   }
-  if (p->fold && p->W > 1 && p->W <= 32 && p->reduce28) {  // (G1: k_group_combine_q on quads; G2: k_group_combine_lp on lane pairs)
+  if (p->fold && p->W > 1 && p->W <= 32 && p->reduce28) {  // (group_combine_body: G1 on quads, G2 on lane pairs)
     int lgW = 0;
     while ((1 << lgW) < p->W) lgW++;
     p->fold_nsel2 = 4 + p->nb + lgW;
@@ -199,7 +199,7 @@ void host_tail_group(const void* in, int job, void* out) {
 template <class F>
 void host_tail_fold(const mlhip_msm_plan* p, XYZZ<F>& total) {
   if (p->fold_nsel2) {
-    // the device has combined the groups (k_group_combine_q): one window of W T chunks, summed on this thread
+    // the device has combined the groups (group_combine_body): one window of W T chunks, summed on this thread
     const size_t sums2 = (size_t)p->fold_nsel2 * sizeof(XYZZ<F>);
     std::vector<unsigned char> blob2(sizeof(HostTailHeader) + sums2);
     const HostTailHeader h2{p->fold_nsel2 - 4, p->lgL, p->fold_nsel2, 0};
@@ -369,74 +369,81 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
   return 0;
 }
 
-// bucket sums in d_buckets -> W x nsel partial sums in d_out (two levels: chunks of L buckets, bit-masked sums)
+// LDS of a masked-sum block of RB threads: one slot per lane group, half of that where the form's tree hands over first
+template <class R, int RB>
+constexpr size_t reduce_masked_lds() {
+  return (size_t)(RB / R::LANES / (R::TREE_HAND_OVER ? 2 : 1)) * R::MEMS * sizeof(typename R::Mem);
+}
+
+// One path of the reduction over the form R: chunk sums, masked sums (RB threads a block) and, for a folded plan, the
+// combine of the groups' sums into one window's (`combine` null: the path has none).  MLHIP_RED_BLOCK sizes the chunk
+// blocks of the quad kernels.
+template <class R, int RB>
+void launch_reduce_kernels(mlhip_msm_plan* p, hipStream_t st, const void* buckets,
+                           void (*chunks)(const typename R::Mem*, size_t, int, typename R::Mem*, typename R::Mem*),
+                           void (*masked)(const typename R::Mem*, const typename R::Mem*, uint32_t, int, XYZZ<typename R::BF>*),
+                           void (*combine)(const XYZZ<typename R::BF>*, int, int, int, XYZZ<typename R::BF>*),
+                           unsigned combine_threads, size_t combine_lds) {
+  typedef typename R::Mem Mem;
+  typedef XYZZ<typename R::BF> X;
+  const size_t n_chunks = (size_t)p->W * p->T;
+  const unsigned cb = R::LANES == 4 ? (unsigned)p->red_block : 256u;
+  chunks<<<dim3((unsigned)((R::LANES * n_chunks + cb - 1) / cb)), dim3(cb), 0, st>>>((const Mem*)buckets, n_chunks, p->L,
+                                                                                     (Mem*)p->d_A, (Mem*)p->d_W0);
+  masked<<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), reduce_masked_lds<R, RB>(), st>>>(
+      (const Mem*)p->d_A, (const Mem*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
+  if (combine && p->fold_nsel2)
+    combine<<<dim3((unsigned)p->fold_nsel2), dim3(combine_threads), combine_lds, st>>>(
+        (const X*)p->d_out, p->W, p->nsel, p->nb, (X*)p->d_out + (size_t)p->W * p->nsel);
+}
+
+// bucket sums in d_buckets (boundary form) or d_state28 (the accumulation's carry-free state, MLHIP_SEG_KEEP28) -> W x nsel
+// partial sums in d_out (two levels: chunks of L buckets, bit-masked sums): picks the reduction form (msm_reduce.h)
 template <class C, class F>
 int launch_reduce(mlhip_msm_plan* p, hipStream_t st) {
   typedef XYZZ<F> X;
-  constexpr bool kLanePairs = std::is_same<F, Fp2Field<C>>::value;  // G2: two lanes per bucket
-  {
-    size_t n_chunks = (size_t)p->W * p->T;
-    if constexpr (kLanePairs) {
-      if (p->reduce28) {
-        typedef XYZZ28L<Fp28<C>> X28;
-        k_chunks_lp28<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>(
-            (const X28*)p->d_state28, n_chunks, p->L, (X28*)p->d_A, (X28*)p->d_W0);
-        constexpr int RB = 512;  // 256 lane pairs, 128 slots x 448 B = 56 KB of LDS per block
-        k_masked_sums_lp28<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * 2 * sizeof(X28), st>>>(
-            (const X28*)p->d_A, (const X28*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-        if (p->fold_nsel2)  // folded plan: the groups' sums combined into one window's
-          k_group_combine_lp<C, 128><<<dim3((unsigned)p->fold_nsel2), dim3((unsigned)(4 * p->W)), 2 * p->W * sizeof(X), st>>>(
-              (const X*)p->d_out, p->W, p->nsel, p->nb, (X*)p->d_out + (size_t)p->W * p->nsel);
-      } else if constexpr (kBuildAlt) {  // (boundary-form lane pairs: MLHIP_REDUCE32 / MLHIP_ACC32, test build only)
-        k_chunks_lp<C><<<dim3((unsigned)((2 * n_chunks + 255) / 256)), dim3(256), 0, st>>>((const X*)p->d_buckets, n_chunks,
-                                                                                          p->L, (X*)p->d_A, (X*)p->d_W0);
-        constexpr int RB = 512;  // 256 lane pairs, 128 slots x 384 B = 48 KB of LDS per block
-        k_masked_sums_lp<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X), st>>>(
-            (const X*)p->d_A, (const X*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
+  constexpr int RB = 512;  // 128 quads or 256 lane pairs a block
+  if constexpr (std::is_same<F, Fp2Field<C>>::value) {  // G2: two lanes per bucket
+    // the combine: one lane pair per input slot
+    const unsigned gthreads = (unsigned)(4 * p->W);
+    const size_t glds = 2 * p->W * sizeof(X);
+    if (p->reduce28) {
+      static_assert(reduce_masked_lds<Pair28Form<C>, RB>() == (RB / 4) * 2 * sizeof(XYZZ28L<Fp28<C>>), "128 slots x 448 B = 56 KB");
+      launch_reduce_kernels<Pair28Form<C>, RB>(p, st, p->d_state28, k_chunks_lp28<C>, k_masked_sums_lp28<C, RB>,
+                                               k_group_combine_lp<C, 128>, gthreads, glds);
+    } else if constexpr (kBuildAlt) {  // (boundary-form lane pairs: MLHIP_REDUCE32 / MLHIP_ACC32, test build only)
+      static_assert(reduce_masked_lds<PairForm<C>, RB>() == (RB / 4) * sizeof(X), "128 slots x 384 B = 48 KB");
+      launch_reduce_kernels<PairForm<C>, RB>(p, st, p->d_buckets, k_chunks_lp<C>, k_masked_sums_lp<C, RB>, nullptr, 0, 0);
+    } else {
+      return mlhip_rt::fail(MLHIP_EINVAL, "G2 reduction: the carry-free bucket state is missing");
+    }
+  } else {
+    // the combine: one quad per input slot, at least a wave; a slot for every quad of its launch bound
+    constexpr int GB = 256;
+    const unsigned gthreads = (unsigned)std::max(64, 8 * p->W);
+    constexpr size_t glds = GB / QuadForm<C>::LANES * sizeof(X);
+    static_assert(glds == 64 * sizeof(X), "64 slots");
+    if (p->reduce28) {
+      static_assert(reduce_masked_lds<Quad28Form<C, false>, RB>() == (RB / 4) * sizeof(XYZZ28<C>), "128 slots: 28 KB");
+      if constexpr (C::HAS_EDWARDS) {
+        if (p->last_ed) {  // the buckets are in extended twisted Edwards coordinates (msm_ed.h): the same kernels on that addition
+          launch_reduce_kernels<Quad28Form<C, true>, RB>(p, st, p->d_state28, k_chunks_q28<C, true>, k_masked_sums_q28<C, RB, true>,
+                                                         k_group_combine_q<C, GB>, gthreads, glds);
+          return 0;  // (both forms leave Weierstrass sums: one combine)
+        }
+      }
+      launch_reduce_kernels<Quad28Form<C, false>, RB>(p, st, p->d_state28, k_chunks_q28<C>, k_masked_sums_q28<C, RB>,
+                                                      k_group_combine_q<C, GB>, gthreads, glds);
+    } else if constexpr (kBuildAlt) {  // boundary-form reductions: test build only
+      if (p->reduce_one_lane) {  // MLHIP_REDUCE_ONE_LANE=1 when the plan was created
+        static_assert(reduce_masked_lds<LaneForm<F>, 256>() == 256 * sizeof(X), "256 slots: 48 KB");
+        launch_reduce_kernels<LaneForm<F>, 256>(p, st, p->d_buckets, k_chunks<F>, k_masked_sums<F, 256>, nullptr, 0, 0);
       } else {
-        return mlhip_rt::fail(MLHIP_EINVAL, "G2 reduction: the carry-free bucket state is missing");
+        static_assert(reduce_masked_lds<QuadForm<C>, RB>() == (RB / 4) * sizeof(X), "128 slots: 24 KB");
+        launch_reduce_kernels<QuadForm<C>, RB>(p, st, p->d_buckets, k_chunks_q<C>, k_masked_sums_q<C, RB>, nullptr, 0, 0);
       }
     } else {
-      if (p->reduce28) {
-        // the accumulation left its carry-free bucket state in d_state28 (MLHIP_SEG_KEEP28)
-        typedef XYZZ28<C> X28;
-        constexpr int RB = 512;  // 128 quads, 28 KB of LDS per block
-        const dim3 cgrid((unsigned)((4 * n_chunks + p->red_block - 1) / p->red_block)), cblock(p->red_block);
-        bool done_ed = false;
-        if constexpr (C::HAS_EDWARDS) {
-          if (p->last_ed) {  // ... in extended twisted Edwards coordinates (msm_ed.h): the same kernels on that addition
-            k_chunks_q28<C, true><<<cgrid, cblock, 0, st>>>((const X28*)p->d_state28, n_chunks, p->L, (X28*)p->d_A, (X28*)p->d_W0);
-            k_masked_sums_q28<C, RB, true><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X28), st>>>(
-                (const X28*)p->d_A, (const X28*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-            done_ed = true;
-          }
-        }
-        if (!done_ed) {
-          k_chunks_q28<C><<<cgrid, cblock, 0, st>>>((const X28*)p->d_state28, n_chunks, p->L, (X28*)p->d_A, (X28*)p->d_W0);
-          k_masked_sums_q28<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X28), st>>>(
-              (const X28*)p->d_A, (const X28*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-        }
-        if (p->fold_nsel2)  // folded plan: the groups' sums combined into one window's (both forms leave Weierstrass sums)
-          k_group_combine_q<C, 256><<<dim3((unsigned)p->fold_nsel2), dim3((unsigned)std::max(64, 8 * p->W)), 64 * sizeof(X), st>>>(
-              (const X*)p->d_out, p->W, p->nsel, p->nb, (X*)p->d_out + (size_t)p->W * p->nsel);
-      } else if constexpr (kBuildAlt) {  // boundary-form reductions: test build only
-        if (p->reduce_one_lane) {  // MLHIP_REDUCE_ONE_LANE=1 when the plan was created
-          k_chunks<F><<<dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, st>>>((const X*)p->d_buckets, n_chunks,
-                                                                                       p->L, (X*)p->d_A, (X*)p->d_W0);
-          constexpr int RB = 256;  // 48 KB of LDS per block
-          k_masked_sums<F, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), RB * sizeof(X), st>>>(
-              (const X*)p->d_A, (const X*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-        } else {
-          // one point per quad of lanes: a group addition is 4 rounds of one multiplication instead of 14 in a row
-          k_chunks_q<C><<<dim3((unsigned)((4 * n_chunks + p->red_block - 1) / p->red_block)), dim3(p->red_block), 0, st>>>((const X*)p->d_buckets, n_chunks,
-                                                                                           p->L, (X*)p->d_A, (X*)p->d_W0);
-          constexpr int RB = 512;  // 128 quads, 24 KB of LDS per block
-          k_masked_sums_q<C, RB><<<dim3((unsigned)(p->W * p->nsel)), dim3(RB), (RB / 4) * sizeof(X), st>>>(
-              (const X*)p->d_A, (const X*)p->d_W0, p->T, p->nsel, (X*)p->d_out);
-        }
-      } else {
-        return mlhip_rt::fail(MLHIP_EINVAL, "G1 reduction: the carry-free bucket state is missing");
-      }
+      return mlhip_rt::fail(MLHIP_EINVAL, "G1 reduction: the carry-free bucket state is missing");
     }
   }
   return 0;

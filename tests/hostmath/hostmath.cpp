@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 #include "../../mathlib_amd/csrc/pairing.h"
 #include "../../mathlib_amd/csrc/msm_body.h"
@@ -22,6 +23,95 @@
 #include "../../mathlib_amd/csrc/pairing_quad.h"
 
 using namespace mlhip;
+
+// ---- reduction forms on the host (msm_reduce.h: "reduction forms"): what reduce_chunk_body (msm_body.h) needs of a form,
+// over the host backends of the kernels' additions.  Mem is the boundary form throughout, so that every form reads the same
+// buckets.  These are hand-written twins of the device forms, NOT the device forms: what they pin is the shared chunk loop
+// (its order, with and without the prefetch) and the additions; the device forms' own set_empty / load / store / store_out
+// are checked by the GPU tests alone (tests/test_msm_reduce_gpu.py).
+struct RefLane {};  // no form: msm_chunk_body itself, one lane with xyzz_add -- the reference
+template <class C>
+struct HostQuadForm {  // QuadForm over QuadHost
+  typedef QuadHost<C> B;
+  static constexpr bool CHUNK_PREFETCH = true;
+  static constexpr int MEMS = 1;
+  typedef XYZZ<FpField<C>> Mem;
+  typedef typename B::V V;
+  static void set_empty(V& v) {
+    Mem inf;
+    xyzz_set_inf<FpField<C>>(inf);
+    B::scatter(v, inf);
+  }
+  static void load(V& v, const Mem* arr, size_t i) { B::scatter(v, arr[i]); }
+  static void store(Mem* arr, size_t i, const V& v) { B::gather(arr[i], v); }
+  static void add(V& a, const V& b) { quad_xyzz_add<C, B>(a, b); }
+};
+template <class C>
+struct HostQuad28Form {  // Quad28Form<C, false> over QuadHost28: all-zero limbs = empty
+  typedef QuadHost28<C> B;
+  static constexpr bool CHUNK_PREFETCH = true;
+  static constexpr int MEMS = 1;
+  typedef XYZZ<FpField<C>> Mem;
+  typedef typename B::V V;
+  static void set_empty(V& v) {
+    for (int k = 0; k < 4; k++) fp28_zero<C>(v.v[k]);
+  }
+  static void load(V& v, const Mem* arr, size_t i) {
+    set_empty(v);
+    if (xyzz_is_inf<FpField<C>>(arr[i])) return;
+    fp28_from_fp<C>(v.v[0], arr[i].x);
+    fp28_from_fp<C>(v.v[1], arr[i].y);
+    fp28_from_fp<C>(v.v[2], arr[i].zz);
+    fp28_from_fp<C>(v.v[3], arr[i].zzz);
+  }
+  static void store(Mem* arr, size_t i, const V& v) {
+    XYZZ28<C> r28;
+    B::gather(r28, v);
+    xyzz28_to<C>(arr[i], r28, fp28_all_zero<C>(r28.zz));
+  }
+  static void add(V& a, const V& b) { quad28_xyzz_add<C, B>(a, b); }
+};
+template <class C>
+struct HostPair28Form {  // Pair28Form over PairHost: the carry-free lane-pair state with its infinity flag
+  typedef PairHost<C> B;
+  static constexpr bool CHUNK_PREFETCH = false;
+  static constexpr int MEMS = 1;
+  typedef XYZZ<Fp2Field<C>> Mem;
+  struct V {
+    XYZZ28L<typename B::V> p;
+    bool inf;
+  };
+  static void set_empty(V& v) { v.inf = true; }
+  static void load(V& v, const Mem* arr, size_t i) {
+    const Mem& q = arr[i];
+    v.inf = xyzz_is_inf<Fp2Field<C>>(q);
+    if (v.inf) return;
+    fp28_from_fp<C>(v.p.x.v[0], q.x.c0);
+    fp28_from_fp<C>(v.p.x.v[1], q.x.c1);
+    fp28_from_fp<C>(v.p.y.v[0], q.y.c0);
+    fp28_from_fp<C>(v.p.y.v[1], q.y.c1);
+    fp28_from_fp<C>(v.p.zz.v[0], q.zz.c0);
+    fp28_from_fp<C>(v.p.zz.v[1], q.zz.c1);
+    fp28_from_fp<C>(v.p.zzz.v[0], q.zzz.c0);
+    fp28_from_fp<C>(v.p.zzz.v[1], q.zzz.c1);
+  }
+  static void store(Mem* arr, size_t i, const V& v) {
+    Mem& a = arr[i];
+    if (v.inf) {
+      xyzz_set_inf<Fp2Field<C>>(a);
+      return;
+    }
+    fp28_to_fp<C>(a.x.c0, v.p.x.v[0]);
+    fp28_to_fp<C>(a.x.c1, v.p.x.v[1]);
+    fp28_to_fp<C>(a.y.c0, v.p.y.v[0]);
+    fp28_to_fp<C>(a.y.c1, v.p.y.v[1]);
+    fp28_to_fp<C>(a.zz.c0, v.p.zz.v[0]);
+    fp28_to_fp<C>(a.zz.c1, v.p.zz.v[1]);
+    fp28_to_fp<C>(a.zzz.c0, v.p.zzz.v[0]);
+    fp28_to_fp<C>(a.zzz.c1, v.p.zzz.v[1]);
+  }
+  static void add(V& a, const V& b) { xyzz28_lp_add<C, B>(a.p, a.inf, b.p, b.inf); }
+};
 
 template <class C>
 struct Ops {
@@ -156,21 +246,40 @@ struct Ops {
     msm_digits_body<C>(0, 1, (const uint32_t*)scalar, mont != 0, c, W, out);
     return W;
   }
-  // level-1 bucket reduction body over an array of n_chunks*L affine "buckets"; returns A and W0 as affine
-  static int chunks(const void* pts, int n_chunks, void* outA, void* outW0) {
-    const A1* p = (const A1*)pts;
-    std::vector<X1> b(n_chunks * 8), A(n_chunks), W0(n_chunks);
-    for (int i = 0; i < n_chunks * 8; i++) xyzz_from_affine<FpField<C>>(b[i], p[i]);
-    for (int g = 0; g < n_chunks; g++) msm_chunk_body<FpField<C>>(g, b.data(), A.data(), W0.data(), 8,
-                                                                  [](X1& a, const X1& q) { xyzz_add<FpField<C>>(a, q); });
+  // level-1 bucket reduction body (reduce_chunk_body over the host form R; RefLane: msm_chunk_body) on n_chunks * l_eff affine "buckets"; returns A and W0
+  // as affine points
+  template <class R, class F>
+  static int chunks_t(const void* pts, int n_chunks, int l_eff, void* outA, void* outW0) {
+    typedef Affine<F> A;
+    typedef XYZZ<F> X;
+    const A* p = (const A*)pts;
+    std::vector<X> b((size_t)n_chunks * l_eff), Av(n_chunks), W0(n_chunks);
+    for (size_t i = 0; i < b.size(); i++) xyzz_from_affine<F>(b[i], p[i]);
     for (int g = 0; g < n_chunks; g++) {
-      A1 r;
-      xyzz_to_affine<FpField<C>>(r, A[g]);
-      memcpy((char*)outA + g * sizeof(A1), &r, sizeof(A1));
-      xyzz_to_affine<FpField<C>>(r, W0[g]);
-      memcpy((char*)outW0 + g * sizeof(A1), &r, sizeof(A1));
+      if constexpr (std::is_same<R, RefLane>::value)
+        msm_chunk_body<F>(g, b.data(), Av.data(), W0.data(), l_eff, [](X& a, const X& q) { xyzz_add<F>(a, q); });
+      else
+        reduce_chunk_body<R>(g, b.data(), Av.data(), W0.data(), l_eff, [](typename R::V& a, const typename R::V& q) { R::add(a, q); });
+    }
+    for (int g = 0; g < n_chunks; g++) {
+      A r;
+      xyzz_to_affine<F>(r, Av[g]);
+      memcpy((char*)outA + g * sizeof(A), &r, sizeof(A));
+      xyzz_to_affine<F>(r, W0[g]);
+      memcpy((char*)outW0 + g * sizeof(A), &r, sizeof(A));
     }
     return 0;
+  }
+  // form 0: msm_chunk_body with xyzz_add (G1 or G2: the reference); 1 / 2: quads in the boundary / carry-free form (G1);
+  // 3: carry-free lane pairs (G2)
+  static int chunks(int group, int form, const void* pts, int n_chunks, int l_eff, void* outA, void* outW0) {
+    if (l_eff < 1 || (group != 1 && group != 2)) return -1;
+    if (form == 0 && group == 1) return chunks_t<RefLane, FpField<C>>(pts, n_chunks, l_eff, outA, outW0);
+    if (form == 0) return chunks_t<RefLane, Fp2Field<C>>(pts, n_chunks, l_eff, outA, outW0);
+    if (form == 1 && group == 1) return chunks_t<HostQuadForm<C>, FpField<C>>(pts, n_chunks, l_eff, outA, outW0);
+    if (form == 2 && group == 1) return chunks_t<HostQuad28Form<C>, FpField<C>>(pts, n_chunks, l_eff, outA, outW0);
+    if (form == 3 && group == 2) return chunks_t<HostPair28Form<C>, Fp2Field<C>>(pts, n_chunks, l_eff, outA, outW0);
+    return -1;
   }
   // the Horner pass of the host tail (msm_plan.h: host_tail): sum_w 2^off[w] V[w] over affine inputs V[w], in XYZZ (which = 0,
   // rounds 1-3) or Jacobian coordinates (which = 1, ec_jac.h); group 1 or 2; affine result
@@ -198,8 +307,8 @@ struct Ops {
   }
   // A whole MSM over shifted-base tables (msm_fold.h), replayed on the host with the kernels' own bodies: the table rows
   // (fold_rows_body), the signed digits of the even layout into ONE bucket set (msm_window_digit, xyzz_madd), the bucket
-  // groups reduced like windows (msm_chunk_body, the plain / masked sums of k_masked_sums), the groups combined into one
-  // window (fold_combine_src, k_group_combine_q) and that window's host tail (host_tail_window).  Digit width c, groups
+  // groups reduced like windows (msm_chunk_body, the half / masked sums of reduce_sel_index), the groups combined into one
+  // window (fold_combine_src, as group_combine_body) and that window's host tail (host_tail_window).  Digit width c, groups
   // of 2^lgM buckets, chunks of 2^lgL.  group 1 or 2; affine result.
   template <class F>
   static int fold_msm_t(const void* pts, const void* scalars, int n, int c, int lgM, int lgL, void* out) {
@@ -235,13 +344,10 @@ struct Ops {
       for (size_t t = 0; t < T; t++)
         msm_chunk_body<F>(t, B.data() + g * M, Ach.data(), W0.data(), (int)L, [](X& a, const X& q) { xyzz_add<F>(a, q); });
       X* o = outg.data() + g * nsel;
-      for (int k = 0; k < nsel; k++) xyzz_set_inf<F>(o[k]);
-      const size_t half = (T + 1) / 2;
-      for (size_t t = 0; t < T; t++) {
-        xyzz_add<F>(o[t < half ? 0 : 1], W0[t]);
-        xyzz_add<F>(o[t < half ? 2 : 3], Ach[t]);
-        for (int k = 0; k < nb; k++)
-          if ((t >> k) & 1) xyzz_add<F>(o[4 + k], Ach[t]);
+      for (int sel = 0; sel < nsel; sel++) {  // list sel of the group: reduce_sel_index, as the kernels
+        xyzz_set_inf<F>(o[sel]);
+        const X* src = sel < 2 ? W0.data() : Ach.data();
+        for (uint32_t j = 0; j < reduce_sel_count(sel, (uint32_t)T); j++) xyzz_add<F>(o[sel], src[reduce_sel_index(sel, j, (uint32_t)T)]);
       }
     }
     // the groups combined into one window of W T chunks
@@ -968,7 +1074,12 @@ int hm_horner(int curve, int group, const void* pts, int W, const int* down, int
 int hm_fold_msm(int curve, int group, const void* pts, const void* scalars, int n, int c, int lgM, int lgL, void* out) {
   DISPATCH(curve, fold_msm(group, pts, scalars, n, c, lgM, lgL, out))
 }
-int hm_chunks(int curve, const void* pts, int n_chunks, void* outA, void* outW0) { DISPATCH(curve, chunks(pts, n_chunks, outA, outW0)) }
+int hm_chunks(int curve, const void* pts, int n_chunks, void* outA, void* outW0) { DISPATCH(curve, chunks(1, 0, pts, n_chunks, 8, outA, outW0)) }
+int hm_chunks_form(int curve, int group, int form, const void* pts, int n_chunks, int l_eff, void* outA, void* outW0) {
+  DISPATCH(curve, chunks(group, form, pts, n_chunks, l_eff, outA, outW0))
+}
+unsigned hm_reduce_sel_count(int sel, unsigned T) { return reduce_sel_count(sel, T); }
+unsigned hm_reduce_sel_index(int sel, unsigned j, unsigned T) { return reduce_sel_index(sel, j, T); }
 int hm_g1_decode(int curve, const uint8_t* w, int compressed, int subgroup, void* out) { DISPATCH(curve, g1dec(w, compressed, subgroup, out)) }
 int hm_g1_encode(int curve, const void* pt, int compressed, uint8_t* w) { DISPATCH(curve, g1enc(pt, compressed, w)) }
 int hm_fp28_op(int curve, int op, const void* a, const void* b, const void* c, const void* d, void* out) { DISPATCH(curve, fp28_op(op, a, b, c, d, out)) }

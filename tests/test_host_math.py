@@ -267,6 +267,65 @@ def test_bucket_chunk_reduction_body(hostmath, name):
         assert R.g1_from_mont_bytes(cp, ow.raw[g * 2 * n : (g + 1) * 2 * n]) == w
 
 
+@pytest.mark.parametrize("name", CURVES)
+@pytest.mark.parametrize("l_eff", [1, 2, 8])
+def test_bucket_chunk_body_over_the_lane_group_forms(hostmath, name, l_eff):
+    """reduce_chunk_body (msm_body.h), the one chunk loop of the reduction kernels, over the host backends of the quad and lane-pair
+    additions (QuadHost, QuadHost28, PairHost: with and without the prefetch) against msm_chunk_body (form 0: the same loop over one lane) with
+    xyzz_add as a point, itself checked against the oracle -- compared as affine points.  Buckets: infinities, the same point twice (acc + b and w0 + acc as
+    doublings), P beside -P (acc back to infinity), and a chunk that is empty but for its last bucket."""
+    cp = R.CURVES[name]
+    L, n = hostmath, cp.fp_bytes
+    for group, rand, neg, enc, forms in ((1, R.random_g1, R.g1_neg, R.g1_to_mont_bytes, (1, 2)),
+                                         (2, R.random_g2, R.g2_neg, R.g2_to_mont_bytes, (3,))):
+        d = R.Drbg("hm/chunk-forms/%s/%d" % (name, group))
+        P = [rand(cp, d) for _ in range(8)]
+        chunks = [[P[i % 8] if i % 3 else None for i in range(l_eff)],  # infinities mixed in
+                  [P[0]] * l_eff,  # the same point in every bucket: every acc += b[i] after the first is b + b or 2b + b ...
+                  [P[1], neg(cp, P[1])] * 4,  # P beside -P
+                  [None] * 7 + [P[2]],  # w0 = acc after empty buckets: w0 += acc is a doubling
+                  [P[3], P[3], None, neg(cp, P[3]), P[4], None, P[4], P[5]]]
+        chunks = [(c * 8)[:l_eff] for c in chunks]
+        buf = b"".join(enc(cp, q) for c in chunks for q in c)
+        sz = 2 * n * group
+        ref = [ctypes.create_string_buffer(sz * len(chunks)) for _ in range(2)]
+        assert L.hm_chunks_form(cp.curve_id, group, 0, buf, len(chunks), l_eff, ref[0], ref[1]) == 0
+        # the reference itself against the oracle
+        add, mul, dec = (R.g1_add, R.g1_mul, R.g1_from_mont_bytes) if group == 1 else (R.g2_add, R.g2_mul, R.g2_from_mont_bytes)
+        for g, c in enumerate(chunks):
+            a = w = None
+            for i, q in enumerate(c):
+                a = add(cp, a, q)
+                w = add(cp, w, mul(cp, q, i) if q is not None else None)
+            assert dec(cp, ref[0].raw[g * sz : (g + 1) * sz]) == a
+            assert dec(cp, ref[1].raw[g * sz : (g + 1) * sz]) == w
+        for form in forms:
+            out = [ctypes.create_string_buffer(sz * len(chunks)) for _ in range(2)]
+            assert L.hm_chunks_form(cp.curve_id, group, form, buf, len(chunks), l_eff, out[0], out[1]) == 0
+            assert out[0].raw == ref[0].raw and out[1].raw == ref[1].raw, (name, group, form, l_eff)
+    assert L.hm_chunks_form(cp.curve_id, 2, 1, buf, 1, l_eff, out[0], out[1]) == -1  # no such form for that group
+
+
+@pytest.mark.parametrize("T", [1, 2, 4, 8, 64])
+def test_reduce_selection_lists(hostmath, T):
+    """reduce_sel_index / reduce_sel_count (msm_body.h), the one place that maps element j of list sel to a chunk index:
+    lists 0 and 1 partition [0, T), as do 2 and 3, split at (T + 1) / 2; list 4 + k is exactly the t with bit k set, each
+    once; every list of T >= 2 has T / 2 elements; at T = 1 the second halves are empty."""
+    L = hostmath
+    L.hm_reduce_sel_count.restype = L.hm_reduce_sel_index.restype = ctypes.c_uint
+    nb = T.bit_length() - 1
+    lists = [[L.hm_reduce_sel_index(sel, j, T) for j in range(L.hm_reduce_sel_count(sel, T))] for sel in range(4 + nb)]
+    half = (T + 1) // 2
+    for a, b in ((0, 1), (2, 3)):
+        assert lists[a] == list(range(half)) and lists[b] == list(range(half, T))
+    for k in range(nb):
+        assert lists[4 + k] == [t for t in range(T) if (t >> k) & 1]
+    if T >= 2:
+        assert all(len(l) == T // 2 for l in lists)
+    else:
+        assert [len(l) for l in lists] == [1, 0, 1, 0]
+
+
 @pytest.mark.parametrize("name", list(R.CURVES))
 def test_g1_wire_codec(hostmath, name):
     """csrc/codec.h (sqrt incl. Tonelli-Shanks for BLS12-377, flag handling, subgroup check) vs the oracle's
