@@ -31,6 +31,7 @@ package hip
 #include "mlhip_bits.h"
 #include "mlhip_products.h"
 #include "mlhip_subgroup.h"
+#include "mlhip_bases_set.h"
 */
 import "C"
 
@@ -982,6 +983,133 @@ func (b *Bases) Close() {
 	if b.h != nil {
 		C.mlhip_bases_destroy(b.h)
 		b.h = nil
+	}
+}
+
+// BasesG2 is a G2 point table kept on the device: Bases for the other group (a Groth16 prover's B2 query).
+type BasesG2 struct {
+	h *C.mlhip_bases
+	n int
+}
+
+func (c *Curve) NewBasesG2(points []driver.G2) *BasesG2 {
+	n := len(points)
+	if n == 0 {
+		panic("hip: NewBasesG2 needs at least one point")
+	}
+	aff := make([]bls12381.G2Affine, n)
+	for i := range points {
+		aff[i] = points[i].(*gurvy381.G2).G2Affine
+	}
+	b := &BasesG2{n: n}
+	check(func() C.int {
+		return C.mlhip_bases_create(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2, unsafe.Pointer(&aff[0]), C.size_t(n),
+			C.int(WindowC), &b.h)
+	})
+	return b
+}
+
+func (b *BasesG2) Close() {
+	if b.h != nil {
+		C.mlhip_bases_destroy(b.h)
+		b.h = nil
+	}
+}
+
+// BasesSet is a set of 1..4 resident tables, G1 and G2 in any order, whose MSMs run over ONE scalar vector from one upload
+// and one sort per tile (mlhip_bases_set_create): a Groth16 prover's A, B1 and B2 queries over the witness.  The members
+// are not owned: they must stay open while the set is, and stay usable on their own.
+type BasesSet struct {
+	h      *C.mlhip_bases
+	n      int
+	groups []int // 1 = G1, 2 = G2, in member order
+}
+
+// NewBasesSet takes *Bases and *BasesG2 members.
+func (c *Curve) NewBasesSet(members ...interface{}) *BasesSet {
+	s := &BasesSet{}
+	hs := make([]*C.mlhip_bases, 0, len(members))
+	for _, m := range members {
+		var h *C.mlhip_bases
+		var n, g int
+		switch b := m.(type) {
+		case *Bases:
+			h, n, g = b.h, b.n, 1
+		case *BasesG2:
+			h, n, g = b.h, b.n, 2
+		default:
+			panic("hip: NewBasesSet takes *Bases and *BasesG2")
+		}
+		if len(hs) == 0 || n < s.n {
+			s.n = n
+		}
+		hs = append(hs, h)
+		s.groups = append(s.groups, g)
+	}
+	if len(hs) == 0 {
+		panic("hip: NewBasesSet needs at least one member")
+	}
+	check(func() C.int {
+		return C.mlhip_bases_set_create((**C.mlhip_bases)(unsafe.Pointer(&hs[0])), C.size_t(len(hs)), &s.h)
+	})
+	return s
+}
+
+// MultiScalarMul returns every member's MSM over the first len(scalars) bases: the G1 members' results and the G2 members'
+// results, each in member order.
+func (s *BasesSet) MultiScalarMul(scalars []driver.Zr) ([]driver.G1, []driver.G2) {
+	if len(scalars) > s.n {
+		panic("hip: more scalars than the smallest member's resident bases")
+	}
+	const g1b, g2b = 96, 192
+	total := 0
+	for _, g := range s.groups {
+		total += g * g1b
+	}
+	// (uint64 backing: the results are arrays of 64-bit limbs)
+	buf := make([]uint64, total/8)
+	sc := make([]fr.Element, len(scalars)+1)
+	for i := range scalars {
+		sc[i] = gurvy381.ZrValue(scalars[i])
+	}
+	check(func() C.int {
+		return C.mlhip_bases_msm(s.h, unsafe.Pointer(&sc[0]), 1, C.size_t(len(scalars)), unsafe.Pointer(&buf[0]))
+	})
+	var o1 []driver.G1
+	var o2 []driver.G2
+	at := 0
+	for _, g := range s.groups {
+		p := unsafe.Pointer(&buf[at/8])
+		if g == 1 {
+			o1 = append(o1, &gurvy381.G1{G1Affine: *(*bls12381.G1Affine)(p)})
+			at += g1b
+		} else {
+			o2 = append(o2, &gurvy381.G2{G2Affine: *(*bls12381.G2Affine)(p)})
+			at += g2b
+		}
+	}
+	return o1, o2
+}
+
+// Route reports how the set's last MultiScalarMul ran: members, sort trains per tile, uploads of the scalar vector, and 1
+// when every member read shifted-base tables (mlhip_bases_set_route).
+func (s *BasesSet) Route() [4]int {
+	var info [4]C.int
+	var out [4]int
+	if s.h == nil {
+		return out
+	}
+	k := int(C.mlhip_bases_set_route(s.h, &info[0], 4))
+	for i := 0; i < k && i < 4; i++ {
+		out[i] = int(info[i])
+	}
+	return out
+}
+
+func (s *BasesSet) Close() {
+	if s.h != nil {
+		C.mlhip_bases_destroy(s.h)
+		s.h = nil
 	}
 }
 

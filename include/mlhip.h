@@ -461,6 +461,38 @@ MLHIP_API mlhip_msm_plan* mlhip_bases_plan(mlhip_bases* bases);
  * subgroup, MLHIP_EDWARDS=0): such tables take the Weierstrass kernels and give the reference's result for any input. */
 MLHIP_API int mlhip_bases_checked_subgroup(mlhip_bases* bases);
 MLHIP_API int mlhip_bases_destroy(mlhip_bases* bases);
+/* ---- sets of handles: the MSMs of several resident tables over ONE scalar vector (a Groth16 prover's A, B1 and B2 queries
+ * over the witness).  A SET of 1..4 single-device handles of one curve on one device, any mix of G1 and G2: a handle itself.
+ * The members are NOT owned: they must outlive the set and stay usable on their own, before, between and after set calls;
+ * mlhip_bases_destroy(set) frees the set only.  Refused with MLHIP_EINVAL: k = 0 or k > 4, a null or repeated member, a set
+ * as a member, members of different curves or devices, a member spread over several devices, a device-result member.
+ *   mlhip_bases_msm(set, scalars, mont, n, out) and mlhip_bases_msm_device(set, d_scalars, mont, n, stream, out) compute every
+ *   member's MSM over the same first n scalars (n <= the smallest member's count) and write the affine results back to back
+ *   in member order, each at its own point size, into HOST memory; n = 0 writes all-zero points.  Both return when the
+ *   results are there.  A set call takes every member's mutex, in address order.
+ *   mlhip_bases_plan(set) is NULL; mlhip_bases_checked_subgroup(set) is 1 iff it is 1 for every member;
+ *   mlhip_bases_msm_batch*, mlhip_bases_batch_tabled are MLHIP_EINVAL: batches run on the members.
+ * What a set call shares: the entry lists of a tile depend on the scalars and the plan's geometry only, not on the group.
+ * Members whose plans have the same geometry (tables or not, digit width, digits, tile, bucket groups, scalar width) form a
+ * CLASS: every tile is sorted once and accumulated once per member (shifted-base tables included: each member gathers from
+ * its own table through the shared lists); a member of another geometry is a class of its own.  Host scalars cross PCIe once
+ * per call whatever the number of classes.  Same result bytes as the members' own calls.
+ * MLHIP_BASES_SET_SHARE=0: every member runs exactly what its own mlhip_bases_msm[_device] would, in member order (the second
+ * implementation, and the A/B of tools/perf_bases_set.py); =1: the shared route at every size; unset: the shared route from
+ * 2^12 host scalars / 2^16 device scalars on, the per-member route below (MLHIP_SET_SHARE_MIN_N_HOST / _DEVICE of
+ * mathlib_amd/csrc/msm_set.h: the smallest measured sizes from which the set call is level with or ahead of the k separate
+ * calls in every cell of profiles/bases_set_ab.txt -- 2^20 scalars, tables on: {G1, G2} 0.80-0.89 of the separate calls with
+ * host scalars and 0.96-0.98 with device scalars, {G1, G1, G2} 0.77-0.86 and 0.93-0.97).
+ * Not offered: per-member scalar offsets, device-result sets, sets over sharded handles. */
+#define MLHIP_GROUP_SET 0x200     /* `group` of mlhip_bases_create: `points` is an array of n member handles (curve, window_c unused) */
+#define MLHIP_MSM_SET_ROUTE 0x100 /* `scalars_mont` of mlhip_bases_msm on a set with scalars = NULL: no MSM, the route report */
+/* include/mlhip_bases_set.h has the two as inline functions over mlhip_bases_create / mlhip_bases_msm, in the house style of
+ * MLHIP_GROUP_SUBGROUP and MLHIP_WINDOW_BITS (the dynamic symbol table stays what it was):
+ *   mlhip_bases_set_create(members, k, &set)
+ *   mlhip_bases_set_route(set, info, cap) -- how the set's last MSM ran: info[0] = members, info[1] = sort trains per tile
+ *   (geometry classes), info[2] = host-to-device copies of the scalar vector (0 for device scalars), info[3] = 1 iff every
+ *   member read tables; returns the number of entries written (<= cap).  Recorded by the code path that ran: the per-member
+ *   route reports (k, k, k or 0, .). */
 /* K independent MSMs over the resident bases of a handle (an idemix or BBS verifier checking many proofs against one issuer
  * key: most pairs of every proof multiply the same few dozen bases):
  *   out[k] = sum_{offsets[k] <= i < offsets[k+1]} [scalars[i]] B[idx(i)]
@@ -627,6 +659,8 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_EDWARDS=0                  BLS12-377 G1 over a checked SRS: keep the Weierstrass bucket sums
  *     MLHIP_BASES_TABLES=0|1           mlhip_bases_create: never / always keep shifted-base tables (default: see there)
  *     MLHIP_FOLD_WINDOW=c, MLHIP_FOLD_TILE_LOG2=t   ... their digit width (default 13 .. 20 by size) and tile (2^20 bases)
+ *     MLHIP_BASES_SET_SHARE=0|1        MSMs on a set of handles: every member's own MSM in turn (also the A/B switch) / one upload
+ *                                      and one sort train per geometry class at every size (default: see mlhip_bases_set_create)
  *     MLHIP_MSM_BATCH_CHUNK=P          mlhip_msm_batch*: pairs per chunk, 1, 2, 4 or 8 (default 4; 1 = one product per lane)
  *     MLHIP_MSM_BATCH_BUCKET_MIN=n     mlhip_msm_batch* and the table-free path of mlhip_bases_msm_batch*: segments of n pairs
  *                                      or more take the bucket route (default 512 for G1, 256 for G2; 0 = never, 1 .. 8 mean 9)

@@ -18,8 +18,9 @@
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
 //   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, MulBatchSubgroup, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
-//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, SumG1, SumG2
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, BasesG2, BasesSet::MultiScalarMul, SumG1, SumG2
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -32,6 +33,7 @@
 #include "mlhip_bits.h"
 #include "mlhip_products.h"
 #include "mlhip_subgroup.h"
+#include "mlhip_bases_set.h"
 
 namespace mlhip_driver {
 
@@ -777,6 +779,7 @@ class Curve {
 };
 
 // A G1 point table kept on the device (mlhip_bases_*): uploaded once, then only the scalars move per call.
+class BasesSet;
 class Bases {
  public:
   Bases(const Curve& c, const std::vector<G1>& points) : curve_(&c), n_(points.size()) {
@@ -858,6 +861,110 @@ class Bases {
  private:
   const Curve* curve_;
   size_t n_;
+  mlhip_bases* h_ = nullptr;
+  friend class BasesSet;
+};
+
+// A G2 point table kept on the device: Bases for the other group (a Groth16 prover's B2 query), as a member of a BasesSet or
+// on its own.
+class BasesG2 {
+ public:
+  BasesG2(const Curve& c, const std::vector<G2>& points) : curve_(&c), n_(points.size()) {
+    Bytes pts;
+    for (auto& x : points) pts.insert(pts.end(), x.raw.begin(), x.raw.end());
+    check(mlhip_bases_create(c.id, MLHIP_GROUP_G2, pts.data(), n_, c.window_c, &h_));
+  }
+  BasesG2(const BasesG2&) = delete;
+  BasesG2& operator=(const BasesG2&) = delete;
+  ~BasesG2() { mlhip_bases_destroy(h_); }
+  G2 MultiScalarMul(const std::vector<Zr>& b) const {
+    if (b.size() > n_) throw std::out_of_range("MultiScalarMul: more scalars than resident bases");
+    G2 out = curve_->NewG2();
+    if (b.empty()) return out;
+    Bytes sc(32 * b.size());
+    for (size_t i = 0; i < b.size(); i++) {
+      auto l = b[i].abi_limbs();
+      memcpy(sc.data() + 32 * i, l.data(), 32);
+    }
+    check(mlhip_bases_msm(h_, sc.data(), curve_->scalars_mont ? 1 : 0, b.size(), out.raw.data()));
+    return out;
+  }
+
+ private:
+  const Curve* curve_;
+  size_t n_;
+  mlhip_bases* h_ = nullptr;
+  friend class BasesSet;
+};
+
+// A set of 1..4 resident tables of one curve, G1 and G2 in any order, whose MSMs run over ONE scalar vector from one upload
+// and one sort per tile (mlhip_bases_set_create).  The members are not owned: they must outlive the set, and stay usable.
+//   BasesSet set(c);  set.Add(a).Add(b1).Add(b2);  auto r = set.MultiScalarMul(witness);   // r.g1 = {A, B1}, r.g2 = {B2}
+class BasesSet {
+ public:
+  struct Result {
+    std::vector<G1> g1;  // the G1 members' results, in member order
+    std::vector<G2> g2;  // the G2 members' results, in member order
+  };
+  explicit BasesSet(const Curve& c) : curve_(&c) {}
+  BasesSet(const BasesSet&) = delete;
+  BasesSet& operator=(const BasesSet&) = delete;
+  ~BasesSet() { mlhip_bases_destroy(h_); }
+  BasesSet& Add(const Bases& b) { return add(b.h_, b.n_, MLHIP_GROUP_G1); }
+  BasesSet& Add(const BasesG2& b) { return add(b.h_, b.n_, MLHIP_GROUP_G2); }
+  Result MultiScalarMul(const std::vector<Zr>& b) {
+    open();
+    if (b.size() > n_) throw std::out_of_range("MultiScalarMul: more scalars than the smallest member's resident bases");
+    Bytes sc(32 * b.size() + 1);
+    for (size_t i = 0; i < b.size(); i++) {
+      auto l = b[i].abi_limbs();
+      memcpy(sc.data() + 32 * i, l.data(), 32);
+    }
+    size_t total = 0;
+    for (int g : groups_) total += g == MLHIP_GROUP_G1 ? curve_->g1_bytes : curve_->g2_bytes;
+    Bytes o(total);
+    check(mlhip_bases_msm(h_, sc.data(), curve_->scalars_mont ? 1 : 0, b.size(), o.data()));
+    Result r;
+    size_t at = 0;
+    for (int g : groups_) {
+      if (g == MLHIP_GROUP_G1) {
+        G1 x = curve_->NewG1();
+        x.raw.assign(o.begin() + at, o.begin() + at + curve_->g1_bytes);
+        r.g1.push_back(x);
+        at += curve_->g1_bytes;
+      } else {
+        G2 x = curve_->NewG2();
+        x.raw.assign(o.begin() + at, o.begin() + at + curve_->g2_bytes);
+        r.g2.push_back(x);
+        at += curve_->g2_bytes;
+      }
+    }
+    return r;
+  }
+  // {members, sort trains per tile, uploads of the scalars, 1 iff every member read shifted-base tables} of the last call
+  std::vector<int> Route() {
+    open();
+    int info[4] = {0, 0, 0, 0};
+    const int k = mlhip_bases_set_route(h_, info, 4);
+    if (k < 0) check(k);
+    return std::vector<int>(info, info + k);
+  }
+
+ private:
+  BasesSet& add(mlhip_bases* h, size_t n, int group) {
+    if (h_) throw std::logic_error("BasesSet: Add after the first call");
+    members_.push_back(h);
+    groups_.push_back(group);
+    n_ = members_.size() == 1 ? n : std::min(n_, n);
+    return *this;
+  }
+  void open() {
+    if (!h_) check(mlhip_bases_set_create(members_.data(), members_.size(), &h_));
+  }
+  const Curve* curve_;
+  std::vector<mlhip_bases*> members_;
+  std::vector<int> groups_;
+  size_t n_ = 0;
   mlhip_bases* h_ = nullptr;
 };
 

@@ -428,6 +428,54 @@ def bases_batch_tabled(lib, handle) -> int:
     return n.value
 
 
+GROUP_SET = 0x200
+"""MLHIP_GROUP_SET of include/mlhip.h: the group argument of mlhip_bases_create whose `points` are member handles"""
+MSM_SET_ROUTE = 0x100
+"""MLHIP_MSM_SET_ROUTE of include/mlhip.h: the scalars_mont argument of mlhip_bases_msm that asks a set for its route"""
+
+
+def mlhip_bases_set_create(lib, members, k: int, set_ref) -> int:
+    """include/mlhip_bases_set.h: a set of k member handles (an array of c_void_p, or None) (the return code, as the C function)"""
+    return lib.mlhip_bases_create(0, GROUP_SET, members, k, 0, set_ref)
+
+
+def mlhip_bases_set_route(lib, handle, info, cap: int) -> int:
+    """include/mlhip_bases_set.h: the route of the set's last MSM into the int array `info` (entries written, or the error code)"""
+    if cap < 0:
+        handle = None
+    return lib.mlhip_bases_msm(handle, None, MSM_SET_ROUTE, max(cap, 0), info)
+
+
+def bases_set_create(lib, handles):
+    """mlhip_bases_set_create over the handles (c_void_p) of `lib`: the set (c_void_p); the members are not owned -- destroy
+    the set with mlhip_bases_destroy before them"""
+    arr = (c_void_p * max(1, len(handles)))(*[h.value if isinstance(h, c_void_p) else h for h in handles])
+    s = c_void_p()
+    check(mlhip_bases_set_create(lib, arr, len(handles), byref(s)))
+    return s
+
+
+def bases_set_route(lib, handle):
+    """mlhip_bases_set_route: (members, sort trains per tile, uploads of the scalar vector, 1 iff every member read tables) of
+    the set's last MSM"""
+    info = (ctypes.c_int * 4)()
+    k = mlhip_bases_set_route(lib, handle, info, 4)
+    if k < 0:
+        check(k)
+    return tuple(info[:k])
+
+
+def bases_set_msm(lib, handle, ptszs, scalars: bytes, scalars_mont: bool, n: int):
+    """mlhip_bases_msm on a set whose members' points have ptszs[i] bytes: one affine point (bytes) per member"""
+    out = ctypes.create_string_buffer(sum(ptszs))
+    check(lib.mlhip_bases_msm(handle, scalars, 1 if scalars_mont else 0, n, out))
+    raw, res, off = out.raw, [], 0
+    for sz_ in ptszs:
+        res.append(raw[off : off + sz_])
+        off += sz_
+    return res
+
+
 def q_index_array(index, ppp: int):
     """the q_index array of mlhip_*_prepared* (ppp uint32 entries shared by every product), or None"""
     if index is None:

@@ -25,6 +25,11 @@ struct mlhip_bases {
   std::vector<mlhip_bases*> shards;
   std::vector<size_t> lo;
   std::vector<int> devs;
+  // a SET of handles (mlhip_bases_set_create): 1 .. 4 single-device handles of one curve on one device, NOT owned; n is the
+  // smallest member's count, ptsz the bytes of all results back to back.  No plan, no points, no stream of its own: a set
+  // call runs on its first member's stream (host scalars) or the caller's (device scalars).
+  std::vector<mlhip_bases*> members;
+  int route[4] = {0, 0, 0, 0};  // how the set's last MSM ran (mlhip_bases_set_route), written under mu
 };
 
 
@@ -194,12 +199,197 @@ int check_bases_batch_index(const mlhip_bases* b, const uint32_t* base_index, co
   return 0;
 }
 
+// mlhip_bases_msm / _msm_device on a single-device handle whose mutex the caller holds, arguments checked, n != 0
+int bases_msm_locked(mlhip_bases* b, const void* scalars, int scalars_mont, size_t n, void* out_affine) {
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  {
+    // after the first MSM (which leaves the converted copy of the bases) large calls stream their scalars
+    const mlhip_msm_plan* p = b->plan;
+    const int segments = stream_segments(p->group, n, p);
+    if (segments > 1 && p->points_static && p->conv_src == b->d_pts && n <= p->conv_n) {
+      int rc = plan_stream(b->plan, b->d_pts, b->d_sc, nullptr, scalars, scalars_mont, n, segments, b->stream);
+      return rc ? rc : mlhip_msm_finish(b->plan, out_affine, nullptr);
+    }
+  }
+  if (hipMemcpy(b->d_sc, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess)
+    return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy of MSM scalars failed");
+  return mlhip_msm_run(b->plan, b->d_pts, b->d_sc, scalars_mont, n, b->stream, out_affine, nullptr);
+}
+
+int bases_msm_device_locked(mlhip_bases* b, const void* d_scalars, int scalars_mont, size_t n, void* stream, void* out_affine) {
+  if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  return mlhip_msm_run(b->plan, b->d_pts, d_scalars, scalars_mont, n, stream, out_affine, nullptr);
+}
+
+bool is_set(const mlhip_bases* b) { return !b->members.empty(); }
+
+int reject_set(const mlhip_bases* b, const char* who) {
+  if (!is_set(b)) return 0;
+  return mlhip_rt::fail(MLHIP_EINVAL, std::string(who) + ": the handle is a set of handles (mlhip_bases_set_create); batches run on its members");
+}
+
+SetGeometry set_geometry(const mlhip_msm_plan* p) {
+  SetGeometry g;
+  g.fold = p->fold;
+  g.c = p->c;
+  g.Wd = p->Wd;
+  g.fold_tile = p->fold_tile;
+  g.W = p->W;
+  g.M = p->M;
+  g.bits = p->bits;
+  g.can_train = plan_can_train(p);
+  return g;
+}
+
+// mlhip_bases_msm (d_scalars null) / mlhip_bases_msm_device (scalars null) on a set: every member's MSM over the same first n
+// scalars, the affine results back to back in member order.  Every member's mutex is held, taken in address order.
+//   shared route (msm_set.h: set_share): the members are put into classes of equal plan geometry; the host scalars are
+//   uploaded ONCE, into the first member's scalar buffer, by the first class -- segment by segment as that member's own
+//   mlhip_bases_msm would --, and the later classes read that copy (the first class's stream has waited for every segment);
+//   a class of two or more members sorts every tile once (plan_train), a class of one runs its handle's own launch; the
+//   classes are queued one after another on one stream and finished -- host tails -- in that order.
+//   per-member route: exactly what each member's own call does, in member order.
+int set_msm(mlhip_bases* set, const void* scalars, const void* d_scalars, int mont, size_t n, void* stream, void* out_affine) {
+  const bool device_form = scalars == nullptr;
+  const int k = (int)set->members.size();
+  if (n > set->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than the resident bases of the set's smallest member");
+  int tables = 1;
+  for (mlhip_bases* m : set->members) tables &= m->plan->fold ? 1 : 0;
+  if (n == 0) {
+    memset(out_affine, 0, set->ptsz);
+    std::lock_guard<std::mutex> lk(set->mu);
+    const int r[4] = {k, 0, 0, tables};
+    memcpy(set->route, r, sizeof(r));
+    return 0;
+  }
+  if (!scalars && !d_scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (hipSetDevice(set->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
+  std::lock_guard<std::mutex> lk(set->mu);
+  std::vector<mlhip_bases*> by_address(set->members);
+  std::sort(by_address.begin(), by_address.end(), std::less<mlhip_bases*>());
+  std::vector<std::unique_lock<std::mutex>> held;
+  for (mlhip_bases* m : by_address) held.emplace_back(m->mu);
+  size_t out_off[MLHIP_SET_MAX_MEMBERS + 1] = {0};
+  for (int i = 0; i < k; i++) out_off[i + 1] = out_off[i] + set->members[i]->ptsz;
+  char* out = (char*)out_affine;
+  if (!set_share(n, device_form)) {
+    for (int i = 0; i < k; i++) {
+      mlhip_bases* m = set->members[i];
+      int rc = device_form ? bases_msm_device_locked(m, d_scalars, mont, n, stream, out + out_off[i])
+                           : bases_msm_locked(m, scalars, mont, n, out + out_off[i]);
+      if (rc) return rc;
+    }
+    const int r[4] = {k, k, device_form ? 0 : k, tables};
+    memcpy(set->route, r, sizeof(r));
+    return 0;
+  }
+  SetGeometry g[MLHIP_SET_MAX_MEMBERS];
+  int cls[MLHIP_SET_MAX_MEMBERS];
+  for (int i = 0; i < k; i++) g[i] = set_geometry(set->members[i]->plan);
+  const int n_cls = set_classes(g, k, cls);
+  hipStream_t st = device_form ? (hipStream_t)stream : set->members[0]->stream;
+  void* dsc = device_form ? const_cast<void*>(d_scalars) : set->members[0]->d_sc;
+  bool uploaded = device_form;
+  int uploads = 0, rc = 0, queued = 0;
+  int order[MLHIP_SET_MAX_MEMBERS];  // the members as their launches were queued
+  for (int c = 0; c < n_cls && !rc; c++) {
+    mlhip_msm_plan* plans[MLHIP_SET_MAX_MEMBERS];
+    void* dpts[MLHIP_SET_MAX_MEMBERS];
+    int m = 0;
+    for (int i = 0; i < k; i++)
+      if (cls[i] == c) {
+        plans[m] = set->members[i]->plan;
+        dpts[m] = set->members[i]->d_pts;
+        order[queued + m] = i;
+        m++;
+      }
+    const void* hs = uploaded ? nullptr : scalars;
+    mlhip_msm_plan* p = plans[0];
+    if (m >= 2) {
+      const int K = set_class_tiles(g[order[queued]], p->group == MLHIP_GROUP_G1, hs != nullptr, n);
+      rc = plan_train(plans, dpts, m, dsc, hs, mont, n, K, st);
+    } else if (hs) {
+      // a class of one that brings the scalars: as its own mlhip_bases_msm (streamed once the converted copy is there)
+      const int segments = stream_segments(p->group, n, p);
+      if (segments > 1 && p->points_static && p->conv_src == dpts[0] && n <= p->conv_n) {
+        rc = plan_stream(p, dpts[0], dsc, nullptr, hs, mont, n, segments, st);
+      } else {
+        if (hipMemcpy(dsc, hs, n * 32, hipMemcpyHostToDevice) != hipSuccess)
+          rc = mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy of MSM scalars failed");
+        if (!rc) rc = mlhip_msm_launch(p, dpts[0], dsc, mont, n, st);
+      }
+    } else {
+      rc = mlhip_msm_launch(p, dpts[0], dsc, mont, n, st);
+    }
+    if (hs) {
+      uploads++;
+      uploaded = true;
+    }
+    if (!rc) queued += m;
+  }
+  for (int q = 0; q < queued && !rc; q++) rc = mlhip_msm_finish(set->members[order[q]]->plan, out + out_off[order[q]], nullptr);
+  if (rc) {  // whatever is still queued may read the caller's scalars: let it drain, and leave every member usable
+    const std::string msg = mlhip_last_error();
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    for (mlhip_bases* m : set->members) m->plan->pending = false;
+    return mlhip_rt::fail(rc, msg);
+  }
+  const int r[4] = {k, n_cls, uploads, tables};
+  memcpy(set->route, r, sizeof(r));
+  return 0;
+}
+
+// mlhip_bases_create with group = MLHIP_GROUP_SET (include/mlhip_bases_set.h: mlhip_bases_set_create); *set is null
+int set_create(mlhip_bases* const* members, size_t k, mlhip_bases** set) {
+  if (k == 0 || k > MLHIP_SET_MAX_MEMBERS) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: a set has 1 .. 4 members");
+  if (!members) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: null member list");
+  for (size_t i = 0; i < k; i++) {
+    if (!members[i]) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: null member");
+    for (size_t j = 0; j < i; j++)
+      if (members[j] == members[i]) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: a handle is listed twice");
+  }
+  size_t n = 0, ptsz = 0;
+  for (size_t i = 0; i < k; i++) {
+    const mlhip_bases* m = members[i];
+    if (is_set(m)) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: a set cannot be a member of a set");
+    if (!m->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: a member is spread over several devices");
+    if (!m->plan || m->plan->device_result)
+      return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: a device-result handle cannot be a member (its result stays in device memory)");
+    if (m->curve != members[0]->curve) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: the members are of different curves");
+    if (m->device != members[0]->device) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_create: the members live on different devices");
+    n = i == 0 ? m->n : std::min(n, m->n);
+    ptsz += m->ptsz;
+  }
+  mlhip_bases* b = new mlhip_bases();
+  b->members.assign(members, members + k);
+  b->curve = members[0]->curve;
+  b->device = members[0]->device;
+  b->n = n;
+  b->ptsz = ptsz;
+  *set = b;
+  return 0;
+}
+
+// mlhip_bases_msm with scalars = NULL and scalars_mont = MLHIP_MSM_SET_ROUTE (mlhip_bases_set_route): entries written
+int set_route(mlhip_bases* set, int* info, size_t cap) {
+  if (!is_set(set)) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_set_route: the handle is not a set (mlhip_bases_set_create)");
+  std::lock_guard<std::mutex> lk(set->mu);
+  const int m = (int)std::min<size_t>(cap, 4);
+  for (int i = 0; i < m; i++) info[i] = set->route[i];
+  return m;
+}
+
 }  // namespace
 
 extern "C" {
 
 int mlhip_bases_destroy(mlhip_bases* b) {
   if (!b) return 0;
+  if (is_set(b)) {  // the members are not owned
+    delete b;
+    return 0;
+  }
   for (mlhip_bases* sh : b->shards) mlhip_bases_destroy(sh);
   if (b->shards.empty()) {
     (void)hipSetDevice(b->device);
@@ -216,6 +406,7 @@ int mlhip_bases_destroy(mlhip_bases* b) {
 int mlhip_bases_create(int curve, int group, const void* points, size_t n, int window_c, mlhip_bases** out) {
   if (!out) return mlhip_rt::fail(MLHIP_EINVAL, "null output pointer");
   *out = nullptr;
+  if (group == MLHIP_GROUP_SET) return set_create((mlhip_bases* const*)points, n, out);  // (curve and window_c: the members')
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   const size_t ptsz = ops->point_size(group);
@@ -262,6 +453,11 @@ int mlhip_bases_create_multi(int curve, int group, const int* devices, int n_dev
 
 int mlhip_bases_checked_subgroup(mlhip_bases* b) {
   if (!b) return 0;
+  if (is_set(b)) {
+    for (mlhip_bases* m : b->members)
+      if (!mlhip_bases_checked_subgroup(m)) return 0;
+    return 1;
+  }
   if (!b->shards.empty()) {
     for (mlhip_bases* s : b->shards)
       if (!s || !mlhip_bases_checked_subgroup(s)) return 0;
@@ -272,6 +468,11 @@ int mlhip_bases_checked_subgroup(mlhip_bases* b) {
 
 int mlhip_bases_msm(mlhip_bases* b, const void* scalars, int scalars_mont, size_t n, void* out_affine) {
   if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!scalars && scalars_mont == MLHIP_MSM_SET_ROUTE) return set_route(b, (int*)out_affine, n);
+  if (is_set(b)) {
+    if (n && !scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+    return set_msm(b, scalars, nullptr, scalars_mont, n, nullptr, out_affine);
+  }
   if (b->plan && b->plan->device_result)
     return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm: a device-result handle leaves its result in device memory; use mlhip_bases_msm_device");
   if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
@@ -294,22 +495,15 @@ int mlhip_bases_msm(mlhip_bases* b, const void* scalars, int scalars_mont, size_
   }
   if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   std::lock_guard<std::mutex> lk(b->mu);
-  {
-    // after the first MSM (which leaves the converted copy of the bases) large calls stream their scalars
-    const mlhip_msm_plan* p = b->plan;
-    const int segments = stream_segments(p->group, n, p);
-    if (segments > 1 && p->points_static && p->conv_src == b->d_pts && n <= p->conv_n) {
-      int rc = plan_stream(b->plan, b->d_pts, b->d_sc, nullptr, scalars, scalars_mont, n, segments, b->stream);
-      return rc ? rc : mlhip_msm_finish(b->plan, out_affine, nullptr);
-    }
-  }
-  if (hipMemcpy(b->d_sc, scalars, n * 32, hipMemcpyHostToDevice) != hipSuccess)
-    return mlhip_rt::fail(MLHIP_EHIP, "hipMemcpy of MSM scalars failed");
-  return mlhip_msm_run(b->plan, b->d_pts, b->d_sc, scalars_mont, n, b->stream, out_affine, nullptr);
+  return bases_msm_locked(b, scalars, scalars_mont, n, out_affine);
 }
 
 int mlhip_bases_msm_device(mlhip_bases* b, const void* d_scalars, int scalars_mont, size_t n, void* stream, void* out_affine) {
   if (!b || !out_affine) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (is_set(b)) {
+    if (n && !d_scalars) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+    return set_msm(b, nullptr, d_scalars, scalars_mont, n, stream, out_affine);
+  }
   if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_device: the handle is spread over several devices");
   if (n > b->n) return mlhip_rt::fail(MLHIP_EINVAL, "more scalars than resident bases");
   // (a device-result handle: out_affine is a device pointer, written in stream order -- the all-zero point too -- and the
@@ -328,6 +522,7 @@ int mlhip_bases_msm_device(mlhip_bases* b, const void* d_scalars, int scalars_mo
 int mlhip_bases_msm_batch_device(mlhip_bases* b, const void* d_scalars, int scalars_mont, const uint32_t* base_index,
                                  const uint64_t* offsets, size_t k, void* stream, void* d_out_affine) {
   if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  if (int rc_set = reject_set(b, "mlhip_bases_msm_batch")) return rc_set;
   int rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
@@ -345,6 +540,7 @@ int mlhip_bases_msm_batch_device(mlhip_bases* b, const void* d_scalars, int scal
 int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont, const uint32_t* base_index, const uint64_t* offsets,
                           size_t k, void* out_affine) {
   if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
+  if (int rc_set = reject_set(b, "mlhip_bases_msm_batch")) return rc_set;
   int rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
@@ -370,6 +566,7 @@ int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont,
 
 int mlhip_bases_batch_tabled(mlhip_bases* b, size_t* n_tabled) {
   if (!b || !n_tabled) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (int rc_set = reject_set(b, "mlhip_bases_batch_tabled")) return rc_set;
   if (!b->shards.empty()) {
     *n_tabled = 0;
     return 0;

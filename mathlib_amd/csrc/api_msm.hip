@@ -442,6 +442,23 @@ int plan_stream(mlhip_msm_plan* p, void* d_pts, void* d_sc, const void* points, 
   return rc;
 }
 
+// a class of a set of resident-bases handles (api_bases.hip): the plan runs the segment train, on the two-level sort
+bool plan_can_train(const mlhip_msm_plan* p) { return plan_can_stream(p) && p->sort_low > 0; }
+
+// k plans of one geometry over one scalar vector (msm_plan.h: plan_stream_train); h_scalars = nullptr: they are at d_scalars
+int plan_train(mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars, int mont,
+               size_t n, int segments, hipStream_t st) {
+  for (int j = 0; j < k; j++)
+    if (int rc_order = plan_begin_on(plans[j], st)) return rc_order;
+  int rc = curve_ops(plans[0]->curve)->plan_train(plans, d_points, k, d_scalars, h_scalars, mont, n, segments, st);
+  if (rc) {  // as plan_stream: let whatever still reads the caller's buffers drain, and leave the plans reusable
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+    for (int j = 0; j < k; j++) plans[j]->pending = false;
+  }
+  return rc;
+}
+
 int host_group_sum(int curve, int group, const void* pts, size_t n, void* out) {
   return group == MLHIP_GROUP_G1 ? mlhip_g1_sum(curve, pts, n, out) : mlhip_g2_sum(curve, pts, n, out);
 }

@@ -26,6 +26,7 @@ void host_parallel(int njobs, void (*fn)(const void*, int, void*), const void* i
   } while (0)
 
 #include "msm_segments.h"  // MLHIP_MAX_SEGMENTS, and how an MSM is cut into segments / tiles
+#include "msm_set.h"       // ... and how the members of a set of resident-bases handles share their sorts
 
 // MLHIP_BUILD_ALT=1 (python -m mathlib_amd.build --alt -> libmlhip_alt.so): the test build.  It also contains the second
 // implementations the parity tests compare the default kernels with -- boundary-form (32-bit limb) bucket accumulation and
@@ -169,6 +170,10 @@ struct mlhip_g2_prepared_tables {
   X(C, int, plan_shared,                                                                                                  \
     (mlhip_msm_plan * g1, mlhip_msm_plan * g2, void* d_points_g1, void* d_points_g2, void* d_scalars,                     \
      const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n, hipStream_t st))        \
+  /* k plans of one geometry, of either group, over one scalar vector (msm_plan.h: plan_stream_train; resident points) */  \
+  X(C, int, plan_train,                                                                                                   \
+    (mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars, int mont,        \
+     size_t n, int segments, hipStream_t st))                                                                             \
   X(C, int, pairing,                                                                                                      \
     (int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out, hipStream_t st))  \
   X(C, int, fp_mul, (const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st))                \

@@ -61,6 +61,10 @@ void plan_reserve_edwards(mlhip_msm_plan* p);
 int stream_segments(int group, size_t n, const mlhip_msm_plan* plan);
 int plan_stream(mlhip_msm_plan* p, void* d_pts, void* d_sc, const void* points, const void* scalars, int mont, size_t n,
                 int segments, hipStream_t st);
+// a set of resident-bases handles: can the plan be a member of a class (msm_set.h), and the train of one class
+bool plan_can_train(const mlhip_msm_plan* p);
+int plan_train(mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars, int mont,
+               size_t n, int segments, hipStream_t st);
 int host_group_sum(int curve, int group, const void* pts, size_t n, void* out);
 // offsets of a batch: k + 1 nondecreasing host entries from 0 (k = 0: nothing to check)
 int check_batch_offsets(const uint64_t* offsets, size_t k);

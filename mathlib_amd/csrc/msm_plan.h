@@ -885,6 +885,75 @@ int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* 
   return stream_end<C, F>(p, cx, st);
 }
 
+// A class of k plans of ONE window geometry, of either group, over one scalar vector: every tile is sorted once -- in the
+// first plan, or with sort-ahead in its helper record -- and accumulated once per plan, plan after plan, on one stream.
+// stream_end of a plan is queued as soon as its last tile is (the last plan's after the loop), so that its reduction, its
+// copy to the host and the host tail of its result run under the next plan's accumulation.
+//   d_points[j] / h_points[j]   as plan_stream's, per plan (a folded plan brings none: its table)
+//   h_scalars                   uploaded once, by the first plan's tiles; `schedule`: a G1 first plan cuts them as plan_stream does
+// Folded plans: the cuts are segment_cuts' over the class's fold_tile, row0 = fold_row(p, off) is taken per plan, and the
+// slices of long buckets gather from each plan's own d_points28 through the sorter's lists (launch_big_slices).
+template <class C>
+int plan_stream_train(mlhip_msm_plan* const* ps, void* const* d_points, const void* const* h_points, int k, void* d_scalars,
+                      const void* h_scalars, int mont, size_t n, int K, bool schedule, hipStream_t st) {
+  typedef FpField<C> F1;
+  typedef Fp2Field<C> F2;
+  if (k < 1) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: no plan");
+  mlhip_msm_plan* p0 = ps[0];
+  for (int j = 1; j < k; j++)
+    if (ps[j]->fold != p0->fold || ps[j]->c != p0->c || ps[j]->Wd != p0->Wd || ps[j]->fold_tile != p0->fold_tile ||
+        ps[j]->W != p0->W || ps[j]->M != p0->M || ps[j]->bits != p0->bits)
+      return mlhip_rt::fail(MLHIP_EINVAL, "the plans of a shared-scalar MSM need the same window width and scalar width");
+  auto g1 = [&](int j) { return ps[j]->group == MLHIP_GROUP_G1; };
+  std::vector<StreamCtx> cx(k);
+  bool points_travel = false;
+  for (int j = 0; j < k; j++) {
+    cx[j].d_points = d_points[j];
+    cx[j].d_scalars = d_scalars;
+    cx[j].h_points = h_points ? h_points[j] : nullptr;
+    cx[j].h_scalars = j == 0 ? h_scalars : nullptr;
+    cx[j].mont = mont;
+    cx[j].n = n;
+    cx[j].K = K;
+    points_travel = points_travel || cx[j].h_points != nullptr;
+  }
+  if (schedule && h_scalars && g1(0)) {
+    stream_schedule(cx[0], cx[0].h_points != nullptr, schedule_tile(p0->fold, p0->fold_tile, plan_use_edwards<C, F1>(p0)), p0->fold != 0);
+    for (int j = 1; j < k; j++) static_cast<SegmentCuts&>(cx[j]) = cx[0];  // (before segment_cuts: every plan cuts alike)
+  }
+  for (int j = 0; j < k; j++) {
+    int rc = g1(j) ? stream_begin<C, F1>(ps[j], cx[j], st, 1) : stream_begin<C, F2>(ps[j], cx[j], st, 1);
+    if (rc) return rc;
+  }
+  bool ahead = false;
+  if (!h_scalars && !points_travel && cx[0].K >= 2) {
+    int rc = sort_ahead_prepare<C>(p0, cx[0].seg, ahead);
+    if (rc) return rc;
+  }
+  if (ahead) HIPCHK(hipStreamWaitEvent(p0->sort_stream, p0->ev_fork, 0));
+  auto end = [&](int j) { return g1(j) ? stream_end<C, F1>(ps[j], cx[j], st) : stream_end<C, F2>(ps[j], cx[j], st); };
+  for (int s = 0; s < cx[0].K; s++) {
+    const mlhip_msm_plan* lists = p0;  // whose entry lists the later plans' tiles read
+    if (ahead) {
+      int rc = sort_ahead_tile<C>(p0, cx[0], s);
+      if (rc) return rc;
+      HIPCHK(hipStreamWaitEvent(st, p0->ev_sorted[s & 1], 0));
+      lists = p0->sort_helper[s & 1];
+    }
+    for (int j = 0; j < k; j++) {
+      const mlhip_msm_plan* sorter = j == 0 ? (ahead ? lists : nullptr) : lists;
+      int rc = g1(j) ? stream_tile<C, F1>(ps[j], cx[j], s, st, sorter) : stream_tile<C, F2>(ps[j], cx[j], s, st, sorter);
+      if (rc) return rc;
+      if (s + 1 == cx[0].K && j + 1 < k) {
+        rc = end(j);
+        if (rc) return rc;
+      }
+    }
+    if (ahead) HIPCHK(hipEventRecord(p0->ev_lists_free[s & 1], st));
+  }
+  return end(k - 1);
+}
+
 // The G1 MSM and the G2 MSM of ONE scalar vector (device-resident inputs; BASELINE configs[3], a Groth16 prover's
 // B-query): the entry lists of a tile depend on the scalars and the window geometry only, so every tile is sorted once
 // (in the G1 plan) and accumulated twice.  One stream, tile by tile: sort, G1 accumulation, G2 accumulation.
@@ -894,53 +963,14 @@ template <class C>
 int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1, void* d_points_g2, void* d_scalars,
                        const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n,
                        hipStream_t st) {
-  typedef FpField<C> F1;
-  typedef Fp2Field<C> F2;
   if (p1->c != p2->c || p1->W != p2->W || p1->M != p2->M || p1->bits != p2->bits)
     return mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width and scalar width");
+  // (plans over shifted-base tables belong to resident-bases handles: their shared-scalar MSM is a set's, mlhip_bases_set_create)
   if (p1->fold || p2->fold) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
-  const int K = shared_segments(h_scalars != nullptr, n);
-  StreamCtx c1, c2;
-  c1.d_points = d_points_g1;
-  c2.d_points = d_points_g2;
-  c1.d_scalars = c2.d_scalars = d_scalars;
-  c1.h_points = h_points_g1;
-  c2.h_points = h_points_g2;
-  c1.h_scalars = h_scalars;  // uploaded once, by the G1 plan's tiles
-  c1.mont = c2.mont = mont;
-  c1.n = c2.n = n;
-  c1.K = c2.K = K;
-  int rc = stream_begin<C, F1>(p1, c1, st, 1);
-  if (rc) return rc;
-  rc = stream_begin<C, F2>(p2, c2, st, 1);
-  if (rc) return rc;
-  bool ahead = false;
-  if (!h_scalars && !h_points_g1 && !h_points_g2 && K >= 2) {
-    rc = sort_ahead_prepare<C>(p1, c1.seg, ahead);
-    if (rc) return rc;
-  }
-  if (ahead) HIPCHK(hipStreamWaitEvent(p1->sort_stream, p1->ev_fork, 0));
-  for (int s = 0; s < c1.K; s++) {
-    const mlhip_msm_plan* lists = p1;  // whose entry lists the G2 tile reads
-    if (ahead) {
-      rc = sort_ahead_tile<C>(p1, c1, s);
-      if (rc) return rc;
-      HIPCHK(hipStreamWaitEvent(st, p1->ev_sorted[s & 1], 0));
-      lists = p1->sort_helper[s & 1];
-    }
-    rc = stream_tile<C, F1>(p1, c1, s, st, ahead ? lists : nullptr);
-    if (rc) return rc;
-    if (s + 1 == c1.K) {
-      // G1 is complete: its reduction and its copy to the host go ahead of G2's last accumulation, so that the host
-      // tail of the G1 result runs under it
-      rc = stream_end<C, F1>(p1, c1, st);
-      if (rc) return rc;
-    }
-    rc = stream_tile<C, F2>(p2, c2, s, st, lists);
-    if (rc) return rc;
-    if (ahead) HIPCHK(hipEventRecord(p1->ev_lists_free[s & 1], st));
-  }
-  return stream_end<C, F2>(p2, c2, st);
+  mlhip_msm_plan* ps[2] = {p1, p2};
+  void* dp[2] = {d_points_g1, d_points_g2};
+  const void* hp[2] = {h_points_g1, h_points_g2};
+  return plan_stream_train<C>(ps, dp, hp, 2, d_scalars, h_scalars, mont, n, shared_segments(h_scalars != nullptr, n), false, st);
 }
 
 // What the tail kernel needs of a plan (msm_tail.h: MsmTailArgs).

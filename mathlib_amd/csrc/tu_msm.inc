@@ -23,6 +23,10 @@ int MLHIP_TU_FN(plan_shared)(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d_poi
                             hipStream_t st) {
   return plan_stream_shared<MLHIP_TU_CURVE>(g1, g2, d_points_g1, d_points_g2, d_scalars, h_points_g1, h_points_g2, h_scalars, mont, n, st);
 }
+int MLHIP_TU_FN(plan_train)(mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars,
+                           int mont, size_t n, int segments, hipStream_t st) {
+  return plan_stream_train<MLHIP_TU_CURVE>(plans, d_points, nullptr, k, d_scalars, h_scalars, mont, n, segments, true, st);
+}
 int MLHIP_TU_FN(scalar_mul)(int group, const void* d_points, size_t point_stride, const void* d_scalars, int mont,
                               size_t n, void* d_out, hipStream_t st, bool subgroup) {
   if (group == MLHIP_GROUP_G1)

@@ -534,6 +534,15 @@ class Curve:
         """Upload a G1 point table once; Bases.MultiScalarMul(scalars) then moves only the scalars."""
         return Bases(self, points)
 
+    def NewBasesG2(self, points: Sequence[G2]) -> "Bases":
+        """The same for a G2 point table (a Groth16 prover's B2 query)."""
+        return Bases(self, points, GROUP_G2)
+
+    def NewBasesSet(self, *members: "Bases") -> "BasesSet":
+        """A set of 1..4 resident tables of this curve, any mix of G1 and G2: BasesSet.MultiScalarMul(scalars) returns every
+        member's MSM over one scalar vector from one upload and one sort per tile (include/mlhip.h: mlhip_bases_set_create)."""
+        return BasesSet(self, members)
+
     def NewG2Prepared(self, points: Sequence[G2]) -> "G2Prepared":
         """Prepare fixed G2 points once (the generator and an issuer key, say); G2Prepared.PairingBatch(g1_lists) then runs
         the verifier's Pairing2 + FExp over many proofs without any G2 arithmetic (include/mlhip.h: mlhip_g2_prepared_*)."""
@@ -681,23 +690,31 @@ def NewCurve(name: str, **kw) -> Curve:
 
 
 class Bases:
-    """Resident G1 bases (mlhip_bases_*): the additive API a prover with a fixed SRS would use."""
+    """Resident bases (mlhip_bases_*): the additive API a prover with a fixed SRS would use.  G1 (Curve.NewBases) or G2
+    (Curve.NewBasesG2)."""
 
-    def __init__(self, curve: "Curve", points: Sequence[G1]):
+    def __init__(self, curve: "Curve", points: Sequence[G1], group: int = GROUP_G1):
         self.curve = curve
+        self.group = group
         self.n = len(points)
         self._h = ctypes.c_void_p()
         blob = b"".join(p.raw for p in points)
         self._lib = _concrete()  # the handle stays with the library that made it
-        check(self._lib.mlhip_bases_create(curve.id, GROUP_G1, blob, self.n, curve.window_c, ctypes.byref(self._h)))
+        check(self._lib.mlhip_bases_create(curve.id, group, blob, self.n, curve.window_c, ctypes.byref(self._h)))
 
-    def MultiScalarMul(self, scalars: Sequence[Zr]) -> G1:
+    def _point(self, raw: bytes):
+        return G1(raw, self.curve) if self.group == GROUP_G1 else G2(raw, self.curve)
+
+    def _point_bytes(self) -> int:
+        return self.curve.g1_bytes if self.group == GROUP_G1 else self.curve.g2_bytes
+
+    def MultiScalarMul(self, scalars: Sequence[Zr]):
         if len(scalars) > self.n:
             raise IndexError("MultiScalarMul: more scalars than resident bases")
-        out = ctypes.create_string_buffer(self.curve.g1_bytes)
+        out = ctypes.create_string_buffer(self._point_bytes())
         c = self.curve
         check(self._lib.mlhip_bases_msm(self._h, c._scalars(scalars), 1 if c.scalars_mont else 0, len(scalars), out))
-        return G1(out.raw, c)
+        return self._point(out.raw)
 
     def MultiScalarMulBatch(self, scalar_lists: Sequence[Sequence[Zr]], index_lists=None) -> List[G1]:
         """out[i] = sum_j [scalar_lists[i][j]] B[index_lists[i][j]] (without index lists: B[j], as MultiScalarMul) for many small
@@ -717,8 +734,8 @@ class Bases:
                 if any(i < 0 or i >= self.n for i in ix):
                     raise IndexError("MultiScalarMulBatch: base index out of range")
         scs = b"".join(c._scalars(b) for b in scalar_lists)
-        raw = _lib.bases_msm_batch(self._lib, self._h, c.g1_bytes, scs, c.scalars_mont, lengths, index_lists)
-        return [G1(r, c) for r in raw]
+        raw = _lib.bases_msm_batch(self._lib, self._h, self._point_bytes(), scs, c.scalars_mont, lengths, index_lists)
+        return [self._point(r) for r in raw]
 
     def BatchTabled(self) -> int:
         """the number of leading bases that have MultiScalarMulBatch tables (include/mlhip.h: mlhip_bases_batch_tabled)"""
@@ -734,6 +751,44 @@ class Bases:
 
         plan = self._lib.mlhip_bases_plan(self._h)
         return bool(plan) and plan_timings(self._lib, plan).get("tables") == 1.0
+
+    def Close(self) -> None:
+        if self._h:
+            self._lib.mlhip_bases_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+class BasesSet:
+    """A set of resident tables that share one scalar vector (mlhip_bases_set_create).  The members stay usable on their own and
+    must outlive the set: the set keeps references to them."""
+
+    def __init__(self, curve: "Curve", members: Sequence[Bases]):
+        self.curve = curve
+        self.members = list(members)
+        self._lib = _concrete()
+        if any(m._lib is not self._lib for m in self.members):
+            raise ValueError("NewBasesSet: a member was made by another build of the library")
+        self._h = _lib.bases_set_create(self._lib, [m._h for m in self.members])
+        self.n = min(m.n for m in self.members)
+
+    def MultiScalarMul(self, scalars: Sequence[Zr]) -> list:
+        """[member.MultiScalarMul(scalars) for every member], G1 or G2 as the member is"""
+        if len(scalars) > self.n:
+            raise IndexError("MultiScalarMul: more scalars than the smallest member's resident bases")
+        c = self.curve
+        raw = _lib.bases_set_msm(self._lib, self._h, [m._point_bytes() for m in self.members], c._scalars(scalars), c.scalars_mont,
+                                 len(scalars))
+        return [m._point(r) for m, r in zip(self.members, raw)]
+
+    def Route(self):
+        """(members, sort trains per tile, uploads of the scalars, 1 iff every member read shifted-base tables) of the last call"""
+        return _lib.bases_set_route(self._lib, self._h)
 
     def Close(self) -> None:
         if self._h:
