@@ -164,6 +164,18 @@ func (c *Curve) MultiScalarMul(a []driver.G1, b []driver.Zr) driver.G1 {
 // identity.  A batch of fewer than MinDeviceMSMBatch pairs in all stays on the embedded gurvy driver, and a segment of
 // MaxBatchSegment pairs or more goes to MultiScalarMul on its own (mlhip_msm_g1 is faster there).
 func (c *Curve) MultiScalarMulBatch(a [][]driver.G1, b [][]driver.Zr) []driver.G1 {
+	return c.msmBatchG1(a, b, false)
+}
+
+// MultiScalarMulBatchSubgroup is MultiScalarMulBatch for points the caller knows to be in G1 (decoded with the subgroup
+// check, issuer keys, generators, outputs of earlier MSMs): the same results with half of the chunks' doublings, from the
+// curve's endomorphism and a split of every scalar (mlhip_msm_batch_subgroup, DESIGN.md section 19).  A point outside G1
+// gives an undefined result for its own segment; MultiScalarMulBatch accepts any point of the curve.
+func (c *Curve) MultiScalarMulBatchSubgroup(a [][]driver.G1, b [][]driver.Zr) []driver.G1 {
+	return c.msmBatchG1(a, b, true)
+}
+
+func (c *Curve) msmBatchG1(a [][]driver.G1, b [][]driver.Zr, subgroup bool) []driver.G1 {
 	if len(a) != len(b) {
 		panic("hip: MultiScalarMulBatch length mismatch")
 	}
@@ -200,6 +212,10 @@ func (c *Curve) MultiScalarMulBatch(a [][]driver.G1, b [][]driver.Zr) []driver.G
 	}
 	res := make([]bls12381.G1Affine, k)
 	check(func() C.int {
+		if subgroup {
+			return C.mlhip_msm_batch_subgroup(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1, unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1,
+				(*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k), unsafe.Pointer(&res[0]))
+		}
 		return C.mlhip_msm_batch(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1, unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1,
 			(*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k), unsafe.Pointer(&res[0]))
 	})
@@ -208,6 +224,60 @@ func (c *Curve) MultiScalarMulBatch(a [][]driver.G1, b [][]driver.Zr) []driver.G
 			out[i] = c.MultiScalarMul(a[i], b[i])
 		} else {
 			out[i] = &gurvy381.G1{G1Affine: res[i]}
+		}
+	}
+	return out
+}
+
+// MultiScalarMulG2BatchSubgroup returns MultiScalarMulG2(a[i], b[i]) for every i, for points the caller knows to be in G2,
+// with one device call (mlhip_msm_batch_subgroup: a quarter of the chunks' doublings).  The length rules are
+// MultiScalarMulBatch's; a batch of fewer than MinDeviceMSMBatch pairs in all, and a segment of MaxBatchSegment pairs or more,
+// go to MultiScalarMulG2.
+func (c *Curve) MultiScalarMulG2BatchSubgroup(a [][]driver.G2, b [][]driver.Zr) []driver.G2 {
+	if len(a) != len(b) {
+		panic("hip: MultiScalarMulG2BatchSubgroup length mismatch")
+	}
+	k := len(a)
+	out := make([]driver.G2, k)
+	total := 0
+	for i := range a {
+		if len(b[i]) < len(a[i]) {
+			_ = b[i][len(a[i])-1] // the reference's index out of range
+		}
+		if len(b[i]) == len(a[i]) && len(a[i]) < MaxBatchSegment {
+			total += len(a[i])
+		}
+	}
+	if total < MinDeviceMSMBatch {
+		for i := range a {
+			out[i] = c.MultiScalarMulG2(a[i], b[i])
+		}
+		return out
+	}
+	offsets := make([]uint64, k+1)
+	points := make([]bls12381.G2Affine, 0, total)
+	scalars := make([]fr.Element, 0, total)
+	for i := range a {
+		offsets[i+1] = offsets[i]
+		if len(b[i]) != len(a[i]) || len(a[i]) >= MaxBatchSegment {
+			continue // the identity, or (below) a segment of its own
+		}
+		for j := range a[i] {
+			points = append(points, a[i][j].(*gurvy381.G2).G2Affine)
+			scalars = append(scalars, gurvy381.ZrValue(b[i][j]))
+		}
+		offsets[i+1] += uint64(len(a[i]))
+	}
+	res := make([]bls12381.G2Affine, k)
+	check(func() C.int {
+		return C.mlhip_msm_batch_subgroup(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2, unsafe.Pointer(&points[0]), unsafe.Pointer(&scalars[0]), 1,
+			(*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k), unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		if len(b[i]) == len(a[i]) && len(a[i]) >= MaxBatchSegment {
+			out[i] = c.MultiScalarMulG2(a[i], b[i])
+		} else {
+			out[i] = &gurvy381.G2{G2Affine: res[i]}
 		}
 	}
 	return out

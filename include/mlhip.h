@@ -423,6 +423,46 @@ MLHIP_API int mlhip_msm_batch_device(int curve, int group, const void* d_points,
 MLHIP_API int mlhip_msm_batch(int curve, int group, const void* points, const void* scalars, int scalars_mont,
                               const uint64_t* offsets, size_t k, void* out_affine);
 
+/* ---- batched MSMs over points promised in G1 / G2: endomorphism-split Straus chunks ------------------------------------------
+ * The promise of "points promised in G1 / G2" above for mlhip_msm_batch / mlhip_msm_batch_device: a verifier's points are
+ * decoded with subgroup_check = 1, are issuer keys or generators, or come out of earlier MSMs.  The library never takes
+ * this route by itself.
+ *
+ * Result.  With the promise kept -- every point is in the prime-order subgroup or is the point at infinity (all zero) --
+ * the bytes of the plain call on the same inputs: every offsets shape, scalars_mont, unreduced 256-bit scalars, empty
+ * segments, every chunk length.  A point outside the subgroup gives an undefined RESULT for the segment that holds it and
+ * for no other, never a fault: no address depends on point data.
+ *
+ * How it is said.  The symbol table does not grow, and `group` stays what it was (both batch entry points go on rejecting
+ * MLHIP_GROUP_SUBGROUP values): the promise travels in the CURVE ID of exactly these two entry points, as
+ * MLHIP_CURVE_SUBGROUP_POINTS(curve_id) below; they take the flag off and read the rest as before.  Everywhere else the
+ * flagged ids are unknown curves, as they were here, and nothing inside the library produces them.  include/mlhip_subgroup.h
+ * wraps this in two inline functions that take a plain curve id: mlhip_msm_batch_subgroup(curve_id, group, points, scalars,
+ * scalars_mont, offsets, k, out_affine) and mlhip_msm_batch_subgroup_device(.., d_out_affine, stream).
+ *
+ * Range.  curve_id = 0, 1 or 2; anything else makes the macro -1, which is MLHIP_EINVAL ("unknown curve id").  Every other
+ * argument rule is the plain call's.
+ *
+ * How it runs (msm_batch_endo.h).  Only the Straus chunks change; segments on the bucket route, the sum
+ * passes and the scratch are the plain call's.  Per pair, where the plain chunk spends 256 / P + 71 group operations: G1 of
+ * the BLS12 curves 128 / P + 7 + <= 66 (s = a + b x^2, joint signed 4-bit windows over one table, b's additions scale X by
+ * beta and flip Y); G2 of the BLS12 curves 64 / P + 11 + <= 64 (four digits base |x| over Q .. psi^3 Q, a 15-entry table, 64
+ * steps of one doubling); G2 of BN254 128 / P + 13 + <= 64 (two digits base 6 x^2, 64 steps of two doublings).  The G2 table
+ * is 15 XYZZ per pair in scratch, so the split chunks are compiled for P = 1, 2, 4 there: at MLHIP_MSM_BATCH_CHUNK=8 a flagged
+ * G2 call runs the plain chunk kernel.  BN254 G1 has no split: the flagged call is accepted and runs the plain kernel.
+ * MLHIP_MSM_BATCH_ENDO=0 sends every flagged call to the plain chunk kernels (second implementation, A/B).
+ * Measured (profiles/msm_batch_endo_ab.txt): flagged call against plain call in one process on one
+ * MI355X, same device buffers, same bytes in every cell; 2^10 .. 2^16 segments of 2 .. 64 pairs.  Flagged / plain time at the
+ * default P = 4, smallest .. largest over the grid (counted from the operations above): G1 0.79 .. 0.90 BLS12-381 and
+ * 0.78 .. 0.89 BLS12-377 (0.78); G2 0.65 .. 0.86 and 0.64 .. 0.84 (0.67), BN254 0.79 .. 0.97 (0.81); from 2^20 pairs per call on,
+ * the device full, 0.88 / 0.86, 0.86 / 0.84 and 0.97.  At P = 1: G1 0.68 .. 0.77 (0.61), G2 0.51 .. 0.62 (0.43), BN254 0.71 .. 0.80
+ * (0.63).  The measured ratios lie above the counted ones because the split removes doublings only, the cheapest operation
+ * (9 field products against 14 of an addition), and G2 builds 11 or 13 more table entries per pair.  Every (curve, group) with
+ * a split is ahead of the plain call in every cell at the default P by more than two identical plain runs differ (at most
+ * 0.015), so all five take it; BN254 G1 reads 1.00.  Flagged calls keep the default P = 4: below ~2^17 pairs in all P = 1 is
+ * faster, as for the plain call, but from 2^18 pairs on it falls behind the plain call at its default. */
+#define MLHIP_CURVE_SUBGROUP_POINTS(curve_id) ((curve_id) >= 0 && (curve_id) <= 2 ? ((curve_id) | 0x100) : -1)
+
 /* ---- resident bases (upload-once point table, only the scalars travel per call) ----------
  * For callers that cannot hold device pointers themselves (the Go shim): the points are uploaded once, every
  * mlhip_bases_msm() uploads n x 32 bytes of scalars and returns sum_i [s_i] P_i over the first n bases (n <= the
@@ -684,6 +724,7 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *     MLHIP_G2_KC=1                    G2 buckets split by coordinate (one-lane Karatsuba Fp2 products; measured 3-5 % slower)
  *     MLHIP_PAIRING_ONE_LANE=1, MLHIP_PAIRING_SAT=1, MLHIP_SCALAR_MUL_ONE_LANE=1   one-lane / saturated-limb pairing and G2.Mul kernels
  *     MLHIP_SCALAR_MUL_ENDO=0          batched Mul with MLHIP_GROUP_SUBGROUP: the plain double-and-add kernels (also the A/B switch)
+ *     MLHIP_MSM_BATCH_ENDO=0           mlhip_msm_batch* with MLHIP_CURVE_SUBGROUP_POINTS: the plain chunk kernels (also the A/B switch)
  *   tests only
  *     MLHIP_FAULT_INJECT=sort_helper_alloc   the sort-ahead helper allocation "fails" (tests/test_gpu_parity.py)
  */

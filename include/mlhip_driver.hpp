@@ -18,7 +18,7 @@
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
 //   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, MulBatchSubgroup, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
-//             MultiScalarMulBatch, MultiScalarMulG2Batch, Mul2Batch, Bases::MultiScalarMulBatch, BasesG2, BasesSet::MultiScalarMul, SumG1, SumG2
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, MultiScalarMulBatchSubgroup, MultiScalarMulG2BatchSubgroup, Mul2Batch, Bases::MultiScalarMulBatch, BasesG2, BasesSet::MultiScalarMul, SumG1, SumG2
 #pragma once
 #include <algorithm>
 #include <array>
@@ -551,6 +551,16 @@ class Curve {
   std::vector<G2> MultiScalarMulG2Batch(const std::vector<std::vector<G2>>& a, const std::vector<std::vector<Zr>>& b) const {
     return msm_batch(MLHIP_GROUP_G2, g2_bytes, a, b, "MultiScalarMulG2Batch");
   }
+  // The same for points the caller knows to be in G1 / G2 (decoded with the subgroup check, issuer keys, generators,
+  // outputs of earlier MSMs): the same results with half (G2 of a BLS12 curve: a quarter) of the chunks' doublings, from the
+  // curve's endomorphism and a split of every scalar (mlhip_msm_batch_subgroup).  A point outside the subgroup gives an
+  // undefined result for its own segment; MultiScalarMulBatch and MultiScalarMulG2Batch accept any point of the curve.
+  std::vector<G1> MultiScalarMulBatchSubgroup(const std::vector<std::vector<G1>>& a, const std::vector<std::vector<Zr>>& b) const {
+    return msm_batch(MLHIP_GROUP_G1, g1_bytes, a, b, "MultiScalarMulBatchSubgroup", true);
+  }
+  std::vector<G2> MultiScalarMulG2BatchSubgroup(const std::vector<std::vector<G2>>& a, const std::vector<std::vector<Zr>>& b) const {
+    return msm_batch(MLHIP_GROUP_G2, g2_bytes, a, b, "MultiScalarMulG2BatchSubgroup", true);
+  }
   // out[i] = g[i].Mul2(e[i], q[i], f[i]): segments of two pairs
   std::vector<G1> Mul2Batch(const std::vector<G1>& g, const std::vector<Zr>& e, const std::vector<G1>& q,
                             const std::vector<Zr>& f) const {
@@ -736,7 +746,7 @@ class Curve {
   }
   template <class P>
   std::vector<P> msm_batch(int group, size_t size, const std::vector<std::vector<P>>& a, const std::vector<std::vector<Zr>>& b,
-                           const char* what) const {
+                           const char* what, bool subgroup = false) const {
     if (a.size() != b.size()) throw std::invalid_argument(std::string(what) + ": as many point lists as scalar lists");
     std::vector<P> out;
     const size_t k = a.size();
@@ -757,7 +767,8 @@ class Curve {
       }
     }
     Bytes o(size * k);
-    check(mlhip_msm_batch(id, group, pts.data(), sc.data(), scalars_mont ? 1 : 0, offsets.data(), k, o.data()));
+    check(mlhip_msm_batch(subgroup ? MLHIP_CURVE_SUBGROUP_POINTS(id) : id, group, pts.data(), sc.data(), scalars_mont ? 1 : 0,
+                          offsets.data(), k, o.data()));
     for (size_t i = 0; i < k; i++) {
       P g;
       g.curve = this;

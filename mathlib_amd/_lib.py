@@ -283,15 +283,17 @@ def batch_offsets(lengths):
     return offs
 
 
-def msm_batch(curve: int, group: int, points: bytes, scalars: bytes, scalars_mont: bool, lengths):
-    """mlhip_msm_batch: one affine point (bytes) per segment; segment i has lengths[i] consecutive pairs"""
+def msm_batch(curve: int, group: int, points: bytes, scalars: bytes, scalars_mont: bool, lengths, subgroup: bool = False):
+    """mlhip_msm_batch: one affine point (bytes) per segment; segment i has lengths[i] consecutive pairs.  subgroup: the
+    caller promises that every point is in the prime-order subgroup or at infinity (mlhip_msm_batch_subgroup)"""
     _, g1, g2, _ = sizes(curve)
     ptsz = g1 if group == GROUP_G1 else g2
     k = len(lengths)
     if k == 0:
         return []
     out = ctypes.create_string_buffer(k * ptsz)
-    check(load().mlhip_msm_batch(curve, group, points, scalars, 1 if scalars_mont else 0, batch_offsets(lengths), k, out))
+    call = msm_batch_subgroup if subgroup else (lambda lib, *args: lib.mlhip_msm_batch(*args))
+    check(call(load(), curve, group, points, scalars, 1 if scalars_mont else 0, batch_offsets(lengths), k, out))
     raw = out.raw
     return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
 
@@ -344,6 +346,23 @@ def scalar_mul_subgroup_device(lib, curve: int, group: int, d_points, point_stri
                                d_out, stream) -> int:
     """include/mlhip_subgroup.h: the same on device pointers, asynchronous and in order on `stream`"""
     return lib.mlhip_scalar_mul_device(curve, GROUP_SUBGROUP(group), d_points, point_stride, d_scalars, scalars_mont, n, d_out, stream)
+
+
+def CURVE_SUBGROUP_POINTS(curve: int) -> int:
+    """MLHIP_CURVE_SUBGROUP_POINTS of include/mlhip.h: the curve id of mlhip_msm_batch / _device with the caller's promise that
+    every point is in the prime-order subgroup (or at infinity); -1, which the library rejects, for any other curve id"""
+    return (curve | 0x100) if 0 <= curve <= 2 else -1
+
+
+def msm_batch_subgroup(lib, curve: int, group: int, points, scalars, scalars_mont: int, offsets, k: int, out) -> int:
+    """include/mlhip_subgroup.h: mlhip_msm_batch for points promised in G1 / G2 (the return code, as the C function)"""
+    return lib.mlhip_msm_batch(CURVE_SUBGROUP_POINTS(curve), group, points, scalars, scalars_mont, offsets, k, out)
+
+
+def msm_batch_subgroup_device(lib, curve: int, group: int, d_points, d_scalars, scalars_mont: int, offsets, k: int, d_out,
+                              stream) -> int:
+    """include/mlhip_subgroup.h: the same on device pointers, asynchronous and in order on `stream`"""
+    return lib.mlhip_msm_batch_device(CURVE_SUBGROUP_POINTS(curve), group, d_points, d_scalars, scalars_mont, offsets, k, d_out, stream)
 
 
 WINDOW_DEVICE_RESULT = 1 << 20

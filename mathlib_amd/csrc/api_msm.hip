@@ -166,6 +166,14 @@ bool take_subgroup_promise(int& group) {
   return true;
 }
 
+// MLHIP_CURVE_SUBGROUP_POINTS(curve_id) of include/mlhip.h taken apart (mlhip_msm_batch / _device only): true and the plain
+// curve id for the three flagged values, otherwise false and `curve` as it came -- so every other value is unknown as before.
+bool take_subgroup_points_promise(int& curve) {
+  if (curve < MLHIP_CURVE_SUBGROUP_POINTS(0) || curve > MLHIP_CURVE_SUBGROUP_POINTS(2)) return false;
+  curve &= 0xFF;
+  return true;
+}
+
 // A launch on `st`: remembered for the finish of a device-result plan, whose previous finish may still be queued on
 // ANOTHER stream -- the new stream then waits for it on the device (the slot, d_out and the sort buffers are being read).
 int plan_begin_on(mlhip_msm_plan* p, hipStream_t st) {
@@ -838,6 +846,7 @@ int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stri
 
 int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
                            const uint64_t* offsets, size_t k, void* d_out_affine, void* stream) {
+  const bool subgroup = take_subgroup_points_promise(curve);
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   if (!ops->point_size(group)) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
@@ -847,11 +856,13 @@ int mlhip_msm_batch_device(int curve, int group, const void* d_points, const voi
   if (!d_out_affine || (offsets[k] && (!d_points || !d_scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   rc = ensure_device();
   if (rc) return rc;
-  return ops->msm_batch(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, (hipStream_t)stream);
+  return ops->msm_batch(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, (hipStream_t)stream, subgroup);
 }
 
 int mlhip_msm_batch(int curve, int group, const void* points, const void* scalars, int scalars_mont, const uint64_t* offsets,
                     size_t k, void* out_affine) {
+  const int curve_arg = curve;  // (with the promise, as mlhip_msm_batch_device takes it)
+  take_subgroup_points_promise(curve);
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   const size_t ptsz = ops->point_size(group);
@@ -869,7 +880,7 @@ int mlhip_msm_batch(int curve, int group, const void* points, const void* scalar
   void* ds = hc.up(scalars, n * 32);
   void* dout = hc.dev(k * ptsz);
   if (hc.rc) return hc.rc;
-  rc = mlhip_msm_batch_device(curve, group, dp, ds, scalars_mont, offsets, k, dout, hc.l.st);
+  rc = mlhip_msm_batch_device(curve_arg, group, dp, ds, scalars_mont, offsets, k, dout, hc.l.st);
   if (rc) return rc;
   return hc.down(out_affine, dout, k * ptsz);
 }

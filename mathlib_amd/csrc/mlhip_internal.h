@@ -195,7 +195,7 @@ struct mlhip_g2_prepared_tables {
   X(C, int, plan_fold_build, (mlhip_msm_plan * p, const void* d_points, size_t n, hipStream_t st))                        \
   X(C, int, msm_batch,                                                                                                    \
     (int group, const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,    \
-     hipStream_t st))                                                                                                     \
+     hipStream_t st, bool subgroup))                                                                                      \
   X(C, int, bases_batch,                                                                                                  \
     (int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars, int mont,          \
      const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out, hipStream_t st))            \

@@ -368,10 +368,17 @@ int msm_batch_run(const MsmBatchLayout& L, const void* extra, size_t extra_bytes
   return 0;
 }
 
-// the chunk kernel of the compiled chunk length P
+// msm_batch_endo.h: the split chunk kernel of a call whose points are promised to be in G1 / G2; false: there is none for
+// this (curve, group, P), or MLHIP_MSM_BATCH_ENDO=0
+template <class C, class F>
+bool msm_batch_endo_launch_chunks(int P, const void* d_points, const void* d_scalars, int mont, const MsmBatchChunk* d_chunks,
+                                  uint32_t n_chunks, void* d_partials, hipStream_t st);
+
+// the chunk kernel of the compiled chunk length P; subgroup: the caller's promise (MLHIP_CURVE_SUBGROUP_POINTS)
 template <class C, class F>
 void msm_batch_launch_chunks_p(int P, const void* d_points, const void* d_scalars, int mont, const MsmBatchChunk* d_chunks,
-                               uint32_t n_chunks, void* d_partials, hipStream_t st) {
+                               uint32_t n_chunks, void* d_partials, hipStream_t st, bool subgroup = false) {
+  if (subgroup && msm_batch_endo_launch_chunks<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st)) return;
   switch (P) {
     case 1: msm_batch_launch_chunks<C, F, 1>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
     case 2: msm_batch_launch_chunks<C, F, 2>(d_points, d_scalars, mont, d_chunks, n_chunks, d_partials, st); break;
@@ -383,12 +390,12 @@ void msm_batch_launch_chunks_p(int P, const void* d_points, const void* d_scalar
 // Straus chunks for every segment.  offsets: k + 1 checked host entries (api_msm.hip: mlhip_msm_batch_device), k >= 1
 template <class C, class F>
 int msm_batch_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
-                     hipStream_t st) {
+                     hipStream_t st, bool subgroup = false) {
   const int P = msm_batch_chunk_len<C, F>();
   MsmBatchLayout L;
   if (!msm_batch_layout(L, offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: more than 2^32 - 1 chunks");
   return msm_batch_run<C, F>(L, nullptr, 0, d_out, st, [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void*, void* part, void*) {
-    msm_batch_launch_chunks_p<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, part, st);
+    msm_batch_launch_chunks_p<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, part, st, subgroup);
   });
 }
 #endif  // __HIPCC__

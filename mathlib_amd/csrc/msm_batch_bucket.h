@@ -480,18 +480,19 @@ struct MsmBucketCall {
 };
 
 // mlhip_msm_batch_device behind the ABI: segments of at least T pairs through the bucket kernels, everything else (a call
-// without a long segment, a call whose scratch would pass the bound) as msm_batch_device has it.
+// without a long segment, a call whose scratch would pass the bound) as msm_batch_device has it.  subgroup: the points are
+// promised to be in G1 / G2 -- the Straus chunks take the split kernels of msm_batch_endo.h, the bucket route stays as it is.
 template <class C, class F>
 int msm_batch_route_device(const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k, void* d_out,
-                           hipStream_t st) {
+                           hipStream_t st, bool subgroup = false) {
   const int P = msm_batch_chunk_len<C, F>();
   MsmBucketCall<C, F> call;
   if (!call.plan(offsets, k, P)) return mlhip_rt::fail(MLHIP_EINVAL, "msm batch: more than 2^32 - 1 chunks");
-  if (call.slices.empty()) return msm_batch_device<C, F>(d_points, d_scalars, mont, offsets, k, d_out, st);
+  if (call.slices.empty()) return msm_batch_device<C, F>(d_points, d_scalars, mont, offsets, k, d_out, st, subgroup);
   return msm_batch_run<C, F>(
       call.L, call.slices.data(), call.slices.size() * sizeof(uint32_t), d_out, st,
       [&](const MsmBatchChunk* d_chunks, uint32_t n_chunks, const void* d_extra, void* part, void* d_scratch) {
-        if (n_chunks > call.n_slices) msm_batch_launch_chunks_p<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, part, st);
+        if (n_chunks > call.n_slices) msm_batch_launch_chunks_p<C, F>(P, d_points, d_scalars, mont, d_chunks, n_chunks, part, st, subgroup);
         call.launch(d_points, MsmBucketDirect(), d_scalars, mont, d_chunks, (const uint32_t*)d_extra, part, d_scratch, st);
       },
       call.scratch);

@@ -35,6 +35,9 @@
 //     LaneForm    k_chunks / k_masked_sums   one lane per point (MLHIP_REDUCE_ONE_LANE, test build)
 //   k_msm_batch_chunk / k_msm_batch_sum (+ _lp for G2)   many small MSMs per call: Straus chunks of <= P pairs per lane,
 //                 then segmented sums of <= 32 partials per lane (msm_batch.h)
+//   k_msm_batch_chunk_endo (+ _lp)   the chunks of a call whose points are promised to be in G1 / G2: the scalar splits of
+//                 msm_scalar_mul_endo.h per pair, half (G1, BN254 G2) or a quarter (BLS12 G2) of the shared doublings
+//                 (msm_batch_endo.h)
 //   k_msm_bucket_digits / k_msm_bucket_accumulate / k_msm_bucket_combine   the segments of such a call that are long enough
 //                 for buckets: 7-bit digit bytes per slice, one wave per (slice, window) with one bucket per lane and an
 //                 in-wave reduction, Horner per slice into the slice's row of the partials (msm_batch_bucket.h); _lp for G2
@@ -93,6 +96,7 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 #include "msm_scalar_mul_endo.h"
 #include "msm_scalar_mul.h"
 #include "msm_batch.h"
+#include "msm_batch_endo.h"
 #include "msm_batch_bucket.h"
 #include "point_sum.h"
 #include "msm_bases_batch.h"

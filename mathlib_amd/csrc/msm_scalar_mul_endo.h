@@ -112,10 +112,10 @@ MLHIP_HD void g2_psi_affine(Affine<F>& r, const Affine<F>& a, bool neg) {
   F::select(r.y, neg, nu, u);
 }
 
-// acc = [s]Q for Q in G2, dig = gt_exp_split(s), s < r.  tab[1 .. 14] are scratch; Q itself is read once.  Every branch
-// depends on the scalar alone: uniform over the two lanes of a product.
+// The 15-entry Straus table of Q in G2 that gt_exp_step_index addresses (index - 1), shared by g2_endo_chain and the chunks
+// of msm_batch_endo.h.  Q itself is read once; no branch or address depends on it.
 template <class C, class F, class O>
-MLHIP_HD void g2_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[15], const Affine<F>& Q, const uint32_t (&dig)[8]) {
+MLHIP_HD void g2_endo_table(XYZZ<F> (&tab)[15], const Affine<F>& Q) {
   xyzz_from_affine<F>(tab[0], Q);
   if constexpr (C::IS_BN) {
     // tab[a + 4 b - 1] = [a]Q + [b]psi(Q), a, b in 0 .. 3
@@ -155,6 +155,13 @@ MLHIP_HD void g2_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[15], const Affine<F>& Q
       }
     }
   }
+}
+
+// acc = [s]Q for Q in G2, dig = gt_exp_split(s), s < r.  tab is scratch.  Every branch depends on the scalar alone: uniform
+// over the two lanes of a product.
+template <class C, class F, class O>
+MLHIP_HD void g2_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[15], const Affine<F>& Q, const uint32_t (&dig)[8]) {
+  g2_endo_table<C, F, O>(tab, Q);
   constexpr int DBL = C::IS_BN ? 2 : 1;
   xyzz_set_inf<F>(acc);
   bool started = false;

@@ -38,9 +38,9 @@ int MLHIP_TU_FN(plan_fold_build)(mlhip_msm_plan* p, const void* d_points, size_t
   return plan_fold_build<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(p, d_points, n, st);
 }
 int MLHIP_TU_FN(msm_batch)(int group, const void* d_points, const void* d_scalars, int mont, const uint64_t* offsets, size_t k,
-                          void* d_out, hipStream_t st) {
-  if (group == MLHIP_GROUP_G1) return msm_batch_route_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, d_scalars, mont, offsets, k, d_out, st);
-  return msm_batch_route_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, d_scalars, mont, offsets, k, d_out, st);
+                          void* d_out, hipStream_t st, bool subgroup) {
+  if (group == MLHIP_GROUP_G1) return msm_batch_route_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, d_scalars, mont, offsets, k, d_out, st, subgroup);
+  return msm_batch_route_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, d_scalars, mont, offsets, k, d_out, st, subgroup);
 }
 int MLHIP_TU_FN(bases_batch)(int group, mlhip_bases_batch_tables* t, const void* d_pts, size_t n_bases, const void* d_scalars,
                              int mont, const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out,

@@ -496,9 +496,9 @@ class Curve:
                                     1 if self.scalars_mont else 0, len(a1), self.window_c, o1, o2))
         return G1(o1.raw, self), G2(o2.raw, self)
 
-    def _msm_batch(self, group: int, a_lists, b_lists, name: str, identity) -> list:
+    def _msm_batch(self, group: int, a_lists, b_lists, name: str, identity, subgroup: bool = False) -> list:
         """one mlhip_msm_batch call for every segment; each keeps MultiScalarMul's length rules (fewer scalars than points
-        raises, more gives the identity: an empty segment)"""
+        raises, more gives the identity: an empty segment).  subgroup: every point is promised to be in G1 / G2"""
         if len(a_lists) != len(b_lists):
             raise ValueError("%s: %d point lists, %d scalar lists" % (name, len(a_lists), len(b_lists)))
         lengths, pts, scs = [], [], []
@@ -513,16 +513,27 @@ class Curve:
             scs.append(self._scalars(b))
         if not lengths:
             return []
-        raw = msm_batch(self.id, group, b"".join(pts), b"".join(scs), self.scalars_mont, lengths)
+        raw = msm_batch(self.id, group, b"".join(pts), b"".join(scs), self.scalars_mont, lengths, subgroup)
         return [identity(r) for r in raw]
 
-    def MultiScalarMulBatch(self, a_lists: Sequence[Sequence[G1]], b_lists: Sequence[Sequence[Zr]]) -> List[G1]:
+    def MultiScalarMulBatch(self, a_lists: Sequence[Sequence[G1]], b_lists: Sequence[Sequence[Zr]], subgroup: bool = False) -> List[G1]:
         """out[i] = MultiScalarMul(a_lists[i], b_lists[i]) for many small MSMs in one device call (include/mlhip.h:
-        mlhip_msm_batch)"""
-        return self._msm_batch(GROUP_G1, a_lists, b_lists, "MultiScalarMulBatch", lambda r: G1(r, self))
+        mlhip_msm_batch).  subgroup=True: MultiScalarMulBatchSubgroup"""
+        return self._msm_batch(GROUP_G1, a_lists, b_lists, "MultiScalarMulBatch", lambda r: G1(r, self), subgroup)
 
-    def MultiScalarMulG2Batch(self, a_lists: Sequence[Sequence[G2]], b_lists: Sequence[Sequence[Zr]]) -> List[G2]:
-        return self._msm_batch(GROUP_G2, a_lists, b_lists, "MultiScalarMulG2Batch", lambda r: G2(r, self))
+    def MultiScalarMulG2Batch(self, a_lists: Sequence[Sequence[G2]], b_lists: Sequence[Sequence[Zr]], subgroup: bool = False) -> List[G2]:
+        return self._msm_batch(GROUP_G2, a_lists, b_lists, "MultiScalarMulG2Batch", lambda r: G2(r, self), subgroup)
+
+    def MultiScalarMulBatchSubgroup(self, a_lists: Sequence[Sequence[G1]], b_lists: Sequence[Sequence[Zr]]) -> List[G1]:
+        """MultiScalarMulBatch for points the caller knows to be in G1 (decoded with the subgroup check, issuer keys,
+        generators, outputs of earlier MSMs): the same results with half of the chunks' doublings, from the curve's
+        endomorphism and a split of every scalar (mlhip_msm_batch_subgroup).  A point outside the subgroup gives an undefined
+        result for its own segment; MultiScalarMulBatch accepts any point of the curve."""
+        return self.MultiScalarMulBatch(a_lists, b_lists, subgroup=True)
+
+    def MultiScalarMulG2BatchSubgroup(self, a_lists: Sequence[Sequence[G2]], b_lists: Sequence[Sequence[Zr]]) -> List[G2]:
+        """the same for points known to be in G2"""
+        return self.MultiScalarMulG2Batch(a_lists, b_lists, subgroup=True)
 
     def Mul2Batch(self, g: Sequence[G1], e: Sequence[Zr], q: Sequence[G1], f: Sequence[Zr]) -> List[G1]:
         """out[i] = g[i].Mul2(e[i], q[i], f[i]): segments of two pairs in one mlhip_msm_batch call"""
