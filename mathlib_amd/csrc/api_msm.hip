@@ -194,42 +194,52 @@ int plan_read_device_times(mlhip_msm_plan* p) {
   HIPCHK(hipSetDevice(p->device));
   HIPCHK(hipEventSynchronize(p->done));
   p->times_stale = false;
-  if (p->timed_n != 0 && p->tiles_timed > 0) {
-    p->ms[0] = p->ms[1] = p->ms[2] = 0;
-    for (int s = 0; s < p->tiles_timed; s++) {
-      float a = 0, b = 0;
-      HIPCHK(hipEventElapsedTime(&a, p->ev_tile[s][0], p->ev_tile[s][1]));
-      HIPCHK(hipEventElapsedTime(&b, p->ev_tile[s][1], p->ev_tile[s][2]));
-      p->ms[1] += a;
-      p->ms[2] += b;
-    }
-    HIPCHK(hipEventElapsedTime(&p->ms[3], p->ev[3], p->ev[4]));
-    HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
-  } else if (p->timed_n != 0 && p->tiles_timed == 0) {
-    for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
-    HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
-  }
+  if (p->timed_n != 0 && p->tiles_timed >= 0)
+    if (int rc_times = plan_read_phase_times(p)) return rc_times;
   HIPCHK(hipEventElapsedTime(&p->ms[5], p->ev_tail[0], p->ev_tail[1]));
   return 0;
 }
 
-// can this plan run the segment train (plan_stream / plan_stream_shared)?  The condition stream_begin checks.
+// can this plan run the segment train (msm_plan.h: plan_stream_train)?  The condition stream_begin checks.
 bool plan_can_stream(const mlhip_msm_plan* p) {
   return p->aux && p->d_points28;
 }
 
-// the shared-scalar train on two plans; h_* = nullptr: everything is already at the d_* pointers
+// After a failed launch on `st`: `done` may never have been recorded, and what was queued may still read the caller's
+// buffers.  Wait for every stream a launch queues work on -- `st` (sorts, accumulation, reduction, the copy of the partial
+// sums), each plan's auxiliary stream (uploads, point conversion) and its sort-ahead stream -- and leave the k plans
+// reusable.  The error text survives: none of these calls goes through fail().
+void drain_failed_launch(mlhip_msm_plan* const* plans, int k, hipStream_t st) {
+  (void)hipStreamSynchronize(st);
+  for (int j = 0; j < k; j++)
+    if (plans[j]->aux) (void)hipStreamSynchronize(plans[j]->aux);
+  for (int j = 0; j < k; j++)
+    if (plans[j]->sort_stream) (void)hipStreamSynchronize(plans[j]->sort_stream);
+  (void)hipGetLastError();
+  for (int j = 0; j < k; j++) {
+    plans[j]->pending = false;
+    plans[j]->upload_src = nullptr;
+  }
+}
+
+// The G1 MSM and the G2 MSM of ONE scalar vector (BASELINE configs[3], a Groth16 prover's B-query): the train of the two
+// plans -- every tile is sorted once, in the G1 plan, and accumulated twice.  h_* = nullptr: everything is already at the d_*
+// pointers; else the caller's pageable memory, staged through d_*: the scalars and the G1 points of a tile travel on the G1
+// plan's auxiliary stream, the G2 points on the G2 plan's, under the kernels of the tile before.
 int plan_shared(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d1, void* d2, void* dsc, const void* h1, const void* h2,
                 const void* hsc, int mont, size_t n, hipStream_t st) {
-  int rc = curve_ops(g1->curve)->plan_shared(g1, g2, d1, d2, dsc, h1, h2, hsc, mont, n, st);
-  if (rc) {  // as mlhip_msm_launch: drain what was queued (copies from the caller's buffers too) and leave both plans reusable
-    (void)hipStreamSynchronize(st);
-    if (g1->aux) (void)hipStreamSynchronize(g1->aux);
-    if (g1->sort_stream) (void)hipStreamSynchronize(g1->sort_stream);
-    if (g2->aux) (void)hipStreamSynchronize(g2->aux);
-    (void)hipGetLastError();
-    g1->pending = g2->pending = false;
-  }
+  mlhip_msm_plan* ps[2] = {g1, g2};
+  void* dp[2] = {d1, d2};
+  const void* hp[2] = {h1, h2};
+  int rc = 0;
+  if (g1->c != g2->c || g1->W != g2->W || g1->M != g2->M || g1->bits != g2->bits)
+    rc = mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width and scalar width");
+  // (plans over shifted-base tables belong to resident-bases handles: their shared-scalar MSM is a set's, mlhip_bases_set_create)
+  else if (g1->fold || g2->fold)
+    rc = mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
+  else
+    rc = curve_ops(g1->curve)->plan_train(ps, dp, hp, 2, dsc, hsc, mont, n, shared_segments(hsc != nullptr, n), false, st);
+  if (rc) drain_failed_launch(ps, 2, st);
   return rc;
 }
 
@@ -403,7 +413,7 @@ int plan_create_ex(int curve, int group, size_t max_n, int window_c, size_t fold
   p->nb = ilog2(p->T);
   p->nsel = 4 + p->nb;  // two half-sums of W0, two of A, nb bit-masked sums
   rc = ops->plan_alloc(p);
-  if (!rc && p->fold && (p->sort_low <= 0 || !p->reduce28))
+  if (!rc && p->fold && (p->lists.sort_low <= 0 || !p->reduce28))
     rc = mlhip_rt::fail(MLHIP_EINVAL, "shifted-base tables need the two-level sort and the carry-free kernels");
   if (rc) {
     mlhip_msm_plan_destroy(p);
@@ -438,32 +448,24 @@ int stream_segments(int group, size_t n, const mlhip_msm_plan* plan) {
   return mlhip::stream_segments(plan->aux && plan->d_points28, group == MLHIP_GROUP_G1, n);
 }
 
+// the train of one plan (msm_plan.h: plan_stream_train, k = 1): a host-buffer MSM streamed in `segments` >= 2 segments
 int plan_stream(mlhip_msm_plan* p, void* d_pts, void* d_sc, const void* points, const void* scalars, int mont, size_t n,
                 int segments, hipStream_t st) {
-  int rc = curve_ops(p->curve)->plan_stream(p, d_pts, d_sc, points, scalars, mont, n, segments, st);
-  if (rc) {
-    // a failure part-way: copies from the caller's buffers may still be queued -- let them drain before the caller gets
-    // its memory back, and leave the plan reusable
-    (void)hipDeviceSynchronize();
-    p->pending = false;
-  }
+  int rc = curve_ops(p->curve)->plan_train(&p, &d_pts, &points, 1, d_sc, scalars, mont, n, segments, true, st);
+  if (rc) drain_failed_launch(&p, 1, st);  // (copies from the caller's buffers may still be queued)
   return rc;
 }
 
 // a class of a set of resident-bases handles (api_bases.hip): the plan runs the segment train, on the two-level sort
-bool plan_can_train(const mlhip_msm_plan* p) { return plan_can_stream(p) && p->sort_low > 0; }
+bool plan_can_train(const mlhip_msm_plan* p) { return plan_can_stream(p) && p->lists.sort_low > 0; }
 
 // k plans of one geometry over one scalar vector (msm_plan.h: plan_stream_train); h_scalars = nullptr: they are at d_scalars
 int plan_train(mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars, int mont,
                size_t n, int segments, hipStream_t st) {
   for (int j = 0; j < k; j++)
     if (int rc_order = plan_begin_on(plans[j], st)) return rc_order;
-  int rc = curve_ops(plans[0]->curve)->plan_train(plans, d_points, k, d_scalars, h_scalars, mont, n, segments, st);
-  if (rc) {  // as plan_stream: let whatever still reads the caller's buffers drain, and leave the plans reusable
-    (void)hipDeviceSynchronize();
-    (void)hipGetLastError();
-    for (int j = 0; j < k; j++) plans[j]->pending = false;
-  }
+  int rc = curve_ops(plans[0]->curve)->plan_train(plans, d_points, nullptr, k, d_scalars, h_scalars, mont, n, segments, true, st);
+  if (rc) drain_failed_launch(plans, k, st);
   return rc;
 }
 
@@ -605,8 +607,8 @@ int mlhip_msm_plan_destroy(mlhip_msm_plan* p) {
   if (!p) return 0;
   (void)hipSetDevice(p->device);
   plan_wait_done(p);  // (a device-result plan: its last finish may still be running)
-  void* ptrs[] = {p->d_result, p->d_digits, p->d_sorted, p->d_zero, p->d_offsets, p->d_biglist, p->d_buckets, p->d_A, p->d_W0, p->d_out,
-                  p->d_order, p->d_hist, p->d_tilesums, p->d_coarse_off, p->d_points28, p->d_blockhist, p->d_state28, p->d_bigprefix, p->d_bigpart, p->d_binprefix};
+  entry_lists_free(&p->lists);
+  void* ptrs[] = {p->d_result, p->d_biglist, p->d_buckets, p->d_A, p->d_W0, p->d_out, p->d_points28, p->d_state28, p->d_bigprefix, p->d_bigpart};
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   if (p->h_out) (void)hipHostFree(p->h_out);
@@ -626,7 +628,10 @@ int mlhip_msm_plan_destroy(mlhip_msm_plan* p) {
       if (e) (void)hipEventDestroy(e);
   if (p->aux) (void)hipStreamDestroy(p->aux);
   for (int i = 0; i < 2; i++) {
-    if (p->sort_helper[i]) (void)mlhip_msm_plan_destroy(p->sort_helper[i]);
+    if (p->sort_helper[i]) {
+      entry_lists_free(p->sort_helper[i]);
+      delete p->sort_helper[i];
+    }
     if (p->ev_sorted[i]) (void)hipEventDestroy(p->ev_sorted[i]);
     if (p->ev_lists_free[i]) (void)hipEventDestroy(p->ev_lists_free[i]);
   }
@@ -645,17 +650,7 @@ int mlhip_msm_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scal
   hipStream_t st = (hipStream_t)stream;
   if (int rc_order = plan_begin_on(p, st)) return rc_order;
   int rc = curve_ops(p->curve)->plan_launch(p, d_points, d_scalars, scalars_mont, n, st);
-  if (rc) {
-    // a failure part-way through the launch train: `done` may never have been recorded, so a later finish must not
-    // read h_out.  Drain what was queued (the error text survives: the drain calls do not go through fail()) and leave
-    // the plan reusable, as plan_stream does.
-    (void)hipStreamSynchronize(st);
-    if (p->aux) (void)hipStreamSynchronize(p->aux);
-    if (p->sort_stream) (void)hipStreamSynchronize(p->sort_stream);
-    (void)hipGetLastError();
-    p->pending = false;
-    p->upload_src = nullptr;
-  }
+  if (rc) drain_failed_launch(&p, 1, st);  // (a later finish must not read h_out)
   return rc;
 }
 
@@ -721,9 +716,9 @@ int mlhip_msm_g1g2(int curve, const void* points_g1, const void* points_g2, cons
                         e1->stream);
     if (!rc) rc = mlhip_msm_finish(e1->plan, out_g1, nullptr);
     if (!rc) rc = mlhip_msm_finish(e2->plan, out_g2, nullptr);
-    if (rc) {  // whatever is still queued reads the caller's buffers: let it drain, leave the plans reusable
-      (void)hipDeviceSynchronize();
-      e1->plan->pending = e2->plan->pending = false;
+    if (rc) {  // (a finish failed, or the launch, drained already: whatever is still queued reads the caller's buffers)
+      mlhip_msm_plan* ps[2] = {e1->plan, e2->plan};
+      drain_failed_launch(ps, 2, e1->stream);
     }
     pool_release(e2, rc != 0);
     pool_release(e1, rc != 0);

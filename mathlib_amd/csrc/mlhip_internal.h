@@ -44,6 +44,39 @@ static inline bool mlhip_alt_switch(const char* name) {
   return e && e[0] == '1';
 }
 
+// The entry lists of one sort: what launch_sort needs and what it leaves for the accumulation (msm_plan.h).  A plan owns one
+// (`lists`); a sort-ahead record is another of the plan's geometry (sort_ahead_prepare), and the later plans of a
+// shared-scalar train read the first plan's.  entry_lists_alloc (msm_plan.h) fills it, entry_lists_free empties it.
+struct MsmEntryLists {
+  // the sort geometry, as the owning plan's fields of the same names (msm_plan.h: plan_entry_lists)
+  int c = 0, bits = 0, W = 0, Wd = 0, fold = 0;
+  uint32_t M = 0;
+  size_t fold_tile = 0;
+  size_t cap = 0;  // scalars one sort may cover
+  int device = 0;
+  uint32_t *d_digits = nullptr, *d_sorted = nullptr, *d_zero = nullptr, *d_offsets = nullptr;
+  int sort_low = 0, sort_idx_bits = 0;  // two-level sort: fine bits per coarse bin (0 = legacy path)
+  uint32_t sort_nb = 0;
+  uint32_t *d_coarse_count = nullptr, *d_coarse_cursor = nullptr, *d_coarse_off = nullptr;
+  uint16_t* d_blockhist = nullptr;  // per-block coarse histograms (k_coarse_hist -> k_coarse_scatter)
+  uint32_t *d_order = nullptr, *d_hist = nullptr, *d_tilesums = nullptr;
+  // views into d_zero, which is zeroed ahead of every sort.  d_bigcount is written by the ACCUMULATION of a tile, always
+  // through the accumulating plan's own lists, whoever sorted the tile
+  uint32_t *d_counts = nullptr, *d_cursor = nullptr, *d_bigcount = nullptr;
+  size_t zero_bytes = 0;
+  uint32_t* d_binprefix = nullptr;  // coarse bins sorted by several workgroups: slice prefix
+};
+
+// gives back whatever entry_lists_alloc got, a half-filled record included
+inline void entry_lists_free(MsmEntryLists* l) {
+  (void)hipSetDevice(l->device);
+  void* ptrs[] = {l->d_digits, l->d_sorted,   l->d_zero,       l->d_offsets,   l->d_order,
+                  l->d_hist,   l->d_tilesums, l->d_coarse_off, l->d_blockhist, l->d_binprefix};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  *l = MsmEntryLists();
+}
+
 struct mlhip_msm_plan {
   int curve, group, device, c, W, L, lgL, nb, nsel;
   size_t max_n;
@@ -66,17 +99,10 @@ struct mlhip_msm_plan {
   // d_out / h_out then hold fold_nsel2 = 4 + nb + lg W more entries behind the W x nsel ones, and the host tail reads those
   int fold_nsel2 = 0;
   size_t pt_size, xyzz_size;
-  uint32_t *d_digits = nullptr, *d_sorted = nullptr, *d_zero = nullptr, *d_offsets = nullptr, *d_biglist = nullptr;
-  int sort_low = 0, sort_idx_bits = 0;  // two-level sort: fine bits per coarse bin (0 = legacy path)
-  uint32_t sort_nb = 0;
-  uint32_t *d_coarse_count = nullptr, *d_coarse_cursor = nullptr, *d_coarse_off = nullptr;
-  uint16_t* d_blockhist = nullptr;  // per-block coarse histograms (k_coarse_hist -> k_coarse_scatter)
-  uint32_t *d_order = nullptr, *d_hist = nullptr, *d_tilesums = nullptr;
-  uint32_t *d_counts = nullptr, *d_cursor = nullptr, *d_bigcount = nullptr;  // views into d_zero
-  size_t zero_bytes = 0;
+  MsmEntryLists lists;  // the plan's own sort buffers, for max_n scalars (a folded plan: one tile of its table)
+  uint32_t* d_biglist = nullptr;
   void *d_buckets = nullptr, *d_A = nullptr, *d_W0 = nullptr, *d_out = nullptr;
   void* h_out = nullptr;
-  uint32_t* d_binprefix = nullptr;  // coarse bins sorted by several workgroups: slice prefix
   uint32_t* d_bigprefix = nullptr;  // long buckets: slice counts (prefix) and slice sums
   void* d_bigpart = nullptr;
   void* d_points28 = nullptr;  // G1: the points in the carry-free 28-bit-limb form (ec28.h), rewritten every MSM
@@ -107,7 +133,7 @@ struct mlhip_msm_plan {
   // curves with C::HAS_EDWARDS may then sum their G1 buckets in twisted Edwards coordinates (mlhip_msm_plan_assume_srs)
   bool trust_subgroup = false;
   bool last_ed = false;  // the last launch summed its buckets in twisted Edwards coordinates (mlhip_msm_plan_timings [9])
-  // streamed host-buffer MSMs (plan_stream): raw carry-free bucket accumulators between segments, one event per segment
+  // streamed host-buffer MSMs (plan_stream_train): raw carry-free bucket accumulators between segments, one event per segment
   void* d_state28 = nullptr;
   hipEvent_t ev_seg[MLHIP_MAX_SEGMENTS] = {};
   hipEvent_t ev_seg_sc[MLHIP_MAX_SEGMENTS] = {};  // ... and one after the segment's SCALARS alone (the sort needs only them)
@@ -129,13 +155,33 @@ struct mlhip_msm_plan {
   hipEvent_t ev_tail[2] = {nullptr, nullptr};  // around the tail kernel, under profiling: [5] of mlhip_msm_plan_timings
   bool times_stale = false;  // a profiled finish whose events mlhip_msm_plan_timings has not read yet
   size_t timed_n = 0;        // ... and its n (0: no phase events but the tail's)
-  // tiles of device-resident inputs: the entry lists of tile s + 1 are sorted on `sort_stream`, in one of two helper
-  // records that hold sort buffers only, while tile s accumulates (msm_plan.h: sort_ahead_*)
-  mlhip_msm_plan* sort_helper[2] = {nullptr, nullptr};
+  // tiles of device-resident inputs: the entry lists of tile s + 1 are sorted on `sort_stream`, into one of two further
+  // records, while tile s accumulates (msm_plan.h: sort_ahead_*).  A record is registered here only once it is complete.
+  MsmEntryLists* sort_helper[2] = {nullptr, nullptr};
   hipStream_t sort_stream = nullptr;
   hipEvent_t ev_sorted[2] = {nullptr, nullptr}, ev_lists_free[2] = {nullptr, nullptr};
 };
 
+// ms[0..4] of the last profiled launch from its phase events: digits / sort / accumulate / reduce / total.  Tiles
+// (tiles_timed > 0): the digits are part of each tile's sort, and accumulate is the sum over the tiles' kernels.  The caller
+// has waited for `done` and knows tiles_timed >= 0 (a streamed host-buffer MSM records no phase events); ms[5] is its own.
+inline int plan_read_phase_times(mlhip_msm_plan* p) {
+  if (p->tiles_timed > 0) {
+    p->ms[0] = p->ms[1] = p->ms[2] = 0;
+    for (int s = 0; s < p->tiles_timed; s++) {
+      float a = 0, b = 0;
+      HIPCHK(hipEventElapsedTime(&a, p->ev_tile[s][0], p->ev_tile[s][1]));
+      HIPCHK(hipEventElapsedTime(&b, p->ev_tile[s][1], p->ev_tile[s][2]));
+      p->ms[1] += a;
+      p->ms[2] += b;
+    }
+    HIPCHK(hipEventElapsedTime(&p->ms[3], p->ev[3], p->ev[4]));
+  } else {
+    for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
+  }
+  HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
+  return 0;
+}
 
 // the per-base fixed-window tables of a mlhip_bases handle for mlhip_bases_msm_batch (msm_bases_batch.h): rows of bases
 // [0, n_tabled) at width w, on the handle's device; freed by mlhip_bases_destroy
@@ -164,16 +210,11 @@ struct mlhip_g2_prepared_tables {
   X(C, int, plan_launch,                                                                                                  \
     (mlhip_msm_plan * p, const void* d_points, const void* d_scalars, int mont, size_t n, hipStream_t st))                \
   X(C, int, plan_finish, (mlhip_msm_plan * p, void* out_affine, void* out_xyzz))                                          \
-  X(C, int, plan_stream,                                                                                                  \
-    (mlhip_msm_plan * p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,          \
-     size_t n, int segments, hipStream_t st))                                                                             \
-  X(C, int, plan_shared,                                                                                                  \
-    (mlhip_msm_plan * g1, mlhip_msm_plan * g2, void* d_points_g1, void* d_points_g2, void* d_scalars,                     \
-     const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n, hipStream_t st))        \
-  /* k plans of one geometry, of either group, over one scalar vector (msm_plan.h: plan_stream_train; resident points) */  \
+  /* the segment train (msm_plan.h: plan_stream_train): k plans of one geometry, of either group, over one scalar vector; \
+     h_points null, or per plan the host points its tiles upload (null: resident); `schedule`: stream_schedule may cut */   \
   X(C, int, plan_train,                                                                                                   \
-    (mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars, int mont,        \
-     size_t n, int segments, hipStream_t st))                                                                             \
+    (mlhip_msm_plan* const* plans, void* const* d_points, const void* const* h_points, int k, void* d_scalars,            \
+     const void* h_scalars, int mont, size_t n, int segments, bool schedule, hipStream_t st))                             \
   X(C, int, pairing,                                                                                                      \
     (int what, const void* d_g1, const void* d_g2, size_t ppp, size_t n, const void* d_in, void* d_out, hipStream_t st))  \
   X(C, int, fp_mul, (const void* d_a, const void* d_b, size_t n, int repeat, void* d_out, hipStream_t st))                \

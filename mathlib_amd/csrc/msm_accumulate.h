@@ -140,7 +140,7 @@ __device__ void big_bucket_total(XYZZ<F>& sum, XYZZ<F>* sh, const XYZZ<F>* __res
   __syncthreads();
 }
 
-// ---- segmented accumulation (host-buffer MSMs streamed over PCIe, plan_stream below) --------------------------
+// ---- segmented accumulation (host-buffer MSMs streamed over PCIe, plan_stream_train below) --------------------------
 // The n pairs arrive in K segments; every segment is sorted by itself and added INTO the bucket sums of the segments
 // before it, so the upload of segment s+1 runs under the kernels of segment s and the reduction runs once.  Between
 // segments a bucket is kept as its raw carry-free accumulator (4 normalized coordinates; ZZ = 0 limbs <=> infinity),

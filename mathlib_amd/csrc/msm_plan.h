@@ -1,6 +1,8 @@
-// msm_plan.h -- host side of the MSM: plan allocation, the launch steps both sequences share (launch_sort, launch_convert,
-// launch_accumulate, launch_reduce, finish_train), the sequences themselves (plan_launch: one pass; stream_begin /
-// stream_tile / stream_end: a train of segments or tiles, cut by msm_segments.h) and the host tail.  Part of msm_kernels.h.
+// msm_plan.h -- host side of the MSM: plan allocation (entry_lists_alloc: the sort buffers, an MsmEntryLists; plan_alloc: the
+// rest), the launch steps both sequences share (launch_sort, launch_convert, launch_accumulate, launch_reduce, finish_train),
+// the two sequences themselves (plan_launch: one pass; plan_stream_train: the one train of segments or tiles over
+// stream_begin / stream_tile / stream_end, cut by msm_segments.h, for one plan or a class of plans) and the host tail.
+// Part of msm_kernels.h.
 #pragma once
 // (included by msm_kernels.h after its common headers and constants; msm_segments.h comes with mlhip_internal.h)
 
@@ -32,18 +34,39 @@ inline bool plan_use_edwards(const mlhip_msm_plan* p) {
   return false;
 }
 
-// the buffers launch_sort works in (a plan's own, or those of a sort-ahead helper record: sort_ahead_prepare)
-inline int plan_alloc_sort(mlhip_msm_plan* p) {
+// Scalars one sort of a plan covers: all max_n, or -- a folded plan (msm_fold.h) sorts one tile of its table at a time -- at
+// most fold_tile of them, Wd entries each, whose indices run over the Wd fold_tile rows of the tile.
+inline size_t plan_sort_capacity(const mlhip_msm_plan* p) { return p->fold ? std::min(p->max_n, p->fold_tile) : p->max_n; }
+// Entries one scalar puts into ONE set of 2^(c-1) buckets: a folded plan's digits all share the set.
+inline size_t entries_per_bucket_set(const mlhip_msm_plan* p) { return p->fold ? (size_t)p->Wd : 1; }
+
+// An empty record of p's sort geometry for sorts of up to `cap` scalars: the plan's own, or a sort-ahead record.  The one
+// place that copies the geometry.
+inline MsmEntryLists plan_entry_lists(const mlhip_msm_plan* p, size_t cap) {
+  MsmEntryLists l;
+  l.c = p->c;
+  l.bits = p->bits;
+  l.W = p->W;
+  l.Wd = p->Wd;
+  l.M = p->M;
+  l.fold = p->fold;
+  l.fold_tile = p->fold_tile;
+  l.cap = cap;
+  l.device = p->device;
+  return l;
+}
+
+// the buffers launch_sort works in, for the geometry and capacity the record holds; on failure entry_lists_free takes
+// back what was allocated
+inline int entry_lists_alloc(MsmEntryLists* p) {
   const size_t nbuckets = (size_t)p->W * p->M;
-  // a folded plan (msm_fold.h) sorts one tile of its table at a time: at most fold_tile scalars, Wd entries each, whose
-  // indices run over the Wd fold_tile rows of the tile
-  const size_t sort_n = p->fold ? std::min(p->max_n, p->fold_tile) : p->max_n;
+  const size_t sort_n = p->cap;
   HIPCHK(hipMalloc(&p->d_digits, (size_t)p->Wd * sort_n * 4));
   HIPCHK(hipMalloc(&p->d_sorted, (size_t)p->Wd * sort_n * 4));
   {
     // sort parameters: packed entry = fine bits | sign | index must fit 32 bits, coarse bins must fit LDS
     int idx_bits = 1;
-    while (((size_t)1 << idx_bits) < (p->fold ? (size_t)p->Wd * p->fold_tile : p->max_n)) idx_bits++;
+    while (((size_t)1 << idx_bits) < (p->fold ? (size_t)p->Wd * p->fold_tile : p->cap)) idx_bits++;
     int low = p->c - 1 < 8 ? p->c - 1 : 8;
     if (low > 31 - idx_bits) low = 31 - idx_bits;
     const char* legacy = getenv("MLHIP_LEGACY_SORT");
@@ -90,13 +113,14 @@ int plan_alloc(mlhip_msm_plan* p) {
   p->pt_size = sizeof(Affine<F>);
   p->xyzz_size = sizeof(XYZZ<F>);
   {
-    int rc_sort = plan_alloc_sort(p);
+    p->lists = plan_entry_lists(p, plan_sort_capacity(p));
+    int rc_sort = entry_lists_alloc(&p->lists);
     if (rc_sort) return rc_sort;
   }
   HIPCHK(hipMalloc(&p->d_biglist, nbuckets * 4));
   {
     // long buckets: at most W n / BIG_BUCKET_MIN of them, and W n / BIG_SLICE + one more slice per bucket
-    const size_t entries = (size_t)p->Wd * (p->fold ? std::min(p->max_n, p->fold_tile) : p->max_n);
+    const size_t entries = (size_t)p->Wd * plan_sort_capacity(p);
     const size_t nbig_max = std::min(nbuckets, entries / BIG_BUCKET_MIN + 1);
     HIPCHK(hipMalloc(&p->d_bigprefix, (nbig_max + 2) * 4));
     HIPCHK(hipMalloc(&p->d_bigpart, (entries / BIG_SLICE + nbig_max + 2) * p->xyzz_size));
@@ -254,16 +278,16 @@ void host_tail(const mlhip_msm_plan* p, XYZZ<F>& total) {
 // slice sums of the long buckets listed by the accumulation kernel (nothing to do, two near-empty launches, when
 // there are none)
 // (`row0`: a folded plan keeps carry-free rows only -- the slices gather from d_points28 + row0, in the form the table holds;
-// `sv`: the plan whose entry lists (sorted / offsets / counts) describe this tile)
+// `sv`: the entry lists (sorted / offsets / counts) that describe this tile; the long-bucket count is p's own)
 template <class F>
-void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t st, const mlhip_msm_plan* sv, size_t row0) {
+void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t st, const MsmEntryLists* sv, size_t row0) {
   typedef typename F::Curve C;
   constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;
   constexpr int BLOCK = 256;  // one XYZZ<F> of LDS per lane (G2: per lane pair): 48 KB for both groups
-  k_big_prefix<<<dim3(1), dim3(1024), 0, st>>>(sv->d_counts, p->d_biglist, p->d_bigcount, p->d_bigprefix);
+  k_big_prefix<<<dim3(1), dim3(1024), 0, st>>>(sv->d_counts, p->d_biglist, p->lists.d_bigcount, p->d_bigprefix);
   auto slices = [&](auto kernel, auto rows) {
     kernel<<<dim3(1024), dim3(BLOCK), (BLOCK / (kG2 ? 2 : 1)) * sizeof(XYZZ<F>), st>>>(
-        rows, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->d_bigcount, p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
+        rows, sv->d_sorted, sv->d_offsets, sv->d_counts, p->d_biglist, p->lists.d_bigcount, p->d_bigprefix, (XYZZ<F>*)p->d_bigpart);
   };
   if (!p->fold) {  // a plain plan: the boundary-form rows the caller gave
     if constexpr (kG2)
@@ -284,8 +308,9 @@ void launch_big_slices(mlhip_msm_plan* p, const Affine<F>* d_points, hipStream_t
 }
 
 // digits -> entries sorted by (window, bucket) in d_sorted / d_offsets / d_counts, and the bucket order by population
+// (`p`: the record sorted into, zeroed by the caller; `ev_digits`: recorded once the digits are taken -- null: no event)
 template <class C>
-int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hipStream_t st, bool prof) {
+int launch_sort(const MsmEntryLists* p, const void* d_scalars, int mont, size_t n, hipStream_t st, hipEvent_t ev_digits) {
   const size_t nbuckets = (size_t)p->W * p->M;
   const int Wd = p->Wd;  // entries per scalar (== W on a plain plan)
   const uint32_t fold_stride = p->fold ? (uint32_t)p->fold_tile : 0u;
@@ -316,7 +341,7 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
     const unsigned blocks = (unsigned)((n + tile - 1) / tile);
     k_coarse_hist<C><<<dim3(blocks), dim3(256), NB * 4, st>>>((const uint32_t*)d_scalars, n, mont, p->c, Wd, p->sort_low, NB,
                                                             p->d_coarse_count, p->d_blockhist, tile, fold_stride, p->bits);
-    if (prof) HIPCHK(hipEventRecord(p->ev[1], st));
+    if (ev_digits) HIPCHK(hipEventRecord(ev_digits, st));
     launch_scan(p->d_coarse_count, p->d_coarse_off, p->d_tilesums, NB, st);
     if (staged) {
       int group = 1;  // lanes per bin in the write-out: the mean run length, rounded down to a power of two
@@ -350,7 +375,7 @@ int launch_sort(mlhip_msm_plan* p, const void* d_scalars, int mont, size_t n, hi
       k_digits<C><<<dim3((unsigned)blocks), dim3(256), 0, st>>>((const uint32_t*)d_scalars, n, mont, p->c, p->W, p->M,
                                                                  p->d_digits, p->d_counts, p->bits);
     }
-    if (prof) HIPCHK(hipEventRecord(p->ev[1], st));
+    if (ev_digits) HIPCHK(hipEventRecord(ev_digits, st));
     launch_scan(p->d_counts, p->d_offsets, p->d_tilesums, nbuckets, st);
     {
       size_t total_e = (size_t)p->W * n;
@@ -449,9 +474,9 @@ int launch_reduce(mlhip_msm_plan* p, hipStream_t st) {
   return 0;
 }
 
-template <class C, class F>
-int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,
-                size_t n, int K, hipStream_t st);
+template <class C>
+int plan_stream_train(mlhip_msm_plan* const* ps, void* const* d_points, const void* const* h_points, int k, void* d_scalars,
+                      const void* h_scalars, int mont, size_t n, int K, bool schedule, hipStream_t st);
 
 // ---- the steps plan_launch (one pass) and stream_tile / stream_end (a train of segments or tiles) share -------------------
 
@@ -467,7 +492,7 @@ inline int fold_check_args(const mlhip_msm_plan* p, size_t n, bool points_travel
 // window (2-4x the mean for these group orders), stay on the one-thread-per-bucket path.
 // (a folded plan's buckets collect the entries of all Wd digits: the mean is Wd len / 2^(c-1))
 inline uint32_t big_bucket_threshold(const mlhip_msm_plan* p, size_t len) {
-  const uint32_t t = (uint32_t)std::min<size_t>((((size_t)(p->fold ? p->Wd : 1) * len) >> (p->c - 1)) * 8, 1u << 30);
+  const uint32_t t = (uint32_t)std::min<size_t>(((entries_per_bucket_set(p) * len) >> (p->c - 1)) * 8, 1u << 30);
   return t < BIG_BUCKET_MIN ? BIG_BUCKET_MIN : t;
 }
 
@@ -491,8 +516,8 @@ void launch_convert(const mlhip_msm_plan* p, const Affine<F>* src, size_t len, s
 
 // The bucket accumulation of one segment of `len` scalars, and the long-bucket step that belongs to it (k_big_prefix, the
 // slices, the kernel that adds the slice sums): the one place that picks these kernels.
-//   sv        the plan whose entry lists (sorted / offsets / counts / order) describe the segment: p itself, a sort-ahead
-//             helper record, or the G1 plan of a shared-scalar MSM
+//   sv        the entry lists (sorted / offsets / counts / order) that describe the segment: p's own, a sort-ahead record,
+//             or those of the first plan of a shared-scalar train.  The count of long buckets is always p's own.
 //   row0      first carry-free row of the segment in d_points28 (a folded plan: fold_row of its tile)
 //   d_points  the segment's points in the boundary form, read by the MLHIP_ACC32 kernels and the slices of a plain plan
 //             (a folded plan gathers from d_points28 + row0 only: a token)
@@ -500,7 +525,7 @@ void launch_convert(const mlhip_msm_plan* p, const Affine<F>* src, size_t len, s
 //   ev_mid    recorded between the accumulation and the long-bucket step (null: no event)
 //   one_pass  the segment is the whole MSM, launched by plan_launch.  What a single pass does differently from a tile:
 template <class C, class F>
-int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, const Affine<F>* d_points, int flags, bool ed,
+int launch_accumulate(mlhip_msm_plan* p, const MsmEntryLists* sv, size_t row0, const Affine<F>* d_points, int flags, bool ed,
                       size_t len, bool one_pass, hipEvent_t ev_mid, hipStream_t st) {
   typedef XYZZ<F> X;
   constexpr bool kG2 = std::is_same<F, Fp2Field<C>>::value;  // two lanes per bucket
@@ -510,7 +535,7 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
   const uint32_t big_threshold = big_bucket_threshold(p, len);
   // (1) a bucket holds at most all len entries (Wd len when folded): a small MSM skips the three near-empty launches of
   //     the long-bucket step.  A tile always runs them: whether an MSM has long buckets does not show in one tile's length.
-  const bool long_buckets = !one_pass || (size_t)(p->fold ? p->Wd : 1) * len > big_threshold;
+  const bool long_buckets = !one_pass || entries_per_bucket_set(p) * len > big_threshold;
   // (2) too few buckets to fill the chip with one lane each: one bucket per quad of lanes (shorter dependent chains), ahead
   //     of the Edwards test.  The quad kernel keeps no state between segments, so tiles never use it.
   const bool quad = !kG2 && one_pass && p->d_points28 && p->reduce28 && nbuckets <= QUAD_ACC_MAX_BUCKETS && !getenv("MLHIP_NO_QUAD_ACC");
@@ -523,16 +548,16 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
   const dim3 grid((unsigned)(((kG2 ? 2 : 1) * nbuckets + p->acc_block - 1) / p->acc_block)), block(p->acc_block);
   auto seg = [&](auto kernel, auto rows, auto state, auto... buckets) {
     kernel<<<grid, block, 0, st>>>(rows + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order, big_threshold,
-                                   p->d_biglist, p->d_bigcount, state, flags, buckets...);
+                                   p->d_biglist, p->lists.d_bigcount, state, flags, buckets...);
   };
   if (!p->d_points28) {
     if constexpr (kBuildAlt) {
       if constexpr (kG2)
         k_accumulate_lp<C><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                                 big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+                                                 big_threshold, p->d_biglist, p->lists.d_bigcount, (X*)p->d_buckets);
       else
         k_accumulate<F><<<grid, block, 0, st>>>(d_points, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, sv->d_order,
-                                              big_threshold, p->d_biglist, p->d_bigcount, (X*)p->d_buckets);
+                                              big_threshold, p->d_biglist, p->lists.d_bigcount, (X*)p->d_buckets);
     }
   } else if constexpr (kG2) {
     typedef XYZZ28L<Fp28<C>> S;
@@ -545,7 +570,7 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
   } else if (quad) {
     k_accumulate_q28<C><<<dim3((unsigned)((4 * nbuckets + 255) / 256)), dim3(256), 0, st>>>(
         (const Affine28<C>*)p->d_points28 + row0, sv->d_sorted, sv->d_offsets, sv->d_counts, nbuckets, big_threshold, p->d_biglist,
-        p->d_bigcount, (XYZZ28<C>*)p->d_state28);
+        p->lists.d_bigcount, (XYZZ28<C>*)p->d_state28);
   } else if (ed) {  // (implies reduce28: the last segment leaves its extended coordinates for the reduction)
     if constexpr (C::HAS_EDWARDS) seg(k_accumulate_ed28_seg<C>, (const EdNiels28<C>*)p->d_points28, (XYZZ28<C>*)p->d_state28);
   } else {
@@ -556,7 +581,7 @@ int launch_accumulate(mlhip_msm_plan* p, const mlhip_msm_plan* sv, size_t row0, 
   // (4) the slices of a plain plan gather from d_points, those of a folded plan from d_points28 + row0
   launch_big_slices<F>(p, d_points, st, sv, row0);
   auto combine = [&](auto kernel, auto state, auto... buckets) {
-    kernel<<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(p->d_biglist, p->d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, state,
+    kernel<<<dim3(256), dim3(BB), BB * sizeof(X), st>>>(p->d_biglist, p->lists.d_bigcount, p->d_bigprefix, (const X*)p->d_bigpart, state,
                                                         flags, buckets...);
   };
   if constexpr (kG2) {
@@ -605,8 +630,10 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
   if (n != 0 && !p->upload_src) {
     const int K = resident_tiles(p->aux && p->d_points28, std::is_same<F, Fp2Field<C>>::value, p->fold, p->fold_tile,
                                  plan_use_edwards<C, F>(p), n);
-    if (K > 1)
-      return plan_stream<C, F>(p, const_cast<void*>(d_points), const_cast<void*>(d_scalars), nullptr, nullptr, mont, n, K, st);
+    if (K > 1) {  // the train of this one plan, everything resident
+      void* dp = const_cast<void*>(d_points);
+      return plan_stream_train<C>(&p, &dp, nullptr, 1, const_cast<void*>(d_scalars), nullptr, mont, n, K, true, st);
+    }
   }
   p->tiles_timed = 0;
   p->pending_n = n;
@@ -622,9 +649,9 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
     // (LDS-atomic bound) sort kernels.  The fork is recorded now (after the previous MSM's work on `st`); the work
     // itself is queued after the sort launches so that a host-blocking upload cannot delay them.
     if (p->d_points28) HIPCHK(hipEventRecord(p->ev_fork, st));
-    HIPCHK(hipMemsetAsync(p->d_zero, 0, p->zero_bytes, st));
+    HIPCHK(hipMemsetAsync(p->lists.d_zero, 0, p->lists.zero_bytes, st));
     if (prof) HIPCHK(hipEventRecord(p->ev[0], st));
-    if (int rc_sort = launch_sort<C>(p, d_scalars, mont, n, st, prof)) return rc_sort;
+    if (int rc_sort = launch_sort<C>(&p->lists, d_scalars, mont, n, st, prof ? p->ev[1] : nullptr)) return rc_sort;
     // resident bases: the carry-free copy of the first conv_n points of this very buffer is already there
     const bool use_ed = p->fold ? p->conv_ed : plan_use_edwards<C, F>(p);  // (a table is read in the form it was built in)
     p->last_ed = use_ed;
@@ -647,7 +674,7 @@ int plan_launch(mlhip_msm_plan* p, const void* d_points, const void* d_scalars, 
     if (p->d_points28) HIPCHK(hipStreamWaitEvent(st, p->ev_join, 0));
     // (the Edwards form always leaves its state and reads no MLHIP_SEG_KEEP28)
     const int flags = MLHIP_SEG_FIRST | MLHIP_SEG_LAST | (p->reduce28 ? MLHIP_SEG_KEEP28 : 0);
-    if (int rc = launch_accumulate<C, F>(p, p, 0, (const A*)d_points, flags, use_ed, n, true, prof ? p->ev[3] : nullptr, st)) return rc;
+    if (int rc = launch_accumulate<C, F>(p, &p->lists, 0, (const A*)d_points, flags, use_ed, n, true, prof ? p->ev[3] : nullptr, st)) return rc;
     return finish_train<C, F>(p, prof, st);
   }
   return 0;
@@ -715,10 +742,10 @@ int stream_begin(mlhip_msm_plan* p, StreamCtx& cx, hipStream_t st, int min_K) {
 }
 
 // tile s = pairs [off, off + len): uploads / conversion on the auxiliary stream, then sort and accumulation on `st`.
-// `sorter` != nullptr: the tile was already sorted in ANOTHER plan of the same window geometry over the same scalars
-// (mlhip_msm_launch_shared: the G1 and the G2 MSM of one scalar vector) -- its entry lists are read, nothing is sorted.
+// `sorter` != nullptr: the tile was already sorted into these entry lists -- a sort-ahead record, or the lists of ANOTHER plan
+// of the same window geometry over the same scalars (plan_stream_train) -- which are read; nothing is sorted.
 template <class C, class F>
-int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, const mlhip_msm_plan* sorter) {
+int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, const MsmEntryLists* sorter) {
   typedef Affine<F> A;
   const size_t off = cx.bound[s];
   const size_t len = cx.bound[s + 1] - off;
@@ -741,17 +768,17 @@ int stream_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s, hipStream_t st, c
   }
   HIPCHK(hipEventRecord(p->ev_seg[s], p->aux));
   if (prof && first) HIPCHK(hipEventRecord(p->ev[0], st));
-  HIPCHK(hipMemsetAsync(p->d_zero, 0, p->zero_bytes, st));
+  HIPCHK(hipMemsetAsync(p->lists.d_zero, 0, p->lists.zero_bytes, st));  // (with a sorter too: the count of long buckets)
   if (prof) HIPCHK(hipEventRecord(p->ev_tile[s][0], st));
   const bool uploads = hs || !cx.resident;
   if (uploads) HIPCHK(hipStreamWaitEvent(st, split ? p->ev_seg_sc[s] : p->ev_seg[s], 0));  // the sort needs the uploaded scalars
   if (!sorter) {
-    int rc_sort = launch_sort<C>(p, dsc, cx.mont, len, st, false);
+    int rc_sort = launch_sort<C>(&p->lists, dsc, cx.mont, len, st, nullptr);
     if (rc_sort) return rc_sort;
   }
   if (!uploads || split) HIPCHK(hipStreamWaitEvent(st, p->ev_seg[s], 0));  // only the accumulation waits for points / conversion
   if (prof) HIPCHK(hipEventRecord(p->ev_tile[s][1], st));
-  if (int rc = launch_accumulate<C, F>(p, sorter ? sorter : p, row0, dpt, flags, cx.ed, len, false, nullptr, st)) return rc;
+  if (int rc = launch_accumulate<C, F>(p, sorter ? sorter : &p->lists, row0, dpt, flags, cx.ed, len, false, nullptr, st)) return rc;
   if (prof) HIPCHK(hipEventRecord(p->ev_tile[s][2], st));
   return 0;
 }
@@ -770,52 +797,38 @@ int stream_end(mlhip_msm_plan* p, const StreamCtx& cx, hipStream_t st) {
 // ---- sorting ahead (round 3) ----------------------------------------------------------------------------------------------
 // A tiled device-resident MSM ran sort(0), accumulate(0), sort(1), accumulate(1) ... on one stream: the sort kernels are
 // bound by LDS atomics and leave the multipliers idle, the accumulation is the opposite.  The entry lists of tile s + 1
-// are now sorted on a second stream, in one of two helper records that own sort buffers only, while tile s accumulates
-// on the caller's stream from the other record's lists (the `sorter` argument of stream_tile, as the G2 plan of a
-// shared-scalar MSM reads the G1 plan's lists).  Events: ev_sorted[b] (sort stream -> accumulation), ev_lists_free[b]
+// are now sorted on a second stream, into one of two further MsmEntryLists of the plan's geometry, while tile s accumulates
+// on the caller's stream from the other record's lists (the `sorter` argument of stream_tile, as the later plans of a
+// shared-scalar train read the first plan's lists).  Events: ev_sorted[b] (sort stream -> accumulation), ev_lists_free[b]
 // (accumulation -> the next sort into record b; it also orders consecutive MSMs on the plan).  MLHIP_SORT_AHEAD=0: off.
 template <class C>
 int sort_ahead_prepare(mlhip_msm_plan* p, size_t seg, bool& on) {
   on = false;
   const char* e = getenv("MLHIP_SORT_AHEAD");
   if (e && e[0] == '0') return 0;
-  if (p->sort_low <= 0) return 0;  // the legacy sort shares the digits buffer with the accumulation path: not split
+  if (p->lists.sort_low <= 0) return 0;  // the legacy sort shares the digits buffer with the accumulation path: not split
   for (int b = 0; b < 2; b++) {
-    mlhip_msm_plan* h = p->sort_helper[b];
-    if (h && h->max_n < seg) {  // longer tiles than last time: rebuild
+    MsmEntryLists* h = p->sort_helper[b];
+    if (h && h->cap < seg) {  // longer tiles than last time: rebuild
       (void)hipStreamSynchronize(p->sort_stream);
-      mlhip_msm_plan_destroy(h);
+      entry_lists_free(h);
+      delete h;
       h = p->sort_helper[b] = nullptr;
     }
     if (!h) {
-      h = new mlhip_msm_plan();
-      h->curve = p->curve;
-      h->group = p->group;
-      h->device = p->device;
-      h->c = p->c;
-      h->bits = p->bits;
-      h->W = p->W;
-      h->Wd = p->Wd;
-      h->fold = p->fold;
-      h->fold_tile = p->fold_tile;
-      h->M = p->M;
-      h->L = p->L;
-      h->lgL = p->lgL;
-      h->T = p->T;
-      h->nb = p->nb;
-      h->nsel = p->nsel;
-      h->max_n = seg;
-      // The helper is an optimisation: if its buffers do not fit (two copies of the tile's entry lists; plausible at
+      // The record is an optimisation: if its buffers do not fit (two copies of the tile's entry lists; plausible at
       // 2^24 pairs) the MSM must still run, with the sort in line as before.  The record is registered only once it is
-      // complete -- a half-allocated one left in p->sort_helper would pass the `max_n >= seg` test of the next launch
+      // complete -- a half-allocated one left in p->sort_helper would pass the `cap >= seg` test of the next launch
       // and hand null list pointers to launch_sort.  MLHIP_FAULT_INJECT=sort_helper_alloc makes the allocation "fail"
       // (tests/test_gpu_parity.py::test_sort_ahead_helper_allocation_failure).
+      h = new MsmEntryLists(plan_entry_lists(p, seg));
       const char* fi = getenv("MLHIP_FAULT_INJECT");
-      int rc = (fi && !strcmp(fi, "sort_helper_alloc")) ? MLHIP_ENOMEM : plan_alloc_sort(h);
+      int rc = (fi && !strcmp(fi, "sort_helper_alloc")) ? MLHIP_ENOMEM : entry_lists_alloc(h);
       if (rc || h->sort_low <= 0) {
-        mlhip_msm_plan_destroy(h);  // frees whatever was allocated
-        (void)hipGetLastError();    // an out-of-memory error must not surface in the next HIPCHK
-        return 0;                   // on = false: the in-line path
+        entry_lists_free(h);      // whatever was allocated
+        delete h;
+        (void)hipGetLastError();  // an out-of-memory error must not surface in the next HIPCHK
+        return 0;                 // on = false: the in-line path
       }
       p->sort_helper[b] = h;  // owned by p from here on
     }
@@ -836,61 +849,32 @@ int sort_ahead_prepare(mlhip_msm_plan* p, size_t seg, bool& on) {
   on = true;
   return 0;
 }
-// queue the sort of tile s into helper record s & 1 (after whatever still reads that record's lists)
+// queue the sort of tile s into record s & 1 (after whatever still reads that record's lists)
 template <class C>
 int sort_ahead_tile(mlhip_msm_plan* p, const StreamCtx& cx, int s) {
   const int b = s & 1;
-  mlhip_msm_plan* h = p->sort_helper[b];
+  const MsmEntryLists* h = p->sort_helper[b];
   const size_t off = cx.bound[s];
   const size_t len = cx.bound[s + 1] - off;
   HIPCHK(hipStreamWaitEvent(p->sort_stream, p->ev_lists_free[b], 0));  // never recorded yet: no wait
   HIPCHK(hipMemsetAsync(h->d_zero, 0, h->zero_bytes, p->sort_stream));
-  int rc = launch_sort<C>(h, (const char*)cx.d_scalars + off * 32, cx.mont, len, p->sort_stream, false);
+  int rc = launch_sort<C>(h, (const char*)cx.d_scalars + off * 32, cx.mont, len, p->sort_stream, nullptr);
   if (rc) return rc;
   HIPCHK(hipEventRecord(p->ev_sorted[b], p->sort_stream));
   return 0;
 }
 
-template <class C, class F>
-int plan_stream(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points, const void* h_scalars, int mont,
-                size_t n, int K, hipStream_t st) {
-  StreamCtx cx;
-  cx.d_points = d_points;
-  cx.d_scalars = d_scalars;
-  cx.h_points = h_points;
-  cx.h_scalars = h_scalars;
-  cx.mont = mont;
-  cx.n = n;
-  cx.K = K;
-  if (h_scalars && std::is_same<F, FpField<C>>::value)
-    stream_schedule(cx, h_points != nullptr, schedule_tile(p->fold, p->fold_tile, plan_use_edwards<C, F>(p)), p->fold != 0);
-  int rc = stream_begin<C, F>(p, cx, st, 2);
-  if (rc) return rc;
-  bool ahead = false;
-  if (!h_scalars && !h_points) {  // device-resident tiles: nothing to upload, the sorts can run ahead
-    rc = sort_ahead_prepare<C>(p, cx.seg, ahead);
-    if (rc) return rc;
-  }
-  if (ahead) HIPCHK(hipStreamWaitEvent(p->sort_stream, p->ev_fork, 0));  // the scalars are ready where `st` stood at launch
-  for (int s = 0; s < cx.K; s++) {
-    if (ahead) {
-      rc = sort_ahead_tile<C>(p, cx, s);
-      if (rc) return rc;
-      HIPCHK(hipStreamWaitEvent(st, p->ev_sorted[s & 1], 0));
-    }
-    rc = stream_tile<C, F>(p, cx, s, st, ahead ? p->sort_helper[s & 1] : nullptr);
-    if (rc) return rc;
-    if (ahead) HIPCHK(hipEventRecord(p->ev_lists_free[s & 1], st));
-  }
-  return stream_end<C, F>(p, cx, st);
-}
-
-// A class of k plans of ONE window geometry, of either group, over one scalar vector: every tile is sorted once -- in the
-// first plan, or with sort-ahead in its helper record -- and accumulated once per plan, plan after plan, on one stream.
-// stream_end of a plan is queued as soon as its last tile is (the last plan's after the loop), so that its reduction, its
-// copy to the host and the host tail of its result run under the next plan's accumulation.
-//   d_points[j] / h_points[j]   as plan_stream's, per plan (a folded plan brings none: its table)
-//   h_scalars                   uploaded once, by the first plan's tiles; `schedule`: a G1 first plan cuts them as plan_stream does
+// THE train: a class of k plans of ONE window geometry, of either group, over one scalar vector.  Every tile is sorted once
+// -- into the first plan's lists, or with sort-ahead into one of its two further records -- and accumulated once per plan,
+// plan after plan, on one stream.  stream_end of a plan is queued as soon as its last tile is (the last plan's after the
+// loop), so that its reduction, its copy to the host and the host tail of its result run under the next plan's accumulation.
+//   d_points[j]   plan j's points in device memory (a folded plan brings none: its table), or the buffer they are staged in
+//   h_points      null: every plan's points are resident; else h_points[j] = the caller's pageable points of plan j (or null),
+//                 uploaded tile by tile on that plan's auxiliary stream
+//   h_scalars     null: the scalars are at d_scalars; else uploaded once, by the first plan's tiles
+//   schedule      a G1 first plan whose scalars travel cuts its segments by stream_schedule (msm_segments.h)
+// k = 1 is the train of a single plan -- a host-buffer MSM streamed in segments, or a device-resident one cut into tiles --
+// and needs at least two segments (one is plan_launch's single pass); a class may run a single tile.
 // Folded plans: the cuts are segment_cuts' over the class's fold_tile, row0 = fold_row(p, off) is taken per plan, and the
 // slices of long buckets gather from each plan's own d_points28 through the sorter's lists (launch_big_slices).
 template <class C>
@@ -921,19 +905,20 @@ int plan_stream_train(mlhip_msm_plan* const* ps, void* const* d_points, const vo
     stream_schedule(cx[0], cx[0].h_points != nullptr, schedule_tile(p0->fold, p0->fold_tile, plan_use_edwards<C, F1>(p0)), p0->fold != 0);
     for (int j = 1; j < k; j++) static_cast<SegmentCuts&>(cx[j]) = cx[0];  // (before segment_cuts: every plan cuts alike)
   }
+  const int min_K = k == 1 ? 2 : 1;
   for (int j = 0; j < k; j++) {
-    int rc = g1(j) ? stream_begin<C, F1>(ps[j], cx[j], st, 1) : stream_begin<C, F2>(ps[j], cx[j], st, 1);
+    int rc = g1(j) ? stream_begin<C, F1>(ps[j], cx[j], st, min_K) : stream_begin<C, F2>(ps[j], cx[j], st, min_K);
     if (rc) return rc;
   }
   bool ahead = false;
-  if (!h_scalars && !points_travel && cx[0].K >= 2) {
+  if (!h_scalars && !points_travel && cx[0].K >= 2) {  // device-resident tiles: nothing to upload, the sorts can run ahead
     int rc = sort_ahead_prepare<C>(p0, cx[0].seg, ahead);
     if (rc) return rc;
   }
-  if (ahead) HIPCHK(hipStreamWaitEvent(p0->sort_stream, p0->ev_fork, 0));
+  if (ahead) HIPCHK(hipStreamWaitEvent(p0->sort_stream, p0->ev_fork, 0));  // the scalars are ready where `st` stood at launch
   auto end = [&](int j) { return g1(j) ? stream_end<C, F1>(ps[j], cx[j], st) : stream_end<C, F2>(ps[j], cx[j], st); };
   for (int s = 0; s < cx[0].K; s++) {
-    const mlhip_msm_plan* lists = p0;  // whose entry lists the later plans' tiles read
+    const MsmEntryLists* lists = &p0->lists;  // the entry lists the later plans' tiles read
     if (ahead) {
       int rc = sort_ahead_tile<C>(p0, cx[0], s);
       if (rc) return rc;
@@ -941,7 +926,7 @@ int plan_stream_train(mlhip_msm_plan* const* ps, void* const* d_points, const vo
       lists = p0->sort_helper[s & 1];
     }
     for (int j = 0; j < k; j++) {
-      const mlhip_msm_plan* sorter = j == 0 ? (ahead ? lists : nullptr) : lists;
+      const MsmEntryLists* sorter = j == 0 ? (ahead ? lists : nullptr) : lists;
       int rc = g1(j) ? stream_tile<C, F1>(ps[j], cx[j], s, st, sorter) : stream_tile<C, F2>(ps[j], cx[j], s, st, sorter);
       if (rc) return rc;
       if (s + 1 == cx[0].K && j + 1 < k) {
@@ -952,25 +937,6 @@ int plan_stream_train(mlhip_msm_plan* const* ps, void* const* d_points, const vo
     if (ahead) HIPCHK(hipEventRecord(p0->ev_lists_free[s & 1], st));
   }
   return end(k - 1);
-}
-
-// The G1 MSM and the G2 MSM of ONE scalar vector (device-resident inputs; BASELINE configs[3], a Groth16 prover's
-// B-query): the entry lists of a tile depend on the scalars and the window geometry only, so every tile is sorted once
-// (in the G1 plan) and accumulated twice.  One stream, tile by tile: sort, G1 accumulation, G2 accumulation.
-// Host buffers (h_* != nullptr: the caller's pageable memory, staged through d_*): the scalars and the G1 points of a
-// tile travel on the G1 plan's auxiliary stream, the G2 points on the G2 plan's, under the kernels of the tile before.
-template <class C>
-int plan_stream_shared(mlhip_msm_plan* p1, mlhip_msm_plan* p2, void* d_points_g1, void* d_points_g2, void* d_scalars,
-                       const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n,
-                       hipStream_t st) {
-  if (p1->c != p2->c || p1->W != p2->W || p1->M != p2->M || p1->bits != p2->bits)
-    return mlhip_rt::fail(MLHIP_EINVAL, "the two plans of a shared-scalar MSM need the same window width and scalar width");
-  // (plans over shifted-base tables belong to resident-bases handles: their shared-scalar MSM is a set's, mlhip_bases_set_create)
-  if (p1->fold || p2->fold) return mlhip_rt::fail(MLHIP_EINVAL, "shared-scalar MSM: plans with shifted-base tables are not supported");
-  mlhip_msm_plan* ps[2] = {p1, p2};
-  void* dp[2] = {d_points_g1, d_points_g2};
-  const void* hp[2] = {h_points_g1, h_points_g2};
-  return plan_stream_train<C>(ps, dp, hp, 2, d_scalars, h_scalars, mont, n, shared_segments(h_scalars != nullptr, n), false, st);
 }
 
 // What the tail kernel needs of a plan (msm_tail.h: MsmTailArgs).
@@ -1046,23 +1012,9 @@ int plan_finish(mlhip_msm_plan* p, void* out_affine, void* out_xyzz) {
     HIPCHK(hipEventSynchronize(p->done));
     auto t0 = std::chrono::steady_clock::now();
     host_tail<F>(p, total);
-    if (p->profiling && p->tiles_timed > 0) {
-      // tiles: digits are part of each tile's sort; accumulate = the sum over the tiles' accumulation kernels
-      p->ms[0] = p->ms[1] = p->ms[2] = 0;
-      for (int s = 0; s < p->tiles_timed; s++) {
-        float a = 0, b = 0;
-        HIPCHK(hipEventElapsedTime(&a, p->ev_tile[s][0], p->ev_tile[s][1]));
-        HIPCHK(hipEventElapsedTime(&b, p->ev_tile[s][1], p->ev_tile[s][2]));
-        p->ms[1] += a;
-        p->ms[2] += b;
-      }
-      HIPCHK(hipEventElapsedTime(&p->ms[3], p->ev[3], p->ev[4]));
-      HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
-      p->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    } else if (p->profiling && p->tiles_timed == 0) {
-      for (int i = 0; i < 4; i++) HIPCHK(hipEventElapsedTime(&p->ms[i], p->ev[i], p->ev[i + 1]));
-      HIPCHK(hipEventElapsedTime(&p->ms[4], p->ev[0], p->ev[4]));
-      p->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (p->profiling && p->tiles_timed >= 0) {
+      if (int rc_times = plan_read_phase_times(p)) return rc_times;
+      p->ms[5] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();  // the host tail
     } else if (p->profiling) {
       for (int i = 0; i < 6; i++) p->ms[i] = 0;  // a streamed host-buffer MSM records no phase events: nothing stale is left
     }

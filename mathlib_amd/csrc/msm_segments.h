@@ -1,7 +1,7 @@
 // msm_segments.h -- how an MSM is cut into segments / tiles: plain integer arithmetic on (group, n, the plan's fold_tile, a
 // few flags, the MLHIP_* switches), without a HIP type, so that tests/hostmath_segments replays it on the CPU
-// (tests/test_msm_segments_host.py; the recorded cuts are tests/golden/msm_segments.json).  The trains that run the
-// segments are in msm_plan.h (plan_stream, plan_stream_shared); api_msm.hip and api_bases.hip ask stream_segments.
+// (tests/test_msm_segments_host.py; the recorded cuts are tests/golden/msm_segments.json).  The train that runs the
+// segments is in msm_plan.h (plan_stream_train); api_msm.hip and api_bases.hip ask stream_segments.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -13,13 +13,13 @@ namespace mlhip {
 
 // the cuts of one streamed / tiled MSM (the part of msm_plan.h's StreamCtx that is policy)
 struct SegmentCuts {
-  size_t n = 0, seg = 0;  // seg: the longest segment (what a sort-ahead helper record must hold)
+  size_t n = 0, seg = 0;  // seg: the longest segment (what a sort-ahead record must hold)
   int K = 0;
   size_t bound[MLHIP_MAX_SEGMENTS + 1] = {};  // segment s = pairs [bound[s], bound[s + 1])
   bool scheduled = false;                     // bound[] was filled by the caller (stream_schedule); else K equal segments
 };
 
-// Number of tiles a device-resident MSM is cut into (1 = one pass over all points); see plan_stream.  Measured
+// Number of tiles a device-resident MSM is cut into (1 = one pass over all points); see plan_stream_train.  Measured
 // (profiles/r02_tiles.txt): G1 from 2^22 points on in tiles of 2^21 (235 MB of points), G2 from 2^23 on in tiles of 2^20
 // (also 235 MB); at most MLHIP_MAX_SEGMENTS tiles.
 // MLHIP_TILE_LOG2 = t forces tiles of 2^t points for every n above that (0 = never tile).
@@ -63,12 +63,12 @@ inline int stream_segments(bool can_stream, bool kG1, size_t n) {
   }
   // segments of 2^18 pairs: at 2^20 the call drops from 5.9 to 4.5 ms, at 2^22 from 21.9 to 12.8 ms (the device-only time)
   // G2 (BLS12-381): segments of 2^17 pairs, 14.9 -> 11.4 ms at 2^20.  For G1 from 2^20 pairs on the count returned here only
-  // says "stream": plan_stream replaces the equal segments by a growing schedule (stream_schedule, round 4)
+  // says "stream": the train replaces the equal segments by a growing schedule (stream_schedule, round 4)
   const size_t k = n >> (kG1 ? 18 : 17);
   return k < 2 ? 1 : (k > MLHIP_MAX_SEGMENTS ? MLHIP_MAX_SEGMENTS : (int)k);
 }
 
-// Number of tiles of the G1 + G2 MSM of one scalar vector (plan_stream_shared)
+// Number of tiles of the G1 + G2 MSM of one scalar vector (api_msm.hip: plan_shared)
 inline int shared_segments(bool scalars_travel, size_t n) {
   int K = 1;
   if (scalars_travel) {

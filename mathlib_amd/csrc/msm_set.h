@@ -46,7 +46,7 @@ inline int set_classes(const SetGeometry* g, int k, int* cls) {
 
 // Tiles of a class of two or more members over n scalars.
 //   scalars_travel: the class uploads the call's host scalars (the first class of mlhip_bases_msm on a set) -- the segments of
-//   the first member's own mlhip_bases_msm (stream_segments; a G1 first member's are then scheduled as plan_stream's are);
+//   the first member's own mlhip_bases_msm (stream_segments; a G1 first member's are then scheduled as a single plan's are);
 //   otherwise the scalars are in device memory: the tiles of a folded plan's table, or those of the shared-scalar pair.
 inline int set_class_tiles(const SetGeometry& g, bool first_is_g1, bool scalars_travel, size_t n) {
   if (scalars_travel) return stream_segments(true, first_is_g1, n);

@@ -13,19 +13,9 @@ int MLHIP_TU_FN(plan_finish)(mlhip_msm_plan* p, void* out_affine, void* out_xyzz
   if (p->group == MLHIP_GROUP_G1) return plan_finish<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(p, out_affine, out_xyzz);
   return plan_finish<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(p, out_affine, out_xyzz);
 }
-int MLHIP_TU_FN(plan_stream)(mlhip_msm_plan* p, void* d_points, void* d_scalars, const void* h_points,
-                            const void* h_scalars, int mont, size_t n, int segments, hipStream_t st) {
-  if (p->group == MLHIP_GROUP_G1) return plan_stream<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(p, d_points, d_scalars, h_points, h_scalars, mont, n, segments, st);
-  return plan_stream<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(p, d_points, d_scalars, h_points, h_scalars, mont, n, segments, st);
-}
-int MLHIP_TU_FN(plan_shared)(mlhip_msm_plan* g1, mlhip_msm_plan* g2, void* d_points_g1, void* d_points_g2, void* d_scalars,
-                            const void* h_points_g1, const void* h_points_g2, const void* h_scalars, int mont, size_t n,
-                            hipStream_t st) {
-  return plan_stream_shared<MLHIP_TU_CURVE>(g1, g2, d_points_g1, d_points_g2, d_scalars, h_points_g1, h_points_g2, h_scalars, mont, n, st);
-}
-int MLHIP_TU_FN(plan_train)(mlhip_msm_plan* const* plans, void* const* d_points, int k, void* d_scalars, const void* h_scalars,
-                           int mont, size_t n, int segments, hipStream_t st) {
-  return plan_stream_train<MLHIP_TU_CURVE>(plans, d_points, nullptr, k, d_scalars, h_scalars, mont, n, segments, true, st);
+int MLHIP_TU_FN(plan_train)(mlhip_msm_plan* const* plans, void* const* d_points, const void* const* h_points, int k,
+                           void* d_scalars, const void* h_scalars, int mont, size_t n, int segments, bool schedule, hipStream_t st) {
+  return plan_stream_train<MLHIP_TU_CURVE>(plans, d_points, h_points, k, d_scalars, h_scalars, mont, n, segments, schedule, st);
 }
 int MLHIP_TU_FN(scalar_mul)(int group, const void* d_points, size_t point_stride, const void* d_scalars, int mont,
                               size_t n, void* d_out, hipStream_t st, bool subgroup) {

@@ -17,8 +17,8 @@ int hseg_stream_segments(int can_stream, int g1, size_t n) { return stream_segme
 
 int hseg_shared_segments(int scalars_travel, size_t n) { return shared_segments(scalars_travel != 0, n); }
 
-// The cuts of one train of K >= min_K segments, as plan_stream (shared == 0: a G1 MSM whose scalars travel is scheduled
-// first) or plan_stream_shared (shared != 0) followed by stream_begin make them.  bound: MLHIP_MAX_SEGMENTS + 1 entries.
+// The cuts of one train of K >= min_K segments, as plan_stream_train with `schedule` (shared == 0: a G1 MSM whose scalars travel is
+// scheduled first) or without (shared != 0: the G1 + G2 pair) followed by stream_begin make them.  bound: MLHIP_MAX_SEGMENTS + 1 entries.
 // 0, or 1 = "bad segment count", 2 = "folded plan: too many tiles" (both MLHIP_EINVAL in the library).
 int hseg_train(int g1, size_t n, int K, int min_K, int fold, size_t fold_tile, int scalars_travel, int points_travel, int edwards,
                int shared, size_t* bound, int* K_out, size_t* seg_out) {

@@ -42,7 +42,7 @@ def hseg():
 
 
 def train(hseg, group, n, K, fold_tile=0, scalars_travel=False, points_travel=False, edwards=False, shared=False):
-    """The bounds and the longest segment of a train of K segments (msm_plan.h: plan_stream / plan_stream_shared), or the
+    """The bounds and the longest segment of a train of K segments (msm_plan.h: plan_stream_train), or the
     library's error."""
     bound = (ctypes.c_size_t * (hseg.hseg_max_segments() + 1))()
     k, seg = ctypes.c_int(0), ctypes.c_size_t(0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device-resident MSMs cut into tiles (msm_plan.h: plan_stream; msm_segments.h: resident_tiles): accumulation time against the tile size.
+"""Device-resident MSMs cut into tiles (msm_plan.h: plan_stream_train; msm_segments.h: resident_tiles): accumulation time against the tile size.
 BLS12-381 G1 and G2, n = 2^22 .. 2^24, MLHIP_TILE_LOG2 = 0 (one pass) / 20 / 21 / 22 and the library's own choice."""
 import os
 import sys
