@@ -170,7 +170,8 @@ func (c *Curve) MultiScalarMulBatch(a [][]driver.G1, b [][]driver.Zr) []driver.G
 // MultiScalarMulBatchSubgroup is MultiScalarMulBatch for points the caller knows to be in G1 (decoded with the subgroup
 // check, issuer keys, generators, outputs of earlier MSMs): the same results with half of the chunks' doublings, from the
 // curve's endomorphism and a split of every scalar (mlhip_msm_batch_subgroup, DESIGN.md section 19).  A point outside G1
-// gives an undefined result for its own segment; MultiScalarMulBatch accepts any point of the curve.
+// gives an undefined result for its own segment; MultiScalarMulBatch accepts any point of the curve.  On BN254 every point
+// of the curve is in G1 (the lattice split of DESIGN.md section 20 runs): only a point off the curve breaks the promise.
 func (c *Curve) MultiScalarMulBatchSubgroup(a [][]driver.G1, b [][]driver.Zr) []driver.G1 {
 	return c.msmBatchG1(a, b, true)
 }
@@ -589,7 +590,8 @@ func (c *Curve) MulBatchG1(a []driver.G1, b []driver.Zr) []driver.G1 {
 // MulBatchSubgroupG1 is MulBatchG1 for points the caller knows to be in G1 (decoded with the subgroup check, MSM outputs
 // over checked bases, generators and their multiples): the same results from the curve's endomorphism and a split of the
 // scalar (mlhip_scalar_mul_subgroup).  A point outside G1 gives an undefined result for its own product; G1.Mul and
-// MulBatchG1 accept any point of the curve.
+// MulBatchG1 accept any point of the curve.  On BN254 every point of the curve is in G1 (the lattice split of DESIGN.md
+// section 20 runs): only a point off the curve breaks the promise.
 func (c *Curve) MulBatchSubgroupG1(a []driver.G1, b []driver.Zr) []driver.G1 {
 	n := len(a)
 	if len(b) != n {

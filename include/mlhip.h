@@ -382,16 +382,19 @@ MLHIP_API int mlhip_scalar_mul(int curve, int group, const void* points, size_t 
  * How it runs (msm_scalar_mul_endo.h).  G1 of the BLS12 curves: s = a + b x^2 with a, b < 2^128,
  * [s]P = [a]P + [b](beta Px, -Py), joint signed 4-bit windows -- 128 doublings and at most 66 additions instead of 256 and
  * 65.  G2 of every curve: the digits of s in base |x| (BLS12, four) or 6 x^2 (BN254, two) over Q, psi(Q), .., a 15-entry
- * table of their sums, 64 steps of one doubling (BN254: two) and at most one addition.  Two routes the flag never changes:
- * BN254 G1 -- E(Fp) has prime order there, the promise is vacuous and no short split exists without a lattice reduction:
- * the flagged call is accepted and runs the plain kernel -- and point_stride = 0 from MLHIP_FIXED_BASE_MIN scalars on, where
- * the fixed-base table has no doubling to save: accepted and ignored.  MLHIP_SCALAR_MUL_ENDO=0 sends every flagged call to
- * the plain kernels (second implementation, A/B).
+ * table of their sums, 64 steps of one doubling (BN254: two) and at most one addition.  G1 of BN254:
+ * s = k1 + k2 lambda with lambda = 36 x^4 - 1 and |k1|, |k2| < 2^127 from a lattice reduction, [s]P = [k1]P + [k2](beta Px, Py),
+ * the chain of the BLS12 curves over the two magnitudes and their signs.  E(Fp) has prime order there, so the promise holds
+ * for EVERY point of the curve (and infinity): any caller of BN254 G1 may set the flag.  A point that is not on the curve
+ * gives an undefined result for its own product and for no other, never a fault.  One route the flag never changes:
+ * point_stride = 0 from MLHIP_FIXED_BASE_MIN scalars on, where the fixed-base table has no doubling to save: accepted and
+ * ignored.  MLHIP_SCALAR_MUL_ENDO=0 sends every flagged call to the plain kernels (second implementation, A/B).
  * Measured: profiles/scalar_mul_endo_ab.txt, DESIGN.md section 17 -- 2^20 products of per-point bases on one MI355X, flagged call
  * against plain call in one process, same bytes, on two machines: G1 0.69 - 0.70 (BLS12-381) / 0.67 (BLS12-377) of the plain
  * call's time, G2 0.54 - 0.58 / 0.53 - 0.56 and 0.72 - 0.76 on BN254 (the operation counts predict 0.67, 0.5 and 0.65); within
  * 0.05 of that from 2^10 products on.  Every (curve, group) that has a split is ahead by far more than two identical plain
- * runs differ (at most 0.012 of their time at 2^20), so all of them take it. */
+ * runs differ (at most 0.012 of their time at 2^20), so all of them take it.  BN254 G1 (profiles/scalar_mul_glv_ab.txt, DESIGN.md
+ * section 20): 0.66 - 0.69 of the plain call's time from 2^10 to 2^20 products (counted: 0.66), spread at most 0.010. */
 #define MLHIP_GROUP_SUBGROUP(group) ((group) == 1 || (group) == 2 ? ((group) | 0x100) : -1)
 
 /* K independent MSMs in one call: out[k] = sum_{offsets[k] <= i < offsets[k+1]} [scalars[i]] points[i] (the batched form of
@@ -449,7 +452,10 @@ MLHIP_API int mlhip_msm_batch(int curve, int group, const void* points, const vo
  * beta and flip Y); G2 of the BLS12 curves 64 / P + 11 + <= 64 (four digits base |x| over Q .. psi^3 Q, a 15-entry table, 64
  * steps of one doubling); G2 of BN254 128 / P + 13 + <= 64 (two digits base 6 x^2, 64 steps of two doublings).  The G2 table
  * is 15 XYZZ per pair in scratch, so the split chunks are compiled for P = 1, 2, 4 there: at MLHIP_MSM_BATCH_CHUNK=8 a flagged
- * G2 call runs the plain chunk kernel.  BN254 G1 has no split: the flagged call is accepted and runs the plain kernel.
+ * G2 call runs the plain chunk kernel.  G1 of BN254 128 / P + 7 + <= 66: the G1 chunk of the BLS12 curves over the lattice
+ * split s = k1 + k2 lambda, |k1|, |k2| < 2^127, the signs of k1, k2 per pair.  E(Fp) has prime order
+ * there, so the promise holds for every point of the curve; a point that is not on the curve gives an undefined result for
+ * its own segment and for no other, never a fault.
  * MLHIP_MSM_BATCH_ENDO=0 sends every flagged call to the plain chunk kernels (second implementation, A/B).
  * Measured (profiles/msm_batch_endo_ab.txt): flagged call against plain call in one process on one
  * MI355X, same device buffers, same bytes in every cell; 2^10 .. 2^16 segments of 2 .. 64 pairs.  Flagged / plain time at the
@@ -459,7 +465,9 @@ MLHIP_API int mlhip_msm_batch(int curve, int group, const void* points, const vo
  * (0.63).  The measured ratios lie above the counted ones because the split removes doublings only, the cheapest operation
  * (9 field products against 14 of an addition), and G2 builds 11 or 13 more table entries per pair.  Every (curve, group) with
  * a split is ahead of the plain call in every cell at the default P by more than two identical plain runs differ (at most
- * 0.015), so all five take it; BN254 G1 reads 1.00.  Flagged calls keep the default P = 4: below ~2^17 pairs in all P = 1 is
+ * 0.015), so all five take it.  BN254 G1 (profiles/msm_batch_glv_ab.txt): 0.76 .. 0.88 at P = 4 (0.78),
+ * 0.67 .. 0.80 at P = 1 (0.61), ahead in all 12 cells at the default P by more than the spread (at most 0.013): it takes the
+ * split too.  Flagged calls keep the default P = 4: below ~2^17 pairs in all P = 1 is
  * faster, as for the plain call, but from 2^18 pairs on it falls behind the plain call at its default. */
 #define MLHIP_CURVE_SUBGROUP_POINTS(curve_id) ((curve_id) >= 0 && (curve_id) <= 2 ? ((curve_id) | 0x100) : -1)
 

@@ -555,6 +555,8 @@ class Curve {
   // outputs of earlier MSMs): the same results with half (G2 of a BLS12 curve: a quarter) of the chunks' doublings, from the
   // curve's endomorphism and a split of every scalar (mlhip_msm_batch_subgroup).  A point outside the subgroup gives an
   // undefined result for its own segment; MultiScalarMulBatch and MultiScalarMulG2Batch accept any point of the curve.
+  // On BN254 every point of the curve is in G1 (the lattice split of DESIGN.md section 20 runs): only a point that is not on
+  // the curve breaks the promise there.
   std::vector<G1> MultiScalarMulBatchSubgroup(const std::vector<std::vector<G1>>& a, const std::vector<std::vector<Zr>>& b) const {
     return msm_batch(MLHIP_GROUP_G1, g1_bytes, a, b, "MultiScalarMulBatchSubgroup", true);
   }
@@ -627,7 +629,8 @@ class Curve {
   // MulBatch for points the caller knows to be in G1 / G2 (decoded with the subgroup check, MSM outputs over checked bases,
   // generators and their multiples): the same results from the curve's endomorphism and a split of the scalar
   // (mlhip_scalar_mul_subgroup).  A point outside the subgroup gives an undefined result for its own product; G1.Mul, G2.Mul
-  // and MulBatch accept any point of the curve.
+  // and MulBatch accept any point of the curve.  On BN254 every point of the curve is in G1 (the lattice split of DESIGN.md
+  // section 20 runs): only a point that is not on the curve breaks the promise there.
   std::vector<G1> MulBatchSubgroup(const std::vector<G1>& points, const std::vector<Zr>& scalars) const {
     return mul_batch<G1>(MLHIP_GROUP_G1, g1_bytes, points, 1, scalars, true);
   }

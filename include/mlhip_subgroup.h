@@ -9,7 +9,8 @@
 #include "mlhip.h"
 
 /* out[i] = [scalars[i]] points[i * point_stride] for points in the prime-order subgroup (or at infinity); group =
- * MLHIP_GROUP_G1 / _G2, anything else is MLHIP_EINVAL */
+ * MLHIP_GROUP_G1 / _G2, anything else is MLHIP_EINVAL.  BN254 G1: the lattice split s = k1 + k2 lambda runs; the promise holds
+ * for every point of the curve, and a point off the curve gives an undefined result for its own product only, never a fault. */
 static inline int mlhip_scalar_mul_subgroup(int curve_id, int group, const void* points, size_t point_stride,
                                             const void* scalars, int scalars_mont, size_t n, void* out_affine) {
   return mlhip_scalar_mul(curve_id, MLHIP_GROUP_SUBGROUP(group), points, point_stride, scalars, scalars_mont, n, out_affine);
@@ -23,7 +24,8 @@ static inline int mlhip_scalar_mul_subgroup_device(int curve_id, int group, cons
 }
 
 /* out[k] = sum over segment k of [scalars[i]] points[i] (mlhip_msm_batch) for points in the prime-order subgroup (or at
- * infinity); curve_id = 0, 1 or 2, anything else is MLHIP_EINVAL */
+ * infinity); curve_id = 0, 1 or 2, anything else is MLHIP_EINVAL.  BN254 G1: the chunks run the lattice split; the promise holds
+ * for every point of the curve, and a point off the curve gives an undefined result for its own segment only, never a fault. */
 static inline int mlhip_msm_batch_subgroup(int curve_id, int group, const void* points, const void* scalars, int scalars_mont,
                                            const uint64_t* offsets, size_t k, void* out_affine) {
   return mlhip_msm_batch(MLHIP_CURVE_SUBGROUP_POINTS(curve_id), group, points, scalars, scalars_mont, offsets, k, out_affine);

@@ -12,7 +12,8 @@
 //                 one doubling and at most one addition per pair               64 / P + 11 + <= 64
 //     G2, BN254   two digits base 6 x^2, table [a]Q + [b]psi Q (a, b <= 3), 64 steps of two doublings
 //                                                                            128 / P + 13 + <= 64
-//     G1, BN254   no split (ScalarMulEndo<C, true>::AVAILABLE is false): the plain chunk kernel.
+//     G1, BN254   s = k1 + k2 lambda, |k1|, |k2| < 2^127 (g1_glv_split; G1Glv<C>, not ScalarMulEndo<C, true>): the G1 body
+//                 of the BLS12 curves with the signs of k1, k2 per pair            128 / P + 7 + <= 66
 // The G2 table is 15 XYZZ per pair where the plain chunk's is 8, all of it scratch: the split chunks are compiled for
 // P = 1, 2, 4 on G2 (P = 4 on a BLS12 curve: 11.5 KB per lane), and at MLHIP_MSM_BATCH_CHUNK=8 a promised G2 call runs the
 // plain chunk kernel.
@@ -23,6 +24,8 @@
 // (0.86); G2 of the BLS12 curves 0.51 - 0.62 at P = 1 (0.43), 0.64 - 0.86 at P = 4 (0.67); G2 of BN254 0.71 - 0.80 at P = 1 (0.63),
 // 0.79 - 0.97 at P = 4 (0.81).  Above the counts because only doublings go, the cheapest operation.  Ahead of the plain call
 // in every cell at the default P = 4, which flagged calls keep: all five (curve, group) with a split take it by default.
+// G1 of BN254 (profiles/msm_batch_glv_ab.txt): 0.67 - 0.80 at P = 1 (0.61), 0.76 - 0.88 at P = 4 (0.78),
+// 0.76 - 0.92 at P = 8 (0.86), ahead in every cell at P = 4 as well: the sixth takes it too.
 // Layout, sum passes, scratch buffer, event ordering and the bucket route of the long segments are those of msm_batch.h /
 // msm_batch_bucket.h, unchanged: a promised call differs in the chunk kernel alone.
 #pragma once
@@ -37,20 +40,24 @@ constexpr bool msm_batch_endo_p_compiled(int p) {
   return p == 1 || p == 2 || p == 4 || (G1 && p == 8);
 }
 
-// acc = sum_{j < count} [s_j] P_j for one chunk (count <= P) of points in G1 of a BLS12 curve; scalars, load as in
+// acc = sum_{j < count} [s_j] P_j for one chunk (count <= P) of points in G1; scalars, load as in
 // msm_batch_chunk.  Per pair the windows of a and b (five words each: both are below 2^128, so window 32 holds the carry
 // and nothing lies above) and the table {1 .. 8}P_j; then windows 32 .. 0, a's digit on the table entry and b's digit on the
-// same entry with X beta and Y flipped -- g1_endo_chain for P pairs at once.
+// same entry with X beta and Y flipped (BN254: flipped as the signs of k1, k2 say) -- g1_endo_chain for P pairs at once.
 template <class F, int P, class Ops, class Load>
 MLHIP_HD void msm_batch_chunk_endo_g1(XYZZ<F>& acc, const uint32_t* scalars, uint32_t count, bool mont, Load load) {
   typedef typename F::Curve C;
+  typedef G1Split<C> S;
   uint32_t wa[P][5], wb[P][5];
+  uint32_t negs = 0;  // BN254: bit 2 j + half = the sign of pair j's k1 / k2 (BLS12: constants, this word is never read)
   XYZZ<F> tab[P][8];
 #pragma unroll 1
   for (int j = 0; j < P; j++) {
     uint32_t s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a[8], b[8], t[9];
     if ((uint32_t)j < count) fr_canonical<C>(s, scalars + 8 * j, mont);
-    g1_endo_split<C>(a, b, s);  // s = 0 (a slot past the chunk's end): a = b = 0, every digit 0, the table is never read
+    bool neg_a, neg_b;
+    S::split(a, b, neg_a, neg_b, s);  // s = 0 (a slot past the chunk's end): a = b = 0, every digit 0, the table is never read
+    if (!S::FIXED_SIGNS) negs |= ((neg_a ? 1u : 0u) | (neg_b ? 2u : 0u)) << (2 * j);
     signed_windows4(t, a);
 #pragma unroll
     for (int k = 0; k < 5; k++) wa[j][k] = t[k];
@@ -68,7 +75,7 @@ MLHIP_HD void msm_batch_chunk_endo_g1(XYZZ<F>& acc, const uint32_t* scalars, uin
     }
   }
   typename F::T beta;
-  fp_from_const<C>(beta, C::ENDO_BETA);
+  S::beta(beta);
   xyzz_set_inf<F>(acc);
   bool started = false;
 #pragma unroll 1
@@ -82,14 +89,15 @@ MLHIP_HD void msm_batch_chunk_endo_g1(XYZZ<F>& acc, const uint32_t* scalars, uin
       }
     }
 #pragma unroll 1
-    for (int jh = 0; jh < 2 * P; jh++) {  // per pair a's digit on P_j, then b's digit on (beta x, -y)
+    for (int jh = 0; jh < 2 * P; jh++) {  // per pair a's digit on +-P_j, then b's digit on (beta x, +-y)
       const int j = jh >> 1, half = jh & 1;
       const int d = signed_window4_digit(half ? wb[j] : wa[j], w);
       if (d) {
         XYZZ<F> q = tab[j][(d < 0 ? -d : d) - 1];
         typename F::T ny;
         F::neg(ny, q.y);
-        F::select(q.y, (d < 0) != (half != 0), ny, q.y);
+        const bool neg_half = S::FIXED_SIGNS ? half != 0 : ((negs >> jh) & 1u) != 0;
+        F::select(q.y, (d < 0) != neg_half, ny, q.y);
         if (half) F::mul(q.x, q.x, beta);
         Ops::add(acc, q);
         started = true;
@@ -211,7 +219,7 @@ template <class C, class F>
 bool msm_batch_endo_launch_chunks(int P, const void* d_points, const void* d_scalars, int mont, const MsmBatchChunk* d_chunks,
                                   uint32_t n_chunks, void* d_partials, hipStream_t st) {
   constexpr bool kG1 = std::is_same<F, FpField<C>>::value;
-  if constexpr (!ScalarMulEndo<C, kG1>::AVAILABLE) {
+  if constexpr (!ScalarMulEndo<C, kG1>::AVAILABLE && !(kG1 && G1Glv<C>::AVAILABLE)) {
     return false;
   } else {
     if (!msm_batch_endo_p_compiled<kG1>(P) || !msm_batch_endo_enabled()) return false;

@@ -13,7 +13,10 @@
 //                 Straus table of the subset sums of g0 .. g3, 64 steps of one doubling and at most one addition.
 //     G2, BN254:  psi(Q) = [p]Q = [6 x^2]Q =: [L]Q.  s = d0 + d1 L, table [a]Q + [b]psi(Q) for a, b <= 3, 64 steps of two
 //                 doublings and at most one addition.
-//     G1, BN254:  E(Fp) has prime order -- nothing to promise -- and ENDO_BETA is not generated for it: the plain kernel.
+//     G1, BN254:  s = a + b x^2 does not exist; phi(x, y) = (beta x, y) = [lambda]P, lambda = 36 x^4 - 1, and a lattice
+//                 reduction gives s = k1 + k2 lambda with |k1|, |k2| < 2^127 (g1_glv_split): the
+//                 chain of the BLS12 curves over (|k1|, |k2|) and their signs.  E(Fp) has prime order, so the promise holds
+//                 for every point of the curve; GLV_BETA / GLV_LAMBDA are names of their own (G1Glv), ENDO_BETA stays unused.
 // A point outside the subgroup gives a wrong value for its own product and nothing else: every address depends on the
 // scalar alone, every operation is the complete XYZZ arithmetic of the plain kernels.
 #pragma once
@@ -53,12 +56,131 @@ MLHIP_HD void g1_endo_split(uint32_t (&a)[8], uint32_t (&b)[8], const uint32_t (
   endo_mac64(b, dig[4] | ((uint64_t)dig[5] << 32), dig[6] | ((uint64_t)dig[7] << 32), GtSplit<C>::LO);
 }
 
-// acc = [s]P for P in G1 (BLS12), s < r.  tab[0] = P on entry; tab[1 .. 7] are scratch.  O: the group operations of the
+// ---- G1 of BN254: the GLV lattice split ----------------------------------------------------------------------------------
+// does the promise change the chain of G1 of this curve although ScalarMulEndo<C, true> says no?  (A trait of its own:
+// ScalarMulEndo keeps meaning "s = a + b x^2 exists".)
+template <class C>
+struct G1Glv {
+  static constexpr bool AVAILABLE = C::IS_BN;
+};
+
+// out[0 .. NA + NB) = a[0 .. NA) * b[0 .. NB), 32-bit limbs (once per product: no need for anything faster)
+template <int NA, int NB>
+MLHIP_HD void glv_mul_words(uint32_t* out, const uint32_t* a, const uint32_t* b) {
+#pragma unroll
+  for (int k = 0; k < NA + NB; k++) out[k] = 0;
+#pragma unroll
+  for (int i = 0; i < NA; i++) {
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      c += (uint64_t)a[i] * b[j] + out[i + j];
+      out[i + j] = (uint32_t)c;
+      c >>= 32;
+    }
+    out[i + NB] = (uint32_t)c;
+  }
+}
+// c = floor((s g + 2^255) / 2^256), four words (below: c < 2^127)
+MLHIP_HD void glv_round_quotient(uint32_t (&c)[4], const uint32_t (&s)[8], const uint32_t (&g)[8]) {
+  uint32_t t[16];
+  glv_mul_words<8, 8>(t, s, g);
+  uint64_t cy = (uint64_t)t[7] + 0x80000000u;
+  cy >>= 32;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    cy += t[8 + k];
+    c[k] = (uint32_t)cy;
+    cy >>= 32;
+  }
+}
+// r -= x (eight words, two's complement mod 2^256)
+MLHIP_HD void glv_sub8(uint32_t (&r)[8], const uint32_t (&x)[8]) {
+  uint64_t br = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const uint64_t d = (uint64_t)r[k] - x[k] - br;
+    r[k] = (uint32_t)d;
+    br = (d >> 32) & 1;
+  }
+}
+// the sign of a two's complement value of eight words, which is replaced by its magnitude
+MLHIP_HD bool glv_abs8(uint32_t (&r)[8]) {
+  const bool neg = (r[7] >> 31) != 0;
+  const uint32_t m = neg ? 0xFFFFFFFFu : 0u;
+  uint64_t c = neg ? 1u : 0u;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    c += (uint64_t)(r[k] ^ m);
+    r[k] = (uint32_t)c;
+    c >>= 32;
+  }
+  return neg;
+}
+
+// s = k1 + k2 lambda (mod r) for canonical s < r: a = |k1|, b = |k2| as eight zero-extended words (what signed_windows4
+// reads), neg_a / neg_b their signs.  With the basis v1 = (A, -B), v2 = (B, A + B) of the lattice {(x, y): x + y lambda = 0
+// mod r} (A = GLV_A1, B = GLV_A2 = |GLV_B1|, A + B = GLV_B2; det = A (A + B) + B^2 = r):
+//     (s, 0) = b1 v1 + b2 v2 over the rationals with b1 = s (A + B) / r, b2 = s B / r;
+//     c1 = floor((s G1 + 2^255) / 2^256), c2 = floor((s G2 + 2^255) / 2^256), G1 = floor(2^256 (A + B) / r), G2 = floor(2^256 B / r);
+//     (k1, k2) = (s, 0) - c1 v1 - c2 v2 = (s - c1 A - c2 B, c1 B - c2 (A + B)),
+// and k1 + k2 lambda = s mod r because v1 and v2 lie in the lattice -- whatever c1, c2 are.
+// The bound.  G1 > 2^256 (A + B) / r - 1, so s G1 / 2^256 lies in (b1 - s / 2^256, b1], and s < r < 2^254 makes that
+// (b1 - 1/4, b1].  c1 = floor(that + 1/2) is then in (b1 - 3/4, b1 + 1/2]: e1 = b1 - c1 lies in [-1/2, 3/4); the same holds
+// for e2 = b2 - c2.  (k1, k2) = e1 v1 + e2 v2 = (e1 A + e2 B, -e1 B + e2 (A + B)), so
+//     |k1| < 3/4 (A + B),  |k2| < 3/4 (A + 2 B),   A + 2 B < 1.48 * 10^38 + 2 * 10^19 < 2^127 = 1.70 * 10^38:
+// |k1|, |k2| < 3/4 * 2^127 < 2^127 for EVERY s < r -- a, b < 2^128 with a bit to spare, so signed_windows4 leaves window 32
+// a carry of 0 and the 33 windows of g1_endo_chain hold them.  c1 <= b1 + 1/2 < A + B + 1 and c2 < B + 1 fit four words;
+// k1 and k2 are computed mod 2^256 in two's complement, exact because the true values are far inside (-2^255, 2^255).
+template <class C>
+MLHIP_HD void g1_glv_split(uint32_t (&a)[8], uint32_t (&b)[8], bool& neg_a, bool& neg_b, const uint32_t (&s)[8]) {
+  static_assert(!C::GLV_A1_NEG && C::GLV_B1_NEG && !C::GLV_A2_NEG && !C::GLV_B2_NEG, "written for v1 = (A, -B), v2 = (B, A + B)");
+  uint32_t c1[4], c2[4], t[8];
+  glv_round_quotient(c1, s, C::GLV_G1);
+  glv_round_quotient(c2, s, C::GLV_G2);
+#pragma unroll
+  for (int k = 0; k < 8; k++) a[k] = s[k];
+  glv_mul_words<4, 4>(t, c1, C::GLV_A1);
+  glv_sub8(a, t);
+  glv_mul_words<4, 4>(t, c2, C::GLV_A2);
+  glv_sub8(a, t);
+  glv_mul_words<4, 4>(b, c1, C::GLV_B1);
+  glv_mul_words<4, 4>(t, c2, C::GLV_B2);
+  glv_sub8(b, t);
+  neg_a = glv_abs8(a);
+  neg_b = glv_abs8(b);
+}
+
+// What g1_endo_chain and the chunks of msm_batch_endo.h run over: [s]P = +-[a]P +- [b]phi(P), phi(x, y) = (beta x, y).
+// BLS12: the signs are constants (+a on P, -b on phi(P): s = a + b x^2 and phi = [-x^2]) and the chain is compiled with
+// them -- the code it was before BN254 had a split.  BN254: the signs of k1, k2 come with every scalar.
+template <class C, bool BN = C::IS_BN>
+struct G1Split {
+  static constexpr bool FIXED_SIGNS = true;
+  MLHIP_HD static void beta(Fp<C>& r) { fp_from_const<C>(r, C::ENDO_BETA); }
+  MLHIP_HD static void split(uint32_t (&a)[8], uint32_t (&b)[8], bool& neg_a, bool& neg_b, const uint32_t (&s)[8]) {
+    g1_endo_split<C>(a, b, s);
+    neg_a = false;
+    neg_b = true;
+  }
+};
+template <class C>
+struct G1Split<C, true> {
+  static constexpr bool FIXED_SIGNS = false;
+  MLHIP_HD static void beta(Fp<C>& r) { fp_from_const<C>(r, C::GLV_BETA); }
+  MLHIP_HD static void split(uint32_t (&a)[8], uint32_t (&b)[8], bool& neg_a, bool& neg_b, const uint32_t (&s)[8]) {
+    g1_glv_split<C>(a, b, neg_a, neg_b, s);
+  }
+};
+
+// acc = [s]P for P in G1, s < r.  tab[0] = P on entry; tab[1 .. 7] are scratch.  O: the group operations of the
 // caller (dbl / add / madd), inline or out of line as its register budget wants.
 template <class C, class F, class O>
 MLHIP_HD void g1_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[8], const Affine<F>& P, const uint32_t (&s)[8]) {
+  typedef G1Split<C> S;
   uint32_t a[8], b[8], wa[9], wb[9];
-  g1_endo_split<C>(a, b, s);
+  bool neg_a, neg_b;
+  S::split(a, b, neg_a, neg_b, s);
   signed_windows4(wa, a);  // a, b < 2^128: the digits of windows 0 .. 31, a carry of 0 / 1 in window 32, nothing above
   signed_windows4(wb, b);
 #pragma unroll 1
@@ -67,7 +189,7 @@ MLHIP_HD void g1_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[8], const Affine<F>& P,
     O::madd(tab[k], P);
   }
   typename F::T beta;
-  fp_from_const<C>(beta, C::ENDO_BETA);
+  S::beta(beta);
   xyzz_set_inf<F>(acc);
   bool started = false;
 #pragma unroll 1
@@ -81,13 +203,14 @@ MLHIP_HD void g1_endo_chain(XYZZ<F>& acc, XYZZ<F> (&tab)[8], const Affine<F>& P,
       }
     }
 #pragma unroll 1
-    for (int half = 0; half < 2; half++) {  // a's digit on P, then b's digit on P' = (beta x, -y)
+    for (int half = 0; half < 2; half++) {  // a's digit on +-P, then b's digit on +-phi(P) = (beta x, +-y)
       const int d = signed_window4_digit(half ? wb : wa, w);
       if (d) {
         XYZZ<F> q = tab[(d < 0 ? -d : d) - 1];
         typename F::T ny;
         F::neg(ny, q.y);
-        F::select(q.y, (d < 0) != (half != 0), ny, q.y);
+        const bool neg_half = S::FIXED_SIGNS ? half != 0 : (half ? neg_b : neg_a);
+        F::select(q.y, (d < 0) != neg_half, ny, q.y);
         if (half) F::mul(q.x, q.x, beta);
         O::add(acc, q);
         started = true;
@@ -203,7 +326,7 @@ struct EndoOpsG2Lp {
   __device__ static void add(XYZZ<F>& acc, const XYZZ<F>& q) { xyzz_add_lp_ool<C>(acc, q); }
 };
 
-// out[i] = [s_i] P_i, P_i in G1 of a BLS12 curve: one lane per product
+// out[i] = [s_i] P_i, P_i in G1 (BLS12: the subgroup; BN254: the curve): one lane per product
 template <class C>
 __global__ void __launch_bounds__(64) k_scalar_mul_endo(const Affine<FpField<C>>* __restrict__ points, size_t point_stride,
                                                         const uint32_t* __restrict__ scalars, int mont, size_t n,
@@ -260,7 +383,7 @@ template <class C, class F>
 bool scalar_mul_endo_launch(const void* d_points, size_t point_stride, const void* d_scalars, int mont, size_t n, void* d_out,
                             hipStream_t st) {
   constexpr bool kG1 = std::is_same<F, FpField<C>>::value;
-  if constexpr (!ScalarMulEndo<C, kG1>::AVAILABLE) {
+  if constexpr (!ScalarMulEndo<C, kG1>::AVAILABLE && !(kG1 && G1Glv<C>::AVAILABLE)) {
     return false;
   } else {
     if (!scalar_mul_endo_enabled()) return false;

@@ -528,7 +528,8 @@ class Curve:
         """MultiScalarMulBatch for points the caller knows to be in G1 (decoded with the subgroup check, issuer keys,
         generators, outputs of earlier MSMs): the same results with half of the chunks' doublings, from the curve's
         endomorphism and a split of every scalar (mlhip_msm_batch_subgroup).  A point outside the subgroup gives an undefined
-        result for its own segment; MultiScalarMulBatch accepts any point of the curve."""
+        result for its own segment; MultiScalarMulBatch accepts any point of the curve.  On BN254 every point of the curve is
+        in G1 (the lattice split of DESIGN.md section 20 runs): only a point that is not on the curve breaks the promise."""
         return self.MultiScalarMulBatch(a_lists, b_lists, subgroup=True)
 
     def MultiScalarMulG2BatchSubgroup(self, a_lists: Sequence[Sequence[G2]], b_lists: Sequence[Sequence[Zr]]) -> List[G2]:
@@ -604,7 +605,8 @@ class Curve:
         """MulBatch for points the caller knows to be in G1 / G2 (decoded with the subgroup check, MSM outputs over checked
         bases, generators and their multiples): the same results from the curve's endomorphism and a split of the scalar
         (mlhip_scalar_mul_subgroup).  A point outside the subgroup gives an undefined result for its own product; G1.Mul,
-        G2.Mul and MulBatch accept any point of the curve."""
+        G2.Mul and MulBatch accept any point of the curve.  On BN254 every point of the curve is in G1 (the lattice split of
+        DESIGN.md section 20 runs): only a point that is not on the curve breaks the promise there."""
         if len(points) != len(scalars):
             raise ValueError("MulBatchSubgroup: length mismatch")
         n = len(points)

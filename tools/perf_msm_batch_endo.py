@@ -14,7 +14,8 @@ device buffers, and the plain call against itself for the spread.
 Every cell runs under a time limit: a cell that passes it ends the run.
 
 Usage: perf_msm_batch_endo.py --ab [--out FILE] [--rounds N] [--warmup N] [--step-limit SECONDS] [--curves A,B] [--groups 1,2]
-                                   [--chunks 1,2,4,8] [--max-k LOG2]"""
+                                   [--chunks 1,2,4,8] [--max-k LOG2]
+       perf_msm_batch_endo.py --ab --curves BN254 --groups 1 --out profiles/msm_batch_glv_ab.txt   (the lattice split of BN254 G1)"""
 import argparse
 import math
 import os
@@ -36,7 +37,7 @@ K_GRID = (1 << 10, 1 << 14, 1 << 16)
 DEFAULT_P = {1: 4, 2: 4}  # MSM_BATCH_P_DEFAULT_G1 / _G2
 # operations per pair, counted from the code: (doublings per chunk, table operations per pair, additions per pair at most)
 PLAIN = (256, 7, 64)
-SPLIT = {("BLS12", 1): (128, 7, 66), ("BLS12", 2): (64, 11, 64), ("BN", 2): (128, 13, 64)}
+SPLIT = {("BLS12", 1): (128, 7, 66), ("BLS12", 2): (64, 11, 64), ("BN", 1): (128, 7, 66), ("BN", 2): (128, 13, 64)}
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--ab", action="store_true", required=True)
