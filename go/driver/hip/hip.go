@@ -32,6 +32,7 @@ package hip
 #include "mlhip_products.h"
 #include "mlhip_subgroup.h"
 #include "mlhip_bases_set.h"
+#include "mlhip_sum_batch.h"
 */
 import "C"
 
@@ -447,6 +448,68 @@ func (c *Curve) SumG2(a []driver.G2) driver.G2 {
 	check(func() C.int {
 		return C.mlhip_g2_sum(C.MLHIP_CURVE_BLS12_381, unsafe.Pointer(&points[0]), C.size_t(n), unsafe.Pointer(&out.G2Affine))
 	})
+	return out
+}
+
+// SumG1Batch returns SumG1(a[i]) for every i -- K committees' keys, K aggregate signatures, K folded proofs -- with one
+// device call (mlhip_sum_batch: strided slices of every list per lane, one mixed addition per point, DESIGN.md section 21).
+// An empty list gives the identity.  There is no host fallback: without a device the call panics.
+func (c *Curve) SumG1Batch(a [][]driver.G1) []driver.G1 {
+	k := len(a)
+	out := make([]driver.G1, k)
+	if k == 0 {
+		return out
+	}
+	offsets := make([]uint64, k+1)
+	var points []bls12381.G1Affine
+	for i := range a {
+		for j := range a[i] {
+			points = append(points, a[i][j].(*gurvy381.G1).G1Affine)
+		}
+		offsets[i+1] = offsets[i] + uint64(len(a[i]))
+	}
+	var pp unsafe.Pointer
+	if len(points) > 0 {
+		pp = unsafe.Pointer(&points[0])
+	}
+	res := make([]bls12381.G1Affine, k)
+	check(func() C.int {
+		return C.mlhip_sum_batch(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G1, pp, (*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+			C.size_t(k), unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		out[i] = &gurvy381.G1{G1Affine: res[i]}
+	}
+	return out
+}
+
+// SumG2Batch is SumG1Batch in G2.
+func (c *Curve) SumG2Batch(a [][]driver.G2) []driver.G2 {
+	k := len(a)
+	out := make([]driver.G2, k)
+	if k == 0 {
+		return out
+	}
+	offsets := make([]uint64, k+1)
+	var points []bls12381.G2Affine
+	for i := range a {
+		for j := range a[i] {
+			points = append(points, a[i][j].(*gurvy381.G2).G2Affine)
+		}
+		offsets[i+1] = offsets[i] + uint64(len(a[i]))
+	}
+	var pp unsafe.Pointer
+	if len(points) > 0 {
+		pp = unsafe.Pointer(&points[0])
+	}
+	res := make([]bls12381.G2Affine, k)
+	check(func() C.int {
+		return C.mlhip_sum_batch(C.MLHIP_CURVE_BLS12_381, C.MLHIP_GROUP_G2, pp, (*C.uint64_t)(unsafe.Pointer(&offsets[0])),
+			C.size_t(k), unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		out[i] = &gurvy381.G2{G2Affine: res[i]}
+	}
 	return out
 }
 
@@ -1023,6 +1086,55 @@ func (b *Bases) MultiScalarMulBatch(scalars [][]driver.Zr, index [][]uint32) []d
 	check(func() C.int {
 		return C.mlhip_bases_msm_batch(b.h, scp, 1, idxp, (*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k),
 			unsafe.Pointer(&res[0]))
+	})
+	for i := range res {
+		out[i] = &gurvy381.G1{G1Affine: res[i]}
+	}
+	return out
+}
+
+// SumBatch returns, for every i, sum_j bases[index[i][j]] in one device call (mlhip_bases_sum_batch); with index nil,
+// the sum of the first lengths[i] bases.  Every index is below the number of bases and every length at most it; the handle's
+// batch tables are neither built nor read.
+func (b *Bases) SumBatch(index [][]uint32, lengths []int) []driver.G1 {
+	k := len(index)
+	if index == nil {
+		k = len(lengths)
+	}
+	out := make([]driver.G1, k)
+	if k == 0 {
+		return out
+	}
+	offsets := make([]uint64, k+1)
+	var idx []uint32
+	for i := 0; i < k; i++ {
+		m := 0
+		if index != nil {
+			for _, x := range index[i] {
+				if int(x) >= b.n {
+					panic("hip: SumBatch: base index out of range")
+				}
+			}
+			idx = append(idx, index[i]...)
+			m = len(index[i])
+		} else {
+			m = lengths[i]
+			if m < 0 || m > b.n {
+				panic("hip: SumBatch: more points than resident bases")
+			}
+		}
+		offsets[i+1] = offsets[i] + uint64(m)
+	}
+	var idxp *C.uint32_t
+	if index != nil {
+		if len(idx) == 0 {
+			idx = []uint32{0}
+		}
+		idxp = (*C.uint32_t)(unsafe.Pointer(&idx[0]))
+	}
+	res := make([]bls12381.G1Affine, k)
+	check(func() C.int {
+		return C.mlhip_bases_sum_batch(b.h, idxp, (*C.uint64_t)(unsafe.Pointer(&offsets[0])), C.size_t(k), unsafe.Pointer(&res[0]))
 	})
 	for i := range res {
 		out[i] = &gurvy381.G1{G1Affine: res[i]}

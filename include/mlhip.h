@@ -471,6 +471,52 @@ MLHIP_API int mlhip_msm_batch(int curve, int group, const void* points, const vo
  * faster, as for the plain call, but from 2^18 pairs on it falls behind the plain call at its default. */
 #define MLHIP_CURVE_SUBGROUP_POINTS(curve_id) ((curve_id) >= 0 && (curve_id) <= 2 ? ((curve_id) | 0x100) : -1)
 
+/* ---- K independent point sums in one call: the batch calls with every scalar 1 ------------------------------------------------
+ * The batched twin of mlhip_g1_sum / mlhip_g2_sum: K committees' public keys, K aggregate signatures, K folded proofs, the
+ * pairwise A[k] + B[k] between two device stages.  out[k] = the sum of the points of segment k; over a handle the points are
+ * B[idx(i)], idx as in mlhip_bases_msm_batch.
+ *
+ * How it is said.  The symbol table does not grow: the flag MLHIP_SCALARS_UNIT below travels in `scalars_mont` of exactly four
+ * entry points -- mlhip_msm_batch, mlhip_msm_batch_device, mlhip_bases_msm_batch, mlhip_bases_msm_batch_device -- and nowhere
+ * else (every other entry point reads scalars_mont as before).  With the flag, scalars_mont must equal it exactly and
+ * `scalars` must be NULL ("unit scalars take no scalar array"); both are MLHIP_EINVAL otherwise.  Every other argument rule
+ * is the plain call's (offsets, K = 0 returns 0, empty segment = all-zero point, unknown curve / group, null points or output
+ * in a non-empty batch, index >= the handle's n, a segment longer than n without base_index, a set or a sharded handle), all
+ * checked before a device is asked for.  MLHIP_CURVE_SUBGROUP_POINTS(curve) beside the flag is accepted and changes nothing:
+ * there is no scalar to split.  No CPU fallback: MLHIP_ENODEVICE without a device, as for mlhip_msm_batch.
+ * include/mlhip_sum_batch.h wraps this in four inline functions: mlhip_sum_batch(curve_id, group, points, offsets, k,
+ * out_affine), mlhip_sum_batch_device(.., d_out_affine, stream), mlhip_bases_sum_batch(bases, base_index, offsets, k,
+ * out_affine) and mlhip_bases_sum_batch_device(bases, base_index, offsets, k, stream, d_out_affine).
+ *
+ * Result.  The canonical affine form of each segment's sum: the bytes of the plain call with an explicit array of
+ * plain-integer ones and of mlhip_g1_sum / mlhip_g2_sum per segment, for any points of the curve in any order and multiplicity
+ * (inside or outside the subgroup, (0,0) = infinity, one point m times, P beside -P).  A point off the curve gives an
+ * undefined result for its own segment only, never a fault: no address depends on point data.
+ *
+ * How it runs (msm_sum_batch.h).  A segment of m points is cut into c = ceil(m / S) slices, slice j
+ * reading the points j, j + c, j + 2 c, .. of the segment; one lane (G1) or lane pair (G2) per slice adds its points with the
+ * complete mixed addition of the plain sums (1 group operation per point, no table, no doubling), and the slice sums go
+ * through mlhip_msm_batch's sum passes: 1 + ~1.4 / S operations per point where the plain call with ones spends ~9 (the
+ * {1..8} P table and one addition), uploads 32 bytes of scalar per point and sends long segments to buckets.  A flagged call
+ * never takes the Straus chunks or the bucket route and needs no scalar memory; on a handle it neither builds nor reads
+ * batch tables (mlhip_bases_batch_tabled is unchanged by it).
+ * S is a power of two per call: the largest of 4, 8, 16, 32 that still gives 2^13 slices, counting total / S of them, else 4
+ * (S = 4 below 2^16 points per call, 32 from 2^18 on); MLHIP_SUM_BATCH_SLICE=s (a power of two, 1 .. 4096) forces it.  The rule
+ * is the one the grid of profiles/sum_batch_ab.txt supports (tools/perf_sum_batch.py runs every cell at S = 4, 8, 16, 32 as
+ * well): the first candidate, "as many slices as the device keeps lanes" (2^16; G2 2^15 lane pairs), stayed at S = 4 up to
+ * 2^18 points, where S = 8 or 16 takes 19 - 27 % less time -- a small call waits for its chain of dependent additions, about
+ * 10 us each, and 2^13 slices already hide it.
+ * Measured (one MI355X, profiles/sum_batch_ab.txt): mlhip_sum_batch_device against
+ * mlhip_msm_batch_device with a resident array of ones in one process, same device buffers, same bytes in every cell;
+ * K = 2^10, 2^14, 2^16 segments of 2 .. 4096 points, at most 2^22 points per call.  Flagged / plain time (counted: 0.12 - 0.15):
+ * about 0.3 - 0.55 up to 2^18 points per call in segments of 2 .. 64 points, where the flagged call is a few launches of
+ * 0.14 - 0.8 ms in all; about 0.2 at 2^20 points; 0.01 - 0.07 for 2^22 points per call and for segments of 512 and 4096 points, where the plain
+ * call builds 2^22 tables or sorts its ones into buckets (2^10 segments of 4096 BLS12-381 G1 points: about 2.2 ms against
+ * 260 ms).  BLS12-381 G1 and G2 and BN254 G1 alike; over a 4096-base handle with an index list 0.4 - 0.55.  Ahead of the plain
+ * call in every cell by more than two identical plain runs differ (at most 0.10).  2^10 lists of 64 G1 points from host
+ * memory: one call 0.6 - 0.75 ms against 26 ms for 2^10 mlhip_g1_sum calls. */
+#define MLHIP_SCALARS_UNIT 0x400 /* `scalars_mont` of the four batch entry points: every scalar is 1, `scalars` must be NULL */
+
 /* ---- resident bases (upload-once point table, only the scalars travel per call) ----------
  * For callers that cannot hold device pointers themselves (the Go shim): the points are uploaded once, every
  * mlhip_bases_msm() uploads n x 32 bytes of scalars and returns sum_i [s_i] P_i over the first n bases (n <= the
@@ -716,6 +762,8 @@ MLHIP_API int mlhip_fp_mul_device(int curve, const void* d_a, const void* d_b, s
  *                                      of the batch)
  *     MLHIP_SUM_DEVICE_MIN=n           mlhip_g1_sum / mlhip_g2_sum: smallest list summed on the device (0 = never, 1 = always;
  *                                      default 2^14 G1 / 2^12 G2)
+ *     MLHIP_SUM_BATCH_SLICE=s          the batch calls with MLHIP_SCALARS_UNIT: points per slice, a power of two 1 .. 4096
+ *                                      (default: the largest of 4 .. 32 that still fills the device's lanes, else 4)
  *     MLHIP_BASES_BATCH_WINDOW=w, MLHIP_BASES_BATCH_CHUNK=P   mlhip_bases_msm_batch*: table width 4 .. 12 (default 12), pairs
  *                                      per chunk on the table path, 1, 2, 4, 8 or 16 (default: the largest that fills 2^16 lanes)
  *     MLHIP_BASES_BATCH_MAX_MB=m       ... tables per handle at most m MB (default 1024; 0 = never: the table-free path)

@@ -18,7 +18,8 @@
 //   G2::Mul / Add, Gt::Mul / Exp / IsUnity, Zr::Plus / Minus / Mul / ...             driver/math.go:191-360
 //   additive: MultiScalarMulG2, MultiScalarMulG1G2, PairingBatch, PairingProduct, MillerLoopProducts, PairingProducts, MulBatch, MulBatchSubgroup, BaseMulBatch, ExpBatch, ExpBatchGt, NewGtFromBytesBatch, GtBytesBatch,
 //   IsInSubGroupBatch, InverseBatch,
-//             MultiScalarMulBatch, MultiScalarMulG2Batch, MultiScalarMulBatchSubgroup, MultiScalarMulG2BatchSubgroup, Mul2Batch, Bases::MultiScalarMulBatch, BasesG2, BasesSet::MultiScalarMul, SumG1, SumG2
+//             MultiScalarMulBatch, MultiScalarMulG2Batch, MultiScalarMulBatchSubgroup, MultiScalarMulG2BatchSubgroup, Mul2Batch, Bases::MultiScalarMulBatch, BasesG2, BasesSet::MultiScalarMul, SumG1, SumG2,
+//             SumG1Batch, SumG2Batch, Bases::SumBatch
 #pragma once
 #include <algorithm>
 #include <array>
@@ -34,6 +35,7 @@
 #include "mlhip_products.h"
 #include "mlhip_subgroup.h"
 #include "mlhip_bases_set.h"
+#include "mlhip_sum_batch.h"
 
 namespace mlhip_driver {
 
@@ -543,6 +545,10 @@ class Curve {
     check(mlhip_g2_sum(id, pts.data(), points.size(), out.raw.data()));
     return out;
   }
+  // out[i] = SumG1(lists[i]) / SumG2(lists[i]) for many lists in one device call (mlhip_sum_batch); an empty list gives the
+  // identity
+  std::vector<G1> SumG1Batch(const std::vector<std::vector<G1>>& lists) const { return sum_batch(MLHIP_GROUP_G1, g1_bytes, lists); }
+  std::vector<G2> SumG2Batch(const std::vector<std::vector<G2>>& lists) const { return sum_batch(MLHIP_GROUP_G2, g2_bytes, lists); }
   // out[i] = MultiScalarMul(a[i], b[i]) for many small MSMs in one device call (mlhip_msm_batch); every segment keeps
   // MultiScalarMul's length rules: fewer scalars than points throws, more gives the identity
   std::vector<G1> MultiScalarMulBatch(const std::vector<std::vector<G1>>& a, const std::vector<std::vector<Zr>>& b) const {
@@ -781,6 +787,27 @@ class Curve {
     return out;
   }
   template <class P>
+  std::vector<P> sum_batch(int group, size_t size, const std::vector<std::vector<P>>& lists) const {
+    std::vector<P> out;
+    const size_t k = lists.size();
+    if (k == 0) return out;
+    std::vector<uint64_t> offsets(k + 1, 0);
+    Bytes pts;
+    for (size_t i = 0; i < k; i++) {
+      offsets[i + 1] = offsets[i] + lists[i].size();
+      for (auto& x : lists[i]) pts.insert(pts.end(), x.raw.begin(), x.raw.end());
+    }
+    Bytes o(size * k);
+    check(mlhip_sum_batch(id, group, pts.data(), offsets.data(), k, o.data()));
+    for (size_t i = 0; i < k; i++) {
+      P g;
+      g.curve = this;
+      g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);
+      out.push_back(g);
+    }
+    return out;
+  }
+  template <class P>
   void pack(const std::vector<P>& a, const std::vector<Zr>& b, Bytes& pts, Bytes& sc) const {
     for (auto& x : a) pts.insert(pts.end(), x.raw.begin(), x.raw.end());
     sc.resize(32 * b.size());
@@ -856,6 +883,30 @@ class Bases {
     }
     return out;
   }
+  // out[i] = sum_j B[index[i][j]] for many sums over the resident bases in one device call (mlhip_bases_sum_batch); every
+  // index below n (out_of_range).  No batch tables are built or read.
+  std::vector<G1> SumBatch(const std::vector<std::vector<uint32_t>>& index) const {
+    std::vector<uint64_t> offsets(index.size() + 1, 0);
+    std::vector<uint32_t> idx;
+    for (size_t i = 0; i < index.size(); i++) {
+      for (uint32_t x : index[i]) {
+        if (x >= n_) throw std::out_of_range("SumBatch: base index out of range");
+        idx.push_back(x);
+      }
+      offsets[i + 1] = offsets[i] + index[i].size();
+    }
+    if (idx.empty()) idx.push_back(0);
+    return sum_batch(idx.data(), offsets);
+  }
+  // out[i] = B[0] + .. + B[lengths[i] - 1]; every length at most n (out_of_range)
+  std::vector<G1> SumBatch(const std::vector<size_t>& lengths) const {
+    std::vector<uint64_t> offsets(lengths.size() + 1, 0);
+    for (size_t i = 0; i < lengths.size(); i++) {
+      if (lengths[i] > n_) throw std::out_of_range("SumBatch: more points than resident bases");
+      offsets[i + 1] = offsets[i] + lengths[i];
+    }
+    return sum_batch(nullptr, offsets);
+  }
   // the number of leading bases that have MultiScalarMulBatch tables (mlhip_bases_batch_tabled)
   size_t BatchTabled() const {
     size_t n = 0;
@@ -873,6 +924,20 @@ class Bases {
   }
 
  private:
+  std::vector<G1> sum_batch(const uint32_t* idx, const std::vector<uint64_t>& offsets) const {
+    std::vector<G1> out;
+    const size_t k = offsets.size() - 1;
+    if (k == 0) return out;
+    const size_t size = curve_->g1_bytes;
+    Bytes o(size * k);
+    check(mlhip_bases_sum_batch(h_, idx, offsets.data(), k, o.data()));
+    for (size_t i = 0; i < k; i++) {
+      G1 g = curve_->NewG1();
+      g.raw.assign(o.begin() + i * size, o.begin() + (i + 1) * size);
+      out.push_back(g);
+    }
+    return out;
+  }
   const Curve* curve_;
   size_t n_;
   mlhip_bases* h_ = nullptr;

@@ -365,6 +365,55 @@ def msm_batch_subgroup_device(lib, curve: int, group: int, d_points, d_scalars, 
     return lib.mlhip_msm_batch_device(CURVE_SUBGROUP_POINTS(curve), group, d_points, d_scalars, scalars_mont, offsets, k, d_out, stream)
 
 
+SCALARS_UNIT = 0x400
+"""MLHIP_SCALARS_UNIT of include/mlhip.h: the scalars_mont argument of the four batch entry points that says every scalar is 1"""
+
+
+def mlhip_sum_batch(lib, curve: int, group: int, points, offsets, k: int, out) -> int:
+    """include/mlhip_sum_batch.h: K point sums in one call (the return code, as the C function)"""
+    return lib.mlhip_msm_batch(curve, group, points, None, SCALARS_UNIT, offsets, k, out)
+
+
+def mlhip_sum_batch_device(lib, curve: int, group: int, d_points, offsets, k: int, d_out, stream) -> int:
+    """include/mlhip_sum_batch.h: the same on device pointers, asynchronous and in order on `stream`"""
+    return lib.mlhip_msm_batch_device(curve, group, d_points, None, SCALARS_UNIT, offsets, k, d_out, stream)
+
+
+def mlhip_bases_sum_batch(lib, handle, base_index, offsets, k: int, out) -> int:
+    """include/mlhip_sum_batch.h: K sums over the resident bases of a handle (the return code, as the C function)"""
+    return lib.mlhip_bases_msm_batch(handle, None, SCALARS_UNIT, base_index, offsets, k, out)
+
+
+def mlhip_bases_sum_batch_device(lib, handle, base_index, offsets, k: int, stream, d_out) -> int:
+    """include/mlhip_sum_batch.h: the same with device outputs, in order on `stream`"""
+    return lib.mlhip_bases_msm_batch_device(handle, None, SCALARS_UNIT, base_index, offsets, k, stream, d_out)
+
+
+def sum_batch(curve: int, group: int, points: bytes, lengths):
+    """mlhip_sum_batch: one affine point (bytes) per segment; segment i is lengths[i] consecutive points"""
+    _, g1, g2, _ = sizes(curve)
+    ptsz = g1 if group == GROUP_G1 else g2
+    k = len(lengths)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k * ptsz)
+    check(mlhip_sum_batch(load(), curve, group, points, batch_offsets(lengths), k, out))
+    raw = out.raw
+    return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
+
+
+def bases_sum_batch(lib, handle, ptsz: int, lengths, index_lists=None):
+    """mlhip_bases_sum_batch on the handle `handle` of `lib` (points of ptsz bytes): one affine point (bytes) per segment;
+    segment i sums lengths[i] bases, those index_lists[i] names or (without index lists) the first lengths[i]"""
+    k = len(lengths)
+    if k == 0:
+        return []
+    out = ctypes.create_string_buffer(k * ptsz)
+    check(mlhip_bases_sum_batch(lib, handle, batch_index(index_lists), batch_offsets(lengths), k, out))
+    raw = out.raw
+    return [raw[i * ptsz : (i + 1) * ptsz] for i in range(k)]
+
+
 WINDOW_DEVICE_RESULT = 1 << 20
 """MLHIP_WINDOW_DEVICE_RESULT of include/mlhip.h: OR-ed onto a plain window_c or onto window_bits(c, bits)"""
 

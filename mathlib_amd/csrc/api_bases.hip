@@ -523,16 +523,21 @@ int mlhip_bases_msm_batch_device(mlhip_bases* b, const void* d_scalars, int scal
                                  const uint64_t* offsets, size_t k, void* stream, void* d_out_affine) {
   if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
   if (int rc_set = reject_set(b, "mlhip_bases_msm_batch")) return rc_set;
-  int rc = check_batch_offsets(offsets, k);
+  bool unit = false;
+  int rc = take_unit_scalars(scalars_mont, d_scalars, &unit);
+  if (rc) return rc;
+  rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
   if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
   size_t need = 0;
   rc = check_bases_batch_index(b, base_index, offsets, k, &need);
   if (rc) return rc;
-  if (!d_out_affine || (offsets[k] && !d_scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!d_out_affine || (offsets[k] && !d_scalars && !unit)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   std::lock_guard<std::mutex> lk(b->mu);
+  // plain sums (msm_sum_batch.h) read the handle's points only: the batch tables are neither built nor read
+  if (unit) return curve_ops(b->curve)->sum_batch(b->group, b->d_pts, true, base_index, offsets, k, d_out_affine, (hipStream_t)stream);
   return curve_ops(b->curve)->bases_batch(b->group, &b->batch, b->d_pts, b->n, d_scalars, scalars_mont, base_index, offsets, k, need,
                                           d_out_affine, (hipStream_t)stream);
 }
@@ -541,7 +546,10 @@ int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont,
                           size_t k, void* out_affine) {
   if (!b) return mlhip_rt::fail(MLHIP_EINVAL, "null handle");
   if (int rc_set = reject_set(b, "mlhip_bases_msm_batch")) return rc_set;
-  int rc = check_batch_offsets(offsets, k);
+  bool unit = false;
+  int rc = take_unit_scalars(scalars_mont, scalars, &unit);
+  if (rc) return rc;
+  rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
   if (!b->shards.empty()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle is spread over several devices");
@@ -549,14 +557,14 @@ int mlhip_bases_msm_batch(mlhip_bases* b, const void* scalars, int scalars_mont,
   rc = check_bases_batch_index(b, base_index, offsets, k, &need);
   if (rc) return rc;
   const size_t n = offsets[k];
-  if (!out_affine || (n && !scalars)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!out_affine || (n && !scalars && !unit)) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   // the call's scratch comes from the process's device (HostCall); a handle made there before a later mlhip_init moved it
   // elsewhere has to be driven through the device form
   if (b->device != call_device()) return mlhip_rt::fail(MLHIP_EINVAL, "mlhip_bases_msm_batch: the handle lives on another device");
   if (hipSetDevice(b->device) != hipSuccess) return mlhip_rt::fail(MLHIP_EHIP, "hipSetDevice failed");
   HostCall hc;
-  hc.reserve(n * 32 + k * b->ptsz);
-  void* ds = hc.up(scalars, n * 32);
+  hc.reserve((unit ? 0 : n * 32) + k * b->ptsz);
+  void* ds = unit ? nullptr : hc.up(scalars, n * 32);
   void* dout = hc.dev(k * b->ptsz);
   if (hc.rc) return hc.rc;
   rc = mlhip_bases_msm_batch_device(b, ds, scalars_mont, base_index, offsets, k, hc.l.st, dout);

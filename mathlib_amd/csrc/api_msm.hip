@@ -483,6 +483,16 @@ int check_batch_offsets(const uint64_t* offsets, size_t k) {
   return 0;
 }
 
+// MLHIP_SCALARS_UNIT of include/mlhip.h taken apart (mlhip_msm_batch*, mlhip_bases_msm_batch* only): every scalar is 1, so
+// there is no scalar array and no other bit of scalars_mont.  Without the flag nothing is checked: scalars_mont as it was.
+int take_unit_scalars(int scalars_mont, const void* scalars, bool* unit) {
+  *unit = (scalars_mont & MLHIP_SCALARS_UNIT) != 0;
+  if (!*unit) return 0;
+  if (scalars_mont != MLHIP_SCALARS_UNIT) return mlhip_rt::fail(MLHIP_EINVAL, "MLHIP_SCALARS_UNIT takes no other bit of scalars_mont");
+  if (scalars) return mlhip_rt::fail(MLHIP_EINVAL, "unit scalars take no scalar array");
+  return 0;
+}
+
 
 void release_plan_pool() {
   std::vector<PoolEntry*> idle;
@@ -842,15 +852,20 @@ int mlhip_scalar_mul(int curve, int group, const void* points, size_t point_stri
 int mlhip_msm_batch_device(int curve, int group, const void* d_points, const void* d_scalars, int scalars_mont,
                            const uint64_t* offsets, size_t k, void* d_out_affine, void* stream) {
   const bool subgroup = take_subgroup_points_promise(curve);
+  bool unit = false;
+  int rc = take_unit_scalars(scalars_mont, d_scalars, &unit);
+  if (rc) return rc;
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   if (!ops->point_size(group)) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
-  int rc = check_batch_offsets(offsets, k);
+  rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
-  if (!d_out_affine || (offsets[k] && (!d_points || !d_scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!d_out_affine || (offsets[k] && (!d_points || (!d_scalars && !unit)))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   rc = ensure_device();
   if (rc) return rc;
+  // plain sums (msm_sum_batch.h): no scalar to split, so the subgroup promise changes nothing
+  if (unit) return ops->sum_batch(group, d_points, false, nullptr, offsets, k, d_out_affine, (hipStream_t)stream);
   return ops->msm_batch(group, d_points, d_scalars, scalars_mont, offsets, k, d_out_affine, (hipStream_t)stream, subgroup);
 }
 
@@ -858,21 +873,24 @@ int mlhip_msm_batch(int curve, int group, const void* points, const void* scalar
                     size_t k, void* out_affine) {
   const int curve_arg = curve;  // (with the promise, as mlhip_msm_batch_device takes it)
   take_subgroup_points_promise(curve);
+  bool unit = false;
+  int rc = take_unit_scalars(scalars_mont, scalars, &unit);
+  if (rc) return rc;
   const CurveOps* ops = curve_ops(curve);
   if (!ops) return mlhip_rt::fail(MLHIP_EINVAL, "unknown curve id");
   const size_t ptsz = ops->point_size(group);
   if (!ptsz) return mlhip_rt::fail(MLHIP_EINVAL, "group must be 1 or 2");
-  int rc = check_batch_offsets(offsets, k);
+  rc = check_batch_offsets(offsets, k);
   if (rc) return rc;
   if (k == 0) return 0;
   const size_t n = offsets[k];
-  if (!out_affine || (n && (!points || !scalars))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
+  if (!out_affine || (n && (!points || (!scalars && !unit)))) return mlhip_rt::fail(MLHIP_EINVAL, "null pointer");
   rc = ensure_device();
   if (rc) return rc;
   HostCall hc;
-  hc.reserve(n * ptsz + n * 32 + k * ptsz);
+  hc.reserve(n * ptsz + (unit ? 0 : n * 32) + k * ptsz);
   void* dp = hc.up(points, n * ptsz);
-  void* ds = hc.up(scalars, n * 32);
+  void* ds = unit ? nullptr : hc.up(scalars, n * 32);
   void* dout = hc.dev(k * ptsz);
   if (hc.rc) return hc.rc;
   rc = mlhip_msm_batch_device(curve_arg, group, dp, ds, scalars_mont, offsets, k, dout, hc.l.st);

@@ -242,6 +242,11 @@ struct mlhip_g2_prepared_tables {
      const uint32_t* base_index, const uint64_t* offsets, size_t k, size_t need, void* d_out, hipStream_t st))            \
   /* d_out = the affine sum of the n >= 1 affine points at d_points (point_sum.h: mlhip_g1_sum / mlhip_g2_sum) */        \
   X(C, int, point_sum, (int group, const void* d_points, size_t n, void* d_out, hipStream_t st))                          \
+  /* K plain sums (msm_sum_batch.h: the batch calls with MLHIP_SCALARS_UNIT): position i reads d_points[i], or, bases set,   \
+     the handle's point base_index[i] / (base_index null) its position in the segment */                                 \
+  X(C, int, sum_batch,                                                                                                    \
+    (int group, const void* d_points, bool bases, const uint32_t* base_index, const uint64_t* offsets, size_t k,          \
+     void* d_out, hipStream_t st))                                                                                        \
   /* what = -1: build t's tables from t->d_q ; 0 / 2: Miller loops / fused pairings of n products against them */         \
   X(C, int, g2_prepared,                                                                                                  \
     (mlhip_g2_prepared_tables * t, int what, const void* d_g1, const uint32_t* q_index, size_t ppp, size_t n,             \

@@ -68,5 +68,8 @@ int plan_train(mlhip_msm_plan* const* plans, void* const* d_points, int k, void*
 int host_group_sum(int curve, int group, const void* pts, size_t n, void* out);
 // offsets of a batch: k + 1 nondecreasing host entries from 0 (k = 0: nothing to check)
 int check_batch_offsets(const uint64_t* offsets, size_t k);
+// MLHIP_SCALARS_UNIT of include/mlhip.h taken apart (the four batch entry points only): *unit = the flag is set; nonzero: the
+// flag beside other bits of scalars_mont, or beside a scalar array
+int take_unit_scalars(int scalars_mont, const void* scalars, bool* unit);
 void release_plan_pool();  // mlhip_release_cache: the idle pooled plans
 }  // namespace mlhip_rt

@@ -46,6 +46,8 @@
 //                 additions per pair, no doubling (msm_bases_batch.h)
 //   k_point_sum (+ _lp)   plain sums of many points (mlhip_g1_sum / mlhip_g2_sum above their threshold): strided slices per
 //                 lane, then k_msm_batch_sum over the lanes' partials (point_sum.h)
+//   k_sum_batch_slice (+ _lp)   K plain sums per call (mlhip_msm_batch* / mlhip_bases_msm_batch* with MLHIP_SCALARS_UNIT):
+//                 strided slices of <= S points of one segment per lane, then k_msm_batch_sum (msm_sum_batch.h)
 //   host tail     Horner over <= W*c bit positions + one inversion (O(1) work, 64-bit limbs)
 // Launch sequence (msm_plan.h): plan_launch runs an MSM in one pass, stream_begin / stream_tile / stream_end as a train of
 // segments or tiles cut by msm_segments.h (stream_segments, resident_tiles, shared_segments, stream_schedule,
@@ -99,6 +101,7 @@ constexpr int CHUNK_L = 8;            // buckets per level-1 reduction thread
 #include "msm_batch_endo.h"
 #include "msm_batch_bucket.h"
 #include "point_sum.h"
+#include "msm_sum_batch.h"
 #include "msm_bases_batch.h"
 #include "msm_fold.h"
 #include "msm_tail.h"

@@ -43,6 +43,11 @@ int MLHIP_TU_FN(point_sum)(int group, const void* d_points, size_t n, void* d_ou
   if (group == MLHIP_GROUP_G1) return point_sum_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, n, d_out, st);
   return point_sum_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, n, d_out, st);
 }
+int MLHIP_TU_FN(sum_batch)(int group, const void* d_points, bool bases, const uint32_t* base_index, const uint64_t* offsets,
+                          size_t k, void* d_out, hipStream_t st) {
+  if (group == MLHIP_GROUP_G1) return sum_batch_device<MLHIP_TU_CURVE, FpField<MLHIP_TU_CURVE>>(d_points, bases, base_index, offsets, k, d_out, st);
+  return sum_batch_device<MLHIP_TU_CURVE, Fp2Field<MLHIP_TU_CURVE>>(d_points, bases, base_index, offsets, k, d_out, st);
+}
 void MLHIP_TU_FN(release_cache)(void) {
   fixed_base_release();
   msm_batch_release();

@@ -536,6 +536,17 @@ class Curve:
         """the same for points known to be in G2"""
         return self.MultiScalarMulG2Batch(a_lists, b_lists, subgroup=True)
 
+    def SumG1Batch(self, lists: Sequence[Sequence[G1]]) -> List[G1]:
+        """out[i] = SumG1(lists[i]) for many lists in one device call (include/mlhip.h: mlhip_msm_batch with
+        MLHIP_SCALARS_UNIT; include/mlhip_sum_batch.h).  An empty list gives the identity."""
+        raw = _lib.sum_batch(self.id, GROUP_G1, b"".join(p.raw for a in lists for p in a), [len(a) for a in lists])
+        return [G1(r, self) for r in raw]
+
+    def SumG2Batch(self, lists: Sequence[Sequence[G2]]) -> List[G2]:
+        """the same in G2"""
+        raw = _lib.sum_batch(self.id, GROUP_G2, b"".join(p.raw for a in lists for p in a), [len(a) for a in lists])
+        return [G2(r, self) for r in raw]
+
     def Mul2Batch(self, g: Sequence[G1], e: Sequence[Zr], q: Sequence[G1], f: Sequence[Zr]) -> List[G1]:
         """out[i] = g[i].Mul2(e[i], q[i], f[i]): segments of two pairs in one mlhip_msm_batch call"""
         if not (len(g) == len(e) == len(q) == len(f)):
@@ -748,6 +759,23 @@ class Bases:
                     raise IndexError("MultiScalarMulBatch: base index out of range")
         scs = b"".join(c._scalars(b) for b in scalar_lists)
         raw = _lib.bases_msm_batch(self._lib, self._h, self._point_bytes(), scs, c.scalars_mont, lengths, index_lists)
+        return [self._point(r) for r in raw]
+
+    def SumBatch(self, index_lists=None, lengths=None) -> list:
+        """out[i] = sum_j B[index_lists[i][j]], or, without index lists, the sum of the first lengths[i] bases, for many sums
+        over the resident bases in one device call (include/mlhip_sum_batch.h: mlhip_bases_sum_batch).  Exactly one of the
+        two is given; no batch tables are built or read."""
+        if (index_lists is None) == (lengths is None):
+            raise ValueError("SumBatch: give index_lists or lengths")
+        if index_lists is None:
+            lengths = [int(m) for m in lengths]
+            if any(m < 0 or m > self.n for m in lengths):
+                raise IndexError("SumBatch: more points than resident bases")
+        else:
+            lengths = [len(ix) for ix in index_lists]
+            if any(i < 0 or i >= self.n for ix in index_lists for i in ix):
+                raise IndexError("SumBatch: base index out of range")
+        raw = _lib.bases_sum_batch(self._lib, self._h, self._point_bytes(), lengths, index_lists)
         return [self._point(r) for r in raw]
 
     def BatchTabled(self) -> int:
